@@ -13,8 +13,15 @@ batch of the single reference sampler stream, rank r takes rows [128r, 128(r+1))
 A step = forward + backward + (RCCL all-reduce for N>1) + dense TF-Adam, replayed from a
 HIP graph; the id batches are resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel, HIP-event timed) and `cpu_baseline`
-(the oracle's torch-CPU restatement of the same step on the host cores; rank 0, N=1 only)."""
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times exactly K steps and prints the headline
+(`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `config`, ...) and nothing else.  `--full` adds what takes runs of
+its own: `roofline` / `attention` / `kernels` (eager HIP-event pass), the other attention precisions, the other
+BASELINE.json shapes, the C5-table gather block and `cpu_baseline` (the oracle's torch-CPU restatement of the same step
+on the host cores); rank 0, N=1 only for the last four.  `--no-*` flags skip single parts of a `--full` run.
+
+`--dump-outputs DIR` writes what the last timed step left for a caller (loss, AUC, parameters and both Adam moments) as
+DIR/<name>.npy in float32; the run starts from the same parameters and step number whatever the conditioning did,
+so two builds given the same arguments can be compared array for array."""
 import argparse
 import glob
 import json
@@ -24,6 +31,7 @@ import subprocess
 import sys
 import time
 import types
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -350,7 +358,7 @@ def other_configs(steps=100, warmup=10):
     import subprocess
     res = []
     for label, flags in OTHER_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), "--no-cpu-baseline", "--no-gather", "--no-extra-precisions", "--no-other-configs",
+        cmd = [sys.executable, os.path.abspath(__file__), "--full", "--no-cpu-baseline", "--no-gather", "--no-extra-precisions", "--no-other-configs",
                "--steps", str(steps), "--warmup", str(warmup)] + flags              # (a config's own --steps / --warmup come last and win)
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
@@ -458,6 +466,35 @@ def gather_block(reps=24):
     return res
 
 
+DUMP_BYTES = 64_000_000          # --dump-outputs: bytes written at most, all arrays together
+DUMP_WHOLE = 1 << 20             # arrays up to this size are written whole; larger ones share the rest as row samples
+
+
+def dump_outputs(eng, out_dir):
+    """What the last step left for a caller of the training path: loss and AUC (state[5:7]), every parameter and both
+    Adam moments by logical name (float32).  Above DUMP_BYTES in all, the larger arrays are cut to a fixed sample of rows
+    (seeded by the parameter's name, the same rows for the parameter and its moments) named <name>.rows<k>."""
+    arrays = [("loss", eng.state[5:6]), ("auc", eng.state[6:7])]
+    for kind, flat in (("param", eng.P), ("adam_m", eng.Mom), ("adam_v", eng.Vel)):
+        arrays += [("%s.%s" % (kind, n), eng.layout.view(flat, n)) for n in eng.layout.logical_names()]
+    total = sum(t.numel() * 4 for _, t in arrays)
+    big = [n for n, t in arrays if total > DUMP_BYTES and t.numel() * 4 > DUMP_WHOLE]
+    share = (DUMP_BYTES - sum(t.numel() * 4 for n, t in arrays if n not in big)) // max(1, len(big))
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, t in arrays:
+        if name in big:
+            rows = t.shape[0]
+            k = max(1, min(rows, share // (t[0].numel() * 4)))
+            pick = np.sort(np.random.RandomState(zlib.crc32(name.split(".", 1)[1].encode())).choice(rows, k, replace=False))
+            t = t.index_select(0, torch.from_numpy(pick).to(t.device))
+            name = "%s.rows%d" % (name, k)
+        a = t.detach().float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -484,9 +521,15 @@ def main():
     ap.add_argument("--sparse-exchange", default="auto", choices=["auto", "on", "off"], help="DP: item-table gradient exchange")
     ap.add_argument("--condition-ms", type=float, default=15.0, help="untimed steps of the workload run in front of the warm-up steps for this "
                     "many milliseconds (the clock governor's transient after idle, reported as `conditioning`); 0 = none")
-    ap.add_argument("--profile-json", default=None, help="write the per-kernel HIP-event table here")
+    ap.add_argument("--profile-json", default=None, help="write the per-kernel HIP-event table here (needs --full)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the per-kernel roofline pass, the other precisions and "
+                    "shapes, the gather block and the CPU baseline (each can be skipped with its --no-* flag)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's loss, AUC, parameters and Adam "
+                    "moments as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.profile_json and not args.full:
+        ap.error("--profile-json needs --full (the per-kernel pass is part of the full run)")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # this process stays off the GPU: N fresh rank processes of this script, rank 0 prints the JSON line
@@ -538,6 +581,7 @@ def main():
     def run(precision, steps, warmup):
         eng = E.Engine(args.model, corpus.usernum, corpus.itemnum, hyper(args), B, training=True, n_slabs=args.n_slabs,
                        batch_global=Bg, row_offset=rank * B * T, attn_precision=precision, lazy_adam=args.lazy_adam)
+        P0 = eng.P.clone() if dist is None else None          # (the state the conditioning steps are undone to)
         dp = None
         use_graph = not args.no_graph
         staged = torch.from_numpy(np.stack([eng.pack_slot(*hb) for hb in host_batches])).cuda()
@@ -607,6 +651,14 @@ def main():
                     torch.cuda.synchronize()
             torch.cuda.synchronize()
             cond = {"steps": nc, "cold_ms_per_step": round((time.perf_counter() - tc) / nc * 1e3, 4)}
+            if dist is None:
+                # the conditioning ran for a time, not a number of steps: back to the first step's state, so that the warm-up and
+                # timed steps (and --dump-outputs) start from the same parameters, moments and step number in every run
+                eng.P.copy_(P0); eng.Mom.zero_(); eng.Vel.zero_(); eng.Gflat.zero_(); eng.Gs.zero_(); eng.state.zero_()
+                eng.set_step(1)
+                if ring:
+                    eng.load_slot(staged[eng.step_number() % NB])
+                torch.cuda.synchronize()
         conditioning.append(cond)
         def run_steps(n, i0):
             # EXACTLY n steps: whole graphs of spg steps, the rest one step per launch
@@ -642,8 +694,32 @@ def main():
     eng, dp, dt, use_graph = run(args.attn_precision, args.steps, args.warmup)
     loss, auc = eng.loss_auc()
     prec = eng.attn_precision
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(eng, args.dump_outputs)
 
     if rank == 0:
+        cfg = {"workload": "%s-shaped synthetic (%d users, %d items), %s maxlen=%d hidden_units=%d num_blocks=%d "
+                           "num_heads=%d dropout=%.2f, batch %d/GPU (global %d), fwd+bwd+%s TF-Adam per step"
+                           % (args.corpus, corpus.usernum, corpus.itemnum, args.model, T, args.hidden_units, args.num_blocks, args.num_heads,
+                              args.dropout_rate, B, Bg, "row-sparse (lazy)" if args.lazy_adam else "dense"),
+               "parallelism": "dp%d" % world, "hip_graph": use_graph, "steps_per_graph_launch": getattr(run, "spg", 1), "launches_per_step": eng.n_kernel_launches(), "abi_calls_per_step": eng.n_launches(),
+               "attn_precision": prec, "final_loss": round(loss, 5), "final_auc": round(auc, 5)}
+        if dist is not None:
+            cfg["collective"] = {"backend": dist.get_backend(), "ranks": dist.get_world_size(),
+                                 "step": "one HIP graph incl. the collectives" if dp._step_graph is not None else "three HIP graphs, collectives between them (table exchange beside the rest of the backward)",
+                                 "table_exchange": "sparse rows (all-gather)" if dp.sparse else "dense (in the bucket all-reduce)",
+                                 "bucket_floats": int(eng.Gflat.numel())}
+        out = {
+            "metric": "user-sequences/sec (fwd+bwd)", "value": round(Bg * args.steps / dt, 1), "unit": "sequences/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
+            "conditioning": dict(conditioning[0], note="untimed steps of the same workload in front of the W warm-up steps (--condition-ms): the chip's "
+                                 "step time settles ~35 steps after any idle period; cold_ms_per_step = the mean over these first steps"),
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": {"f32": "f32", "bf16x3": "f32 (bf16x3 split MFMA in attention)", "bf16": "bf16 (attention) / f32"}[prec],
+            "data": "synthetic", "config": cfg,
+        }
+
+    if rank == 0 and args.full:
         per_launch, by_name = kernel_profile(eng, run.staged)
         dom = max(by_name.items(), key=lambda kv: kv[1]["us"])
         name, d = dom
@@ -690,29 +766,10 @@ def main():
         if args.profile_json:
             with open(args.profile_json, "w") as f:
                 json.dump(dict(per_launch=per_launch, by_name=by_name, n_launches=eng.n_launches()), f, indent=1, default=str)
-        cfg = {"workload": "%s-shaped synthetic (%d users, %d items), %s maxlen=%d hidden_units=%d num_blocks=%d "
-                           "num_heads=%d dropout=%.2f, batch %d/GPU (global %d), fwd+bwd+%s TF-Adam per step"
-                           % (args.corpus, corpus.usernum, corpus.itemnum, args.model, T, args.hidden_units, args.num_blocks, args.num_heads,
-                              args.dropout_rate, B, Bg, "row-sparse (lazy)" if args.lazy_adam else "dense"),
-               "parallelism": "dp%d" % world, "hip_graph": use_graph, "steps_per_graph_launch": getattr(run, "spg", 1), "launches_per_step": eng.n_kernel_launches(), "abi_calls_per_step": eng.n_launches(),
-               "attn_precision": prec, "final_loss": round(loss, 5), "final_auc": round(auc, 5)}
-        if dist is not None:
-            cfg["collective"] = {"backend": dist.get_backend(), "ranks": dist.get_world_size(),
-                                 "step": "one HIP graph incl. the collectives" if dp._step_graph is not None else "three HIP graphs, collectives between them (table exchange beside the rest of the backward)",
-                                 "table_exchange": "sparse rows (all-gather)" if dp.sparse else "dense (in the bucket all-reduce)",
-                                 "bucket_floats": int(eng.Gflat.numel())}
-        out = {
-            "metric": "user-sequences/sec (fwd+bwd)", "value": round(Bg * args.steps / dt, 1), "unit": "sequences/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
-            "conditioning": dict(conditioning[0], note="untimed steps of the same workload in front of the W warm-up steps (--condition-ms): the chip's "
-                                 "step time settles ~35 steps after any idle period; cold_ms_per_step = the mean over these first steps"),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": {"f32": "f32", "bf16x3": "f32 (bf16x3 split MFMA in attention)", "bf16": "bf16 (attention) / f32"}[prec],
-            "data": "synthetic", "config": cfg, "roofline": roofline, "attention": attn, "kernels": kernels,
-        }
+        out.update(roofline=roofline, attention=attn, kernels=kernels)
     del eng
     torch.cuda.empty_cache()
-    if rank == 0:
+    if rank == 0 and args.full:
         if world == 1 and not args.no_extra_precisions:
             # the same step in the other attention arithmetics (short runs; the headline line above is `attn_precision`)
             others = {}
@@ -733,6 +790,7 @@ def main():
             c1 = cpu_baseline("sasrec", 50, args, host_batches, corpus.usernum, corpus.itemnum, budget_s=8.0)   # BASELINE configs[0]
             c1["config"] = "configs[0]: ml-1m SASRec maxlen=50 hidden_units=50 num_blocks=2 num_heads=1 batch=128"
             out["cpu_baseline_c1"] = c1
+    if rank == 0:
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

@@ -32,7 +32,7 @@ def test_reader_takes_the_reference_runs_records():
     assert ev[-1][0] == 201 and abs(ev[-1][1]["TRAIN/loss"] - 0.38796103) < 1e-7
 
 
-def test_writer_reproduces_tensorflows_bytes():
+def test_writer_reproduces_tensorflows_bytes(tmp_path):
     """Re-encoding every scalar record of the fixture (its own wall time, step, tags, values) gives TensorFlow's bytes."""
     data = open(FIX, "rb").read()
     pos, n_checked = 0, 0
@@ -43,7 +43,7 @@ def test_writer_reproduces_tensorflows_bytes():
         pos += 16 + n
         assert body[0] == (1 << 3 | 1)
         (wall,) = struct.unpack("<d", body[1:9])
-        tmp = os.path.join(os.environ.get("TMPDIR", "/tmp"), "castrec_tb_one.tfevents")
+        tmp = str(tmp_path / "one.tfevents")
         open(tmp, "wb").write(rec)
         got = T.read_events(tmp)
         if not got:
