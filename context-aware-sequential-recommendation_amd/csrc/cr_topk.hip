@@ -1,0 +1,506 @@
+// Full-catalogue top-K (castrec.h cr_score_topk): s[b, i] = q_b . item_i for every item of the table, a per-query top-K and the
+// rank of one target per query, without ever writing the [B, V] score matrix.  Two launches:
+//
+//  * sweep  (grid: query tile x item chunk, 256 threads).  The workgroup splits its QT = 16 QB queries into bf16 hi / lo once and
+//    keeps them in LDS as ready-made B fragments (one 16-byte read per lane, product and k-step).  Each wave streams 16 item rows
+//    of its chunk per round straight from global memory into A fragments (cr_bf16.hpp items: any D >= 8, zero fill past D),
+//    prefetching the next round's rows, and runs v_mfma_f32_16x16x32_bf16 products against every query block: three per k-step
+//    (CR_PREC_BF16X3) or one (CR_PREC_BF16).  A score that reaches its query's running threshold (the K-th best of the chunk so far)
+//    goes to the query's candidate buffer in LDS; after a round, a wave per query folds a buffer that might not hold another
+//    round into the query's sorted top-K (exclusion check, then a merge by ranks), and the threshold rises.  Beside that every
+//    score is compared with the query's target score (integer counts in registers).  The chunk's sorted top-K and count go to the
+//    workspace.
+//  * merge  (a wave per query).  K steps of a tournament over the chunks' sorted lists; the rank: the chunks' counts summed, minus
+//    the distinct excluded items that beat the target (their scores from the same product path).
+//
+// Determinism: a chunk's top-K is the exact top-K of its eligible items under the total order (score desc, id asc), whatever the
+// order in which candidates reached the buffer; the chunk partition is fixed by the shape; counts are integers.
+// One MFMA shape in this file (build.py ISA_CHECKED): v_mfma_f32_16x16x32_bf16.
+#include <algorithm>
+
+#include "cr_bf16.hpp"
+
+namespace {
+
+constexpr int TK_CAP = 128;                 // candidate buffer per query; a round appends at most 64 (4 waves x 16 items)
+constexpr int TK_PAD = 0x7fffffff;          // id of an empty list entry (score -inf): worse than every item
+constexpr int TK_MAX_CHUNKS = 256;
+
+struct TkArgs {
+    const float* q; int64_t ldq;
+    const float* table;
+    int V, D, B, K;
+    const int64_t* off;                     // device copy of the CSR offsets, or null
+    const int32_t* excl;
+    const int32_t* tgt;
+    float* part_s; int32_t* part_id;        // [n_chunks, B, K]
+    int32_t* part_cnt;                      // [n_chunks, B]
+    float* st_ws;                           // [B] target scores (written by chunk 0's workgroups)
+    int32_t* top_ids; float* top_scores; int32_t* rank;
+    int chunk, n_chunks;
+};
+
+// a better than b: higher score, equal scores -> smaller id (empty entries carry TK_PAD, the largest id)
+__device__ __forceinline__ bool tk_better(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
+
+// One row per lane (li) of a 16-row operand, columns 32 ks + 8 lg .. + 7: the cr_bf16.hpp items with an arbitrary row per lane.
+// A lane without a row reads the row-0 columns that end at D (inside the matrix for any shape) and is masked to zero.
+template <int NK>
+__device__ __forceinline__ void tk_row_issue(float (&v)[NK][8], const float* src, int64_t ld, int row, bool rok, bool last, int D) {
+    const int lg = (threadIdx.x & 63) >> 4;
+    const float* p = src + (rok ? (int64_t)row * ld : 0);
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        const int c = 32 * ks + 8 * lg;
+        item_issue(v[ks], p, c, D, !rok || item_fix(rok, last, c, D));
+    }
+}
+template <int NK, bool SPLIT>
+__device__ __forceinline__ void tk_row_finish(float (&v)[NK][8], const float* src, int64_t ld, int row, bool rok, bool last, int D,
+                                              bf8 (&hi)[NK], bf8 (&lo)[NK]) {
+    const int lg = (threadIdx.x & 63) >> 4;
+    const float* p = src + (rok ? (int64_t)row * ld : 0);
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        const int c = 32 * ks + 8 * lg;
+        const bool fix = item_fix(rok, last, c, D);
+        item_mask(v[ks], c, D, rok, fix);
+        if (fix) item_refill(v[ks], p, c, D);          // the partial chunk of the matrix's last row (one lane group of the grid)
+        split8<SPLIT>(v[ks], hi[ks], lo[ks]);
+    }
+}
+
+// The score tile every path of this file uses (sweep, target diagonal, excluded rows): one fixed sequence of products per element,
+// so the same (item, query) pair gets the same bits wherever it sits in a tile.  Lane (li, lg), register r: item row 4 lg + r of the
+// A operand against query column li of the B operand.
+template <int NK, bool SPLIT>
+__device__ __forceinline__ f32x4 tk_tile(const bf8 (&ah)[NK], const bf8 (&al)[NK], const bf8 (&bh)[NK], const bf8 (&bl)[NK]) {
+    f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) c = mma<SPLIT>(ah[ks], al[ks], bh[ks], bl[ks], c);
+    return c;
+}
+
+__device__ __forceinline__ float tk_pick(const f32x4& c, int r) { return r == 0 ? c[0] : r == 1 ? c[1] : r == 2 ? c[2] : c[3]; }
+
+// LDS ordering between the lanes of ONE wave (the fold below runs a wave per query, other waves on other queries)
+__device__ __forceinline__ void tk_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__device__ __forceinline__ bool tk_excluded(const int32_t* excl, int64_t e0, int64_t e1, int id) {
+    bool ex = false;
+    for (int64_t j = e0; j < e1; ++j) ex |= excl[j] == id;           // uniform addresses: one scalar load serves the wave
+    return ex;
+}
+
+struct TkLds {
+    bf8* img_hi; bf8* img_lo;
+    float* top_s; int* top_id;              // [QT, K] sorted best first
+    float* buf_s; int* buf_id;              // [QT, TK_CAP]
+    int* cnt; float* thr; float* st; int* tq;
+    float* scr_s; int* scr_id;              // [4 waves, K]
+};
+__host__ __device__ inline size_t tk_lds_bytes(int QT, int NK, int K) {
+    return (size_t)QT * NK * 64 * 16 * 2 / 16 + (size_t)QT * K * 8 + (size_t)QT * TK_CAP * 8 + (size_t)QT * 16 + (size_t)4 * K * 8;
+}
+__device__ inline TkLds tk_lds(unsigned char* base, int QT, int NK, int K) {
+    TkLds l;
+    l.img_hi = reinterpret_cast<bf8*>(base);
+    l.img_lo = l.img_hi + (QT / 16) * NK * 64;
+    l.top_s = reinterpret_cast<float*>(l.img_lo + (QT / 16) * NK * 64);
+    l.top_id = reinterpret_cast<int*>(l.top_s + QT * K);
+    l.buf_s = reinterpret_cast<float*>(l.top_id + QT * K);
+    l.buf_id = reinterpret_cast<int*>(l.buf_s + QT * TK_CAP);
+    l.cnt = l.buf_id + QT * TK_CAP;
+    l.thr = reinterpret_cast<float*>(l.cnt + QT);
+    l.st = l.thr + QT;
+    l.tq = reinterpret_cast<int*>(l.st + QT);
+    l.scr_s = reinterpret_cast<float*>(l.tq + QT);
+    l.scr_id = reinterpret_cast<int*>(l.scr_s + 4 * K);
+    return l;
+}
+
+// Folds query qi's n buffered candidates into its sorted top-K (one wave).  Excluded candidates are dropped first; then every
+// surviving candidate's place is (better candidates) + (better list entries, a binary search), every list entry's place is its index
+// + (better candidates), and whatever lands below K is written to the wave's scratch and copied back.  Ids are distinct within a chunk,
+// so the places of the real entries are a bijection onto the merged order; empty list entries go last.
+__device__ void tk_fold(const TkLds& l, int qi, int n, int K, const TkArgs& a, int b, int wave) {
+    const int lane = threadIdx.x & 63;
+    float* bs = l.buf_s + qi * TK_CAP;
+    int* bi = l.buf_id + qi * TK_CAP;
+    float* ts = l.top_s + qi * K;
+    int* ti = l.top_id + qi * K;
+    float* ss = l.scr_s + wave * K;
+    int* si = l.scr_id + wave * K;
+    if (a.off) {
+        const int64_t e0 = a.off[b], e1 = a.off[b + 1];
+        for (int i = lane; i < n; i += 64)
+            if (tk_excluded(a.excl, e0, e1, bi[i])) { bs[i] = -INFINITY; bi[i] = TK_PAD; }
+        tk_wave_sync();
+    }
+    for (int i = lane; i < n; i += 64) {
+        const float s = bs[i];
+        const int id = bi[i];
+        if (id == TK_PAD) continue;
+        int pos = 0;
+        for (int j = 0; j < n; ++j) pos += tk_better(bs[j], bi[j], s, id) ? 1 : 0;
+        int lo = 0, hi = K;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (tk_better(ts[mid], ti[mid], s, id)) lo = mid + 1; else hi = mid;
+        }
+        pos += lo;
+        if (pos < K) { ss[pos] = s; si[pos] = id; }
+    }
+    for (int k = lane; k < K; k += 64) {
+        const float s = ts[k];
+        const int id = ti[k];
+        int pos = k;
+        for (int j = 0; j < n; ++j) pos += tk_better(bs[j], bi[j], s, id) ? 1 : 0;
+        if (pos < K) { ss[pos] = s; si[pos] = id; }
+    }
+    tk_wave_sync();
+    for (int k = lane; k < K; k += 64) { ts[k] = ss[k]; ti[k] = si[k]; }
+    tk_wave_sync();
+    if (lane == 0) { l.cnt[qi] = 0; l.thr[qi] = ts[K - 1]; }
+    tk_wave_sync();
+}
+
+template <int NK, int QB, bool SPLIT>
+__global__ __launch_bounds__(256) void k_topk_sweep(TkArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    constexpr int QT = 16 * QB;
+    const int K = a.K;
+    const TkLds l = tk_lds(smem, QT, NK, K);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
+    const int q0 = blockIdx.x * QT;
+    const int nq = min(QT, a.B - q0);
+    const int c0 = blockIdx.y * a.chunk, c1 = min(a.V, c0 + a.chunk);
+
+    // the query tile as B fragments, once
+    for (int qb = wave; qb < QB; qb += 4) {
+        const int row = q0 + qb * 16 + li;
+        const bool rok = row < a.B;
+        float v[NK][8];
+        bf8 h[NK], lo[NK];
+        tk_row_issue<NK>(v, a.q, a.ldq, row, rok, row == a.B - 1, a.D);
+        tk_row_finish<NK, SPLIT>(v, a.q, a.ldq, row, rok, row == a.B - 1, a.D, h, lo);
+#pragma unroll
+        for (int ks = 0; ks < NK; ++ks) {
+            l.img_hi[(qb * NK + ks) * 64 + lane] = h[ks];
+            if (SPLIT) l.img_lo[(qb * NK + ks) * 64 + lane] = lo[ks];
+        }
+    }
+    for (int i = threadIdx.x; i < QT * K; i += 256) { l.top_s[i] = -INFINITY; l.top_id[i] = TK_PAD; }
+    for (int i = threadIdx.x; i < QT; i += 256) {
+        int t = -1;
+        if (a.tgt && i < nq) t = a.tgt[q0 + i];
+        l.tq[i] = (t >= 1 && t < a.V) ? t : -1;
+        l.cnt[i] = 0;
+        l.thr[i] = i < nq ? -INFINITY : INFINITY;          // a query row past B takes no candidates
+        l.st[i] = 0.0f;
+    }
+    __syncthreads();
+
+    // target scores: the diagonal of (target rows of the block's queries) x (the block's queries)
+    if (a.tgt) {
+        for (int qb = wave; qb < QB; qb += 4) {
+            const int t = l.tq[qb * 16 + li];
+            float v[NK][8];
+            bf8 ah[NK], al[NK], bh[NK], bl[NK];
+            tk_row_issue<NK>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D);
+            tk_row_finish<NK, SPLIT>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D, ah, al);
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                bh[ks] = l.img_hi[(qb * NK + ks) * 64 + lane];
+                bl[ks] = SPLIT ? l.img_lo[(qb * NK + ks) * 64 + lane] : bh[ks];
+            }
+            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+            const int r = li - 4 * lg;
+            if (r >= 0 && r < 4) {
+                l.st[qb * 16 + li] = tk_pick(c, r);
+                if (blockIdx.y == 0 && qb * 16 + li < nq) a.st_ws[q0 + qb * 16 + li] = tk_pick(c, r);
+            }
+        }
+        __syncthreads();
+    }
+
+    int rk[QB];
+#pragma unroll
+    for (int qb = 0; qb < QB; ++qb) rk[qb] = 0;
+    const int n_rounds = (c1 - c0 + 63) / 64;
+    float v[NK][8];
+    {
+        const int row = c0 + wave * 16 + li;
+        tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
+    }
+    for (int round = 0; round < n_rounds; ++round) {
+        const int it0 = c0 + round * 64 + wave * 16;
+        bf8 ah[NK], al[NK];
+        {
+            const int row = it0 + li;
+            tk_row_finish<NK, SPLIT>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D, ah, al);
+        }
+        if (round + 1 < n_rounds) {
+            const int row = it0 + 64 + li;
+            tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
+        }
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb) {
+            bf8 bh[NK], bl[NK];
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                bh[ks] = l.img_hi[(qb * NK + ks) * 64 + lane];
+                bl[ks] = SPLIT ? l.img_lo[(qb * NK + ks) * 64 + lane] : bh[ks];
+            }
+            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+            const int qi = qb * 16 + li;
+            const float th = l.thr[qi], s_t = l.st[qi];
+            const int t = l.tq[qi];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int id = it0 + 4 * lg + r;
+                const bool ok = id >= 1 && id < c1;
+                if (ok && c[r] >= th) {
+                    const int k = atomicAdd(&l.cnt[qi], 1);
+                    l.buf_s[qi * TK_CAP + k] = c[r];
+                    l.buf_id[qi * TK_CAP + k] = id;
+                }
+                rk[qb] += (t > 0 && ok && id != t && (c[r] > s_t || (c[r] == s_t && id < t))) ? 1 : 0;
+            }
+        }
+        __syncthreads();
+        // the wave's queries wave, wave + 4, ... : one LDS read for all of them, then a fold per set bit
+        const bool last = round + 1 == n_rounds;
+        const int my_q = wave + 4 * lane;
+        const bool full = my_q < nq && l.cnt[my_q] > (last ? 0 : TK_CAP - 64);
+        for (uint64_t m = __ballot(full); m; m &= m - 1) {
+            const int qi = wave + 4 * (int)__builtin_ctzll(m);
+            tk_fold(l, qi, __builtin_amdgcn_readfirstlane(l.cnt[qi]), K, a, q0 + qi, wave);
+        }
+        __syncthreads();
+    }
+
+    // the chunk's list and target count (every buffer is empty now: cnt[] = 0)
+    const size_t slot = (size_t)blockIdx.y * a.B;
+    for (int i = threadIdx.x; i < nq * K; i += 256) {
+        const int qi = i / K, k = i - qi * K;
+        a.part_s[(slot + q0 + qi) * K + k] = l.top_s[i];
+        a.part_id[(slot + q0 + qi) * K + k] = l.top_id[i];
+    }
+    if (a.tgt) {
+#pragma unroll
+        for (int qb = 0; qb < QB; ++qb)
+            if (rk[qb]) atomicAdd(&l.cnt[qb * 16 + li], rk[qb]);        // integer sums: the same total in any order
+        __syncthreads();
+        for (int i = threadIdx.x; i < nq; i += 256) a.part_cnt[slot + q0 + i] = l.cnt[i];
+    }
+}
+
+// wave-wide best of (s, id): butterfly, every lane ends with the winner
+__device__ __forceinline__ void tk_wave_best(float& s, int& id) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float os = __shfl_xor(s, o, 64);
+        const int oi = __shfl_xor(id, o, 64);
+        if (tk_better(os, oi, s, id)) { s = os; id = oi; }
+    }
+}
+
+template <int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_topk_merge(TkArgs a) {
+    __shared__ float sc[4][16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
+    const int b = blockIdx.x * 4 + wave;
+    if (b >= a.B) return;                                  // wave-uniform; no workgroup barrier below
+    const int K = a.K;
+    constexpr int J = TK_MAX_CHUNKS / 64;
+    int head[J];
+    float hs[J];
+    int hid[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int c = lane + 64 * j;
+        head[j] = 0;
+        const bool ok = c < a.n_chunks;
+        hs[j] = ok ? a.part_s[((size_t)c * a.B + b) * K] : -INFINITY;
+        hid[j] = ok ? a.part_id[((size_t)c * a.B + b) * K] : TK_PAD;
+    }
+    int k = 0;
+    for (; k < K; ++k) {
+        float s = hs[0];
+        int id = hid[0];
+#pragma unroll
+        for (int j = 1; j < J; ++j)
+            if (tk_better(hs[j], hid[j], s, id)) { s = hs[j]; id = hid[j]; }
+        tk_wave_best(s, id);
+        if (id == TK_PAD) break;                           // every list is exhausted
+        if (lane == 0) { a.top_ids[(size_t)b * K + k] = id; a.top_scores[(size_t)b * K + k] = s; }
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if (hid[j] == id) {                            // ids are distinct across chunks: exactly one head holds the winner
+                const int c = lane + 64 * j;
+                const int h = ++head[j];
+                hs[j] = h < K ? a.part_s[((size_t)c * a.B + b) * K + h] : -INFINITY;
+                hid[j] = h < K ? a.part_id[((size_t)c * a.B + b) * K + h] : TK_PAD;
+            }
+    }
+    for (int kk = k + lane; kk < K; kk += 64) { a.top_ids[(size_t)b * K + kk] = 0; a.top_scores[(size_t)b * K + kk] = -INFINITY; }
+
+    if (!a.tgt) return;
+    const int t = a.tgt[b];
+    const int64_t e0 = a.off ? a.off[b] : 0, e1 = a.off ? a.off[b + 1] : 0;
+    int raw = 0;
+    for (int c = lane; c < a.n_chunks; c += 64) raw += a.part_cnt[(size_t)c * a.B + b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) raw += __shfl_xor(raw, o, 64);
+    bool hit_t = false;
+    for (int64_t j = e0 + lane; j < e1; j += 64) hit_t |= a.excl[j] == t;
+    const bool bad = !(t >= 1 && t < a.V) || __any(hit_t);
+    if (bad) {
+        if (lane == 0) a.rank[b] = -1;
+        return;
+    }
+    // distinct excluded items (1 <= e < V, e != t) that beat the target, 16 rows at a time against the query in every column
+    const float s_t = a.st_ws[b];
+    int sub = 0;
+    if (e1 > e0) {
+        float qv[NK][8];
+        bf8 bh[NK], bl[NK];
+        tk_row_issue<NK>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.D);
+        tk_row_finish<NK, SPLIT>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.D, bh, bl);
+        for (int64_t p0 = e0; p0 < e1; p0 += 16) {
+            const int64_t p = p0 + li;
+            const int e = p < e1 ? a.excl[p] : 0;
+            const bool rok = e >= 1 && e < a.V;
+            float v[NK][8];
+            bf8 ah[NK], al[NK];
+            tk_row_issue<NK>(v, a.table, a.D, e, rok, e == a.V - 1, a.D);
+            tk_row_finish<NK, SPLIT>(v, a.table, a.D, e, rok, e == a.V - 1, a.D, ah, al);
+            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+            if (li == 0) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sc[wave][4 * lg + r] = c[r];
+            }
+            tk_wave_sync();
+            bool hit = false;
+            if (lane < 16 && rok && e != t) {
+                const float s = sc[wave][lane];
+                if (s > s_t || (s == s_t && e < t)) {
+                    hit = true;
+                    for (int64_t j = e0; j < p; ++j)
+                        if (a.excl[j] == e) { hit = false; break; }       // counted at its first occurrence
+                }
+            }
+            sub += __popcll(__ballot(hit));
+            tk_wave_sync();
+        }
+    }
+    if (lane == 0) a.rank[b] = raw - sub;
+}
+
+struct TkGeom {
+    int NK, QB, n_qt, n_chunks, chunk;
+    size_t lds;
+};
+
+bool tk_geometry(int B, int V, int D, int K, TkGeom& g) {
+    if (B < 1 || V < 1 || D < 8 || D > 256 || K < 1 || K > CR_TOPK_MAX) return false;
+    const int nk = (D + 31) / 32;
+    g.NK = nk <= 1 ? 1 : nk <= 2 ? 2 : nk <= 4 ? 4 : 8;
+    g.QB = 4;
+    while (g.QB > 1 && (tk_lds_bytes(16 * g.QB, g.NK, K) > 160 * 1024 || 16 * (g.QB / 2) >= B)) g.QB /= 2;
+    g.lds = tk_lds_bytes(16 * g.QB, g.NK, K);
+    if (g.lds > 160 * 1024) return false;
+    g.n_qt = (B + 16 * g.QB - 1) / (16 * g.QB);
+    // about 512 workgroups, chunks of at least 2 048 items (a chunk's first rounds fill its list: short chunks repeat that work)
+    int nc = (512 + g.n_qt - 1) / g.n_qt;
+    nc = std::min(nc, std::min(TK_MAX_CHUNKS, (V + 2047) / 2048));
+    nc = std::max(nc, 1);
+    g.chunk = ((V + nc - 1) / nc + 63) / 64 * 64;
+    g.n_chunks = (V + g.chunk - 1) / g.chunk;
+    return true;
+}
+
+size_t tk_align(size_t x) { return (x + 255) / 256 * 256; }
+
+// workspace: [offsets (B + 1) int64 | target scores B | chunk lists n_chunks B K (float, int32) | chunk counts n_chunks B]
+size_t tk_workspace(int B, const TkGeom& g, int K) {
+    const size_t nb = (size_t)g.n_chunks * B;
+    return tk_align(8 * ((size_t)B + 1)) + tk_align(4 * (size_t)B) + 2 * tk_align(nb * K * 4) + tk_align(nb * 4);
+}
+
+template <int NK, bool SPLIT>
+void tk_launch(const TkArgs& a, const TkGeom& g, hipStream_t st) {
+    const dim3 grid(g.n_qt, g.n_chunks);
+    if (g.QB == 4) hipLaunchKernelGGL((k_topk_sweep<NK, 4, SPLIT>), grid, dim3(256), g.lds, st, a);
+    else if (g.QB == 2) hipLaunchKernelGGL((k_topk_sweep<NK, 2, SPLIT>), grid, dim3(256), g.lds, st, a);
+    else hipLaunchKernelGGL((k_topk_sweep<NK, 1, SPLIT>), grid, dim3(256), g.lds, st, a);
+    hipLaunchKernelGGL((k_topk_merge<NK, SPLIT>), dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+}
+
+}  // namespace
+
+extern "C" size_t cr_score_topk_workspace(int B, int V, int D, int K) {
+    TkGeom g;
+    if (!tk_geometry(B, V, D, K, g)) return 0;
+    return tk_workspace(B, g, K);
+}
+
+extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
+    CR_REQUIRE(d, "cr_score_topk: NULL descriptor");
+    CR_REQUIRE(d->K >= 1 && d->K <= CR_TOPK_MAX, "cr_score_topk: K=%d outside 1 .. CR_TOPK_MAX (%d)", d->K, CR_TOPK_MAX);
+    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_score_topk: D=%d outside 8 .. 256", d->D);
+    CR_REQUIRE(d->B >= 1 && d->V >= 1, "cr_score_topk: B=%d, V=%d must be >= 1", d->B, d->V);
+    CR_REQUIRE(d->ld >= d->D, "cr_score_topk: ld=%d < D=%d", d->ld, d->D);
+    CR_REQUIRE(d->query && d->table, "cr_score_topk: NULL query or table");
+    CR_REQUIRE(d->top_ids && d->top_scores, "cr_score_topk: NULL output (top_ids / top_scores)");
+    CR_REQUIRE(!d->targets || d->rank, "cr_score_topk: targets given but rank is NULL");
+    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
+               "cr_score_topk: unknown precision %d", d->precision);
+    if (d->excl_off) {
+        CR_REQUIRE(d->excl_off[0] >= 0, "cr_score_topk: excl_off[0]=%lld < 0", (long long)d->excl_off[0]);
+        for (int b = 0; b < d->B; ++b)
+            CR_REQUIRE(d->excl_off[b + 1] >= d->excl_off[b], "cr_score_topk: excl_off decreases at row %d (%lld -> %lld)", b,
+                       (long long)d->excl_off[b], (long long)d->excl_off[b + 1]);
+        CR_REQUIRE(d->excl_ids || d->excl_off[d->B] == d->excl_off[0], "cr_score_topk: excl_off names ids but excl_ids is NULL");
+    }
+    TkGeom g;
+    CR_REQUIRE(tk_geometry(d->B, d->V, d->D, d->K, g), "cr_score_topk: unsupported shape");
+    const size_t need = tk_workspace(d->B, g, d->K);
+    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_score_topk: workspace of %zu bytes, cr_score_topk_workspace says %zu",
+               d->workspace ? d->workspace_bytes : (size_t)0, need);
+
+    hipStream_t st = cr_stream(stream);
+    unsigned char* w = static_cast<unsigned char*>(d->workspace);
+    const size_t nb = (size_t)g.n_chunks * d->B;
+    TkArgs a;
+    a.q = d->query; a.ldq = d->ld; a.table = d->table;
+    a.V = d->V; a.D = d->D; a.B = d->B; a.K = d->K;
+    a.off = nullptr;
+    if (d->excl_off && d->excl_off[d->B] > d->excl_off[0]) {
+        int64_t* off = reinterpret_cast<int64_t*>(w);
+        const hipError_t e = hipMemcpyAsync(off, d->excl_off, 8 * ((size_t)d->B + 1), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return cr_set_error(CR_ERR_HIP, "cr_score_topk: offsets copy: %s", hipGetErrorString(e));
+        a.off = off;
+    }
+    w += tk_align(8 * ((size_t)d->B + 1));
+    a.st_ws = reinterpret_cast<float*>(w); w += tk_align(4 * (size_t)d->B);
+    a.part_s = reinterpret_cast<float*>(w); w += tk_align(nb * d->K * 4);
+    a.part_id = reinterpret_cast<int32_t*>(w); w += tk_align(nb * d->K * 4);
+    a.part_cnt = reinterpret_cast<int32_t*>(w);
+    a.excl = d->excl_ids; a.tgt = d->targets;
+    a.top_ids = d->top_ids; a.top_scores = d->top_scores; a.rank = d->rank;
+    a.chunk = g.chunk; a.n_chunks = g.n_chunks;
+    const bool split = d->precision != CR_PREC_BF16;       // CR_PREC_F32: the bf16x3 products (fp32-grade)
+#define TK_NK(NK) (split ? tk_launch<NK, true>(a, g, st) : tk_launch<NK, false>(a, g, st))
+    if (g.NK == 1) TK_NK(1);
+    else if (g.NK == 2) TK_NK(2);
+    else if (g.NK == 4) TK_NK(4);
+    else TK_NK(8);
+#undef TK_NK
+    return cr_check_launch("cr_score_topk");
+}

@@ -1509,6 +1509,36 @@ class Engine:
         O.test_logits(self.seq_emb, self.seq_emb.shape[1], self.p("item_emb"), cand, self.B, self.T, self.D, out)
         return out
 
+    def topk(self, k, excl_off=None, excl_ids=None, targets=None):
+        """Full-catalogue top-k of the last position of every sequence (after forward_eval): (ids [B, k] int32, scores [B, k] fp32,
+        rank [B] int32 or None) as device tensors.  excl_off: host int64 [B + 1] CSR offsets into excl_ids (int32, host or device) --
+        the items each row must not return nor count in its target's rank; targets: [B] ids whose rank among the eligible items is
+        wanted (-1: excluded).  Scores come from bf16x3 products (fp32-grade; plain bf16 on an engine at attn_precision 'bf16');
+        test_logits keeps its exact fp32 form.  castrec.h cr_score_topk."""
+        B, V, D = self.B, self.itemnum + 1, self.D
+        need = O.topk_workspace_bytes(B, V, D, int(k))
+        ws = getattr(self, "_topk_ws", None)
+        if ws is None or ws.numel() < need:
+            ws = self._topk_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+        if excl_ids is not None and not torch.is_tensor(excl_ids):
+            excl_ids = torch.from_numpy(np.ascontiguousarray(excl_ids, np.int32))
+        if excl_ids is not None:
+            excl_ids = excl_ids.to(self.dev, torch.int32).contiguous()
+            if excl_ids.numel() == 0:
+                excl_ids = None
+                excl_off = None
+        if targets is not None:
+            targets = torch.as_tensor(np.asarray(targets, np.int32) if not torch.is_tensor(targets) else targets).to(self.dev, torch.int32).contiguous()
+        ids = torch.empty(B, int(k), dtype=torch.int32, device=self.dev)
+        scores = torch.empty(B, int(k), dtype=torch.float32, device=self.dev)
+        rank = torch.empty(B, dtype=torch.int32, device=self.dev) if targets is not None else None
+        prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
+        se = self.seq_emb
+        ld = se.shape[1]
+        query = se[self.T - 1:]                           # row b of the queries: seq_emb row b * T + T - 1
+        O.score_topk(query, self.T * ld, self.p("item_emb"), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank)
+        return ids, scores, rank
+
     # ---- parameter / gradient access (tests, checkpoints) ----------------------------------------
     def get_params(self):
         return {n: self.layout.view(self.P, n).detach().clone() for n in self.layout.logical_names()}

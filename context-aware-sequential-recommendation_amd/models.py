@@ -181,11 +181,7 @@ class _Model(object):
         if seq.ndim == 1:
             seq = seq[None]
         B = seq.shape[0]
-        key = (B, bool(want_attention))
-        if key not in self._eval:
-            self._eval[key] = Engine(self.name, self.usernum, self.itemnum, self.hp, B, training=False, share=self._owner,
-                                     want_attn=want_attention)
-        eng = self._eval[key]
+        eng = self._eval_engine(B, want_attention)
         z = np.zeros_like(seq)
         f = lambda a: z if a is None else np.asarray(a).reshape(B, -1)
         eng.forward_eval(seq, f(timeseq), f(hours_seq), f(days_seq))
@@ -196,6 +192,49 @@ class _Model(object):
         self.attention_weights = eng.attn_weights
         attn = eng.attn_weights.cpu().numpy() if (want_attention and eng.attn_weights is not None) else None
         return lg.cpu().numpy(), attn
+
+    def _eval_engine(self, B, want_attention):
+        key = (B, bool(want_attention))
+        if key not in self._eval:
+            self._eval[key] = Engine(self.name, self.usernum, self.itemnum, self.hp, B, training=False, share=self._owner,
+                                     want_attn=want_attention)
+        return self._eval[key]
+
+    def recommend(self, u, seq, k=10, timeseq=None, hours_seq=None, days_seq=None, exclude="history", return_scores=True,
+                  targets=None):
+        """The k best items of the whole catalogue for each row of a batch (the last position's scores against every item row,
+        sasrec.py:93-97 extended from a candidate list to the table; castrec.h cr_score_topk).  exclude: "history" (the nonzero ids
+        of each row of seq), None, or one iterable of ids per row.  Returns numpy (ids [B, k], scores [B, k]) -- ids only when
+        return_scores is False -- and, with targets ([B] ids), a third array: each target's 0-based rank among the eligible items
+        (-1 for an excluded target).  Rows with fewer than k eligible items end in id 0, score -inf."""
+        seq = np.asarray(seq)
+        if seq.ndim == 1:
+            seq = seq[None]
+        B = seq.shape[0]
+        eng = self._eval_engine(B, False)
+        z = np.zeros_like(seq)
+        f = lambda a: z if a is None else np.asarray(a).reshape(B, -1)
+        eng.forward_eval(seq, f(timeseq), f(hours_seq), f(days_seq))
+        if isinstance(exclude, str):
+            if exclude != "history":
+                raise ValueError("exclude must be 'history', None or a list of per-row id iterables")
+            rows = [r[r != 0] for r in seq.astype(np.int64)]
+        elif exclude is None:
+            rows = None
+        else:
+            rows = [np.asarray(list(r), np.int64).ravel() for r in exclude]
+            if len(rows) != B:
+                raise ValueError("exclude has %d rows for a batch of %d" % (len(rows), B))
+        off = ids = None
+        if rows is not None:
+            off = np.zeros(B + 1, np.int64)
+            off[1:] = np.cumsum([len(r) for r in rows])
+            ids = np.concatenate(rows).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
+        top, sc, rk = eng.topk(int(k), off, ids, targets)
+        out = (top.cpu().numpy(),) + ((sc.cpu().numpy(),) if return_scores else ())
+        if targets is not None:
+            out = out + (rk.cpu().numpy(),)
+        return out if len(out) > 1 else out[0]
 
     # -- checkpoints (tf.train.Saver, main.py:159,227) ----------------------------------------------
     def state_dict(self):

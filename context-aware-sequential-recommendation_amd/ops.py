@@ -126,6 +126,29 @@ def test_logits(seq_emb, ld, table, cand, B, T, D, logits):
            cand.shape[1], _p(logits), _stream())
 
 
+def topk_workspace_bytes(B, V, D, K):
+    n = L.lib.cr_score_topk_workspace(B, V, D, K)
+    if n == 0:
+        raise ValueError("cr_score_topk: unsupported shape B=%d V=%d D=%d K=%d (1 <= K <= %d, 8 <= D <= 256)" % (B, V, D, K, L.CR_TOPK_MAX))
+    return n
+
+
+def score_topk(query, ld, table, B, K, precision, excl_off, excl_ids, targets, workspace, top_ids, top_scores, rank=None):
+    """cr_score_topk: query rows query + b * ld (a float32 CUDA tensor's storage), table [V, D]; excl_off a host int64 numpy array
+    [B + 1] or None, excl_ids an int32 CUDA tensor; workspace a uint8 CUDA tensor of at least topk_workspace_bytes bytes."""
+    import numpy as np
+    off = None
+    if excl_off is not None:
+        off = np.ascontiguousarray(excl_off, np.int64)
+        if off.shape != (B + 1,):
+            raise ValueError("excl_off must have B + 1 = %d entries, got %s" % (B + 1, off.shape))
+    d = L.TopkDesc(_p(_f32(query, "query")), ld, _p(_f32(table, "table")), table.shape[0], table.shape[1], B, K, precision,
+                   None if off is None else off.ctypes.data, _p(_i32(excl_ids, "excl_ids")), _p(_i32(targets, "targets")),
+                   _p(_i32(top_ids, "top_ids")), _p(_f32(top_scores, "top_scores")), _p(_i32(rank, "rank")),
+                   _p(workspace), workspace.numel() * workspace.element_size())
+    L.call("cr_score_topk", C.byref(d), _stream())
+
+
 def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, state, beta1=0.9, beta2=0.98, eps=1e-8,
               stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None):
     d = L.AdamDesc(_p(p), _p(m), _p(v), _p(table_grad), _p(dense_slabs), n_table, n_dense, n_slabs, lr, beta1, beta2,

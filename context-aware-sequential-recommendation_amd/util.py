@@ -143,8 +143,9 @@ def train_corpus(train, usernum, itemnum):
 
 
 # ---------------------------------------------------------------------------------------------------
-def _eval_inputs(train, valid, test, u, mode, args, itemnum, min_td, max_td):
-    """One user's predict() inputs (util.py:245-315 / 355-415); candidates come from np.random (global)."""
+def _eval_inputs(train, valid, test, u, mode, args, itemnum, min_td, max_td, draw=True):
+    """One user's predict() inputs (util.py:245-315 / 355-415); candidates come from np.random (global).  draw=False: no candidates
+    are drawn (np.random is not touched) and the last element is (target id, the `rated` set the negatives are drawn outside of)."""
     target = test if mode == "test" else valid
     if len(train[u]) < 1 or len(target[u]) < 1:
         return None
@@ -170,7 +171,7 @@ def _eval_inputs(train, valid, test, u, mode, args, itemnum, min_td, max_td):
                                            min_td, max_td)
     rated = set(_ev(e)[0] for e in train[u]); rated.add(0)   # util.py:291-298
     item_idx = [_ev(target[u][0])[0]]
-    for _ in range(100):
+    for _ in range(100 if draw else 0):
         t = np.random.randint(1, itemnum + 1)
         while t in rated:
             t = np.random.randint(1, itemnum + 1)
@@ -180,6 +181,8 @@ def _eval_inputs(train, valid, test, u, mode, args, itemnum, min_td, max_td):
             raise Exception("test_seq_len is not provided")
         n = min(args.test_seq_len, args.maxlen)
         seq[:-n] = 0; timeseq[:-n] = 0; hours[:-n] = 0; days[:-n] = 0
+    if not draw:
+        return seq, timeseq, hours, days, (item_idx[0], rated)
     return seq, timeseq, hours, days, np.asarray(item_idx, np.int32)
 
 
@@ -228,3 +231,50 @@ def evaluate(model, dataset, args, sess=None):
 def evaluate_valid(model, dataset, args, sess=None):
     """util.py:342-430: validation split."""
     return _evaluate(model, dataset, args, "valid")
+
+
+def _eval_users(usernum):
+    """The users _evaluate's next call will sample (util.py:241-244), without moving the `random` module's state."""
+    if usernum > 10000:
+        st = random.getstate()
+        users = random.sample(range(1, usernum + 1), 10000)
+        random.setstate(st)
+        return users
+    return range(1, usernum + 1)
+
+
+def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256):
+    """Full-ranking form of _evaluate: the same users (those its next call samples) and inputs, the target ranked against EVERY item outside the user's `rated`
+    set (the set the sampled evaluator draws its 100 negatives outside of) instead of against 100 of them.  Draws nothing from
+    np.random.  rank = #{eligible i : s_i > s_t} + #{eligible i != t : s_i == s_t, i < t} (castrec.h cr_score_topk)."""
+    train, valid, test, usernum, itemnum = dataset[0], dataset[1], dataset[2], dataset[3], dataset[4]
+    min_td, max_td = get_delta_range(train)
+    rows = []
+    for u in _eval_users(usernum):
+        r = _eval_inputs(train, valid, test, u, mode, args, itemnum, min_td, max_td, draw=False)
+        if r is not None:
+            rows.append((u,) + r)
+    NDCG = HT = 0.0
+    for i in range(0, len(rows), eval_batch):
+        chunk = rows[i:i + eval_batch]
+        us = [c[0] for c in chunk]
+        seq, ts, hrs, dys = (np.stack([c[j] for c in chunk]) for j in range(1, 5))
+        tgt = np.array([c[5][0] for c in chunk], np.int32)
+        excl = [sorted(c[5][1] - {c[5][0]}) for c in chunk]     # the target itself always competes (as item_idx[0] does)
+        _, _, rank = model.recommend(us, seq, k=k, timeseq=ts, hours_seq=hrs, days_seq=dys, exclude=excl, targets=tgt)
+        for rk in rank:
+            if 0 <= rk < k:
+                NDCG += 1 / np.log2(rk + 2)
+                HT += 1
+    n = float(len(rows))
+    return NDCG / n, HT / n
+
+
+def evaluate_full(model, dataset, args, sess=None, k=10):
+    """(NDCG@k, HR@k) of the test split over the full catalogue (see _evaluate_full)."""
+    return _evaluate_full(model, dataset, args, "test", k)
+
+
+def evaluate_valid_full(model, dataset, args, sess=None, k=10):
+    """(NDCG@k, HR@k) of the validation split over the full catalogue."""
+    return _evaluate_full(model, dataset, args, "valid", k)

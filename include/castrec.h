@@ -434,6 +434,40 @@ int cr_stack_fwd_head(const cr_stack_desc* d, const cr_head_desc* h, const cr_ln
 int cr_test_logits(const float* seq_emb, int ld, const float* table, const int32_t* cand,
                    int B, int T, int D, int V, int n_cand, float* logits, void* stream);
 
+/* ---- full-catalogue top-K (csrc/cr_topk.hip) -----------------------------------------------------------------------
+ * s[b, i] = query[b, :] . table[i, :] for every item i = 1 .. V-1 (row 0 is the padding row and is never returned); per query
+ * the K best items that its exclusion list does not name, without forming [B, V]: a fused GEMM + selection sweep over the table
+ * in item chunks, then a merge of the per-chunk lists.  Both launches are deterministic (no float atomics; the chunks do not
+ * depend on timing): two calls return the same bits.
+ *   - query row b = query + b * ld (ld >= D floats: an engine's last positions are seq_emb + (T - 1) * ld_seq with ld = T * ld_seq).
+ *   - outputs sorted by score descending, equal scores by smaller id first; fewer than K eligible items: id 0, score -inf.
+ *   - exclusions: CSR, excl_off a HOST array [B + 1] (non-decreasing, read before the call returns), excl_ids a device array;
+ *     a row may be unsorted, hold duplicates, 0 or ids >= V.  excl_off == NULL: no exclusions.
+ *   - targets (optional, device [B]): rank[b] = #{eligible i != t : s_i > s_t} + #{eligible i != t : s_i == s_t, i < t}, with s_t
+ *     from the same products as the sweep's; -1 when t is excluded or outside 1 .. V-1.
+ *   - precision: CR_PREC_BF16X3 (three bf16 products per term: fp32-grade scores) or CR_PREC_BF16 (one); CR_PREC_F32 takes the
+ *     bf16x3 path (cr_test_logits keeps its exact fp32 form).
+ *   - shapes: 1 <= K <= CR_TOPK_MAX, 8 <= D <= 256, V >= 1, B >= 1.
+ *   - workspace: at least cr_score_topk_workspace(B, V, D, K) bytes of device memory (workspace_bytes says how many there are). */
+#define CR_TOPK_MAX 128
+typedef struct cr_topk_desc cr_topk_desc;
+struct cr_topk_desc {
+    const float* query; int ld;       /* [B] rows of D floats, pitch ld */
+    const float* table;               /* [V, D] */
+    int V, D, B, K;
+    int precision;                    /* CR_PREC_* */
+    const int64_t* excl_off;          /* host [B + 1] or NULL */
+    const int32_t* excl_ids;          /* device [excl_off[B]] */
+    const int32_t* targets;           /* device [B] or NULL */
+    int32_t* top_ids;                 /* device [B, K] */
+    float* top_scores;                /* device [B, K] */
+    int32_t* rank;                    /* device [B]; required with targets */
+    void* workspace;
+    size_t workspace_bytes;
+};
+size_t cr_score_topk_workspace(int B, int V, int D, int K);    /* 0 for a shape outside the supported range */
+int cr_score_topk(const cr_topk_desc* d, void* stream);
+
 /* ---- occurrence index of a batch (round 5; csrc/cr_index.cpp, csrc/cr_tgrad.hip) ---------------------------------
  * The gradient of a looked-up table row is the sum of the gradient rows of every position that looked it up: the three
  * lookups of the item table (seq ids: modules.py:157 through sasrec.py:27; pos / neg ids: sasrec.py:89-90) and the learned

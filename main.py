@@ -25,7 +25,7 @@ from castrec_amd.engine import MODELS  # noqa: E402
 from castrec_amd.models import build_model  # noqa: E402
 from castrec_amd.sampler import WarpSampler  # noqa: E402
 from castrec_amd.tb_events import EventWriter  # noqa: E402
-from castrec_amd.util import data_partition, evaluate, evaluate_valid, partition, train_corpus  # noqa: E402
+from castrec_amd.util import data_partition, evaluate, evaluate_full, evaluate_valid, evaluate_valid_full, partition, train_corpus  # noqa: E402
 
 
 def parse_args(argv=None):
@@ -53,6 +53,8 @@ def parse_args(argv=None):
     parser.add_argument('--input_context', type=bool, default=False)
     parser.add_argument('--model', default="cast_1", required=True, help="model to use from" + str(MODELS))
     parser.add_argument('--eval_every', type=int, default=20, help='evaluate + checkpoint every N epochs (reference: 20)')
+    parser.add_argument('--eval_full_ranking', action='store_true',
+                        help='also log NDCG@10 / HR@10 over the full catalogue (every item outside the user\'s rated set) at each evaluation')
     return parser.parse_args(argv)
 
 
@@ -112,8 +114,11 @@ def main(argv=None):
             u, seq, pos, neg, timeseq, ratings_seq, hours_seq, days_seq, _ = sampler.next_batch()
             auc, loss = model.train_step(u, seq, pos, neg, timeseq, hours_seq, days_seq)   # the reference's one-train-step quirk
             print(auc); print(loss)
+            f_test = evaluate_full(model, dataset, args) if args.eval_full_ranking else None   # (same users: it restores `random`)
             t_test = evaluate(model, dataset, args)
             logger.info('test (NDCG@10: %.4f, HR@10: %.4f)' % (t_test[0], t_test[1]))
+            if f_test is not None:
+                logger.info('test full ranking (NDCG@10: %.4f, HR@10: %.4f)' % (f_test[0], f_test[1]))
             with open(os.path.join(args.test_model, 'test_seq_len.txt'), 'a') as f:
                 f.write('{},{},{}\n'.format(args.test_seq_len, t_test[0], t_test[1]))
         else:
@@ -171,10 +176,15 @@ def main(argv=None):
                 logger.info('Model saved in path: %s' % model.save(save_path))
                 logger.info('Evaluating')
                 T += time.time() - t0
+                f_test = evaluate_full(model, dataset, args) if args.eval_full_ranking else None
                 t_test = evaluate(model, dataset, args)
+                f_valid = evaluate_valid_full(model, dataset, args) if args.eval_full_ranking else None
                 t_valid = evaluate_valid(model, dataset, args)
                 logger.info('epoch:%d, time: %f(s), valid (NDCG@10: %.4f, HR@10: %.4f), test (NDCG@10: %.4f, HR@10: %.4f)' % (
                     epoch, T, t_valid[0], t_valid[1], t_test[0], t_test[1]))
+                if f_test is not None:
+                    logger.info('epoch:%d, full ranking: valid (NDCG@10: %.4f, HR@10: %.4f), test (NDCG@10: %.4f, HR@10: %.4f)' % (
+                        epoch, f_valid[0], f_valid[1], f_test[0], f_test[1]))
                 f.write(str(tuple(float(x) for x in t_valid)) + ' ' + str(tuple(float(x) for x in t_test)) + '\n')   # plain floats, as main.py:238 prints under numpy 1.16
                 f.flush()
                 writer.add_scalars(epoch, {'VALID/NDCG@10': float(t_valid[0]), 'VALID/HR@10': float(t_valid[1]),

@@ -20,7 +20,7 @@ out = os.path.join(root, "profiles")
 
 
 def short(name):
-    name = name.replace("void ", "")
+    name = name.replace("void ", "").replace("(anonymous namespace)::", "")
     return name.split("(")[0]
 
 
