@@ -43,43 +43,7 @@ struct TkArgs {
 // a better than b: higher score, equal scores -> smaller id (empty entries carry TK_PAD, the largest id)
 __device__ __forceinline__ bool tk_better(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
 
-// One row per lane (li) of a 16-row operand, columns 32 ks + 8 lg .. + 7: the cr_bf16.hpp items with an arbitrary row per lane.
-// A lane without a row reads the row-0 columns that end at D (inside the matrix for any shape) and is masked to zero.
-template <int NK>
-__device__ __forceinline__ void tk_row_issue(float (&v)[NK][8], const float* src, int64_t ld, int row, bool rok, bool last, int D) {
-    const int lg = (threadIdx.x & 63) >> 4;
-    const float* p = src + (rok ? (int64_t)row * ld : 0);
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-        const int c = 32 * ks + 8 * lg;
-        item_issue(v[ks], p, c, D, !rok || item_fix(rok, last, c, D));
-    }
-}
-template <int NK, bool SPLIT>
-__device__ __forceinline__ void tk_row_finish(float (&v)[NK][8], const float* src, int64_t ld, int row, bool rok, bool last, int D,
-                                              bf8 (&hi)[NK], bf8 (&lo)[NK]) {
-    const int lg = (threadIdx.x & 63) >> 4;
-    const float* p = src + (rok ? (int64_t)row * ld : 0);
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-        const int c = 32 * ks + 8 * lg;
-        const bool fix = item_fix(rok, last, c, D);
-        item_mask(v[ks], c, D, rok, fix);
-        if (fix) item_refill(v[ks], p, c, D);          // the partial chunk of the matrix's last row (one lane group of the grid)
-        split8<SPLIT>(v[ks], hi[ks], lo[ks]);
-    }
-}
-
-// The score tile every path of this file uses (sweep, target diagonal, excluded rows): one fixed sequence of products per element,
-// so the same (item, query) pair gets the same bits wherever it sits in a tile.  Lane (li, lg), register r: item row 4 lg + r of the
-// A operand against query column li of the B operand.
-template <int NK, bool SPLIT>
-__device__ __forceinline__ f32x4 tk_tile(const bf8 (&ah)[NK], const bf8 (&al)[NK], const bf8 (&bh)[NK], const bf8 (&bl)[NK]) {
-    f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) c = mma<SPLIT>(ah[ks], al[ks], bh[ks], bl[ks], c);
-    return c;
-}
+// (tk_row_issue / tk_row_finish / tk_tile: cr_bf16.hpp, shared with cr_ce.hip)
 
 __device__ __forceinline__ float tk_pick(const f32x4& c, int r) { return r == 0 ? c[0] : r == 1 ? c[1] : r == 2 ? c[2] : c[3]; }
 

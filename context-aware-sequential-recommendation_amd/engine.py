@@ -28,6 +28,9 @@ from . import ops as O
 # split operands (three products, ~1e-5 relative: inside the 1e-3 fp32 bound); "bf16" = plain bf16 operands
 ATTN_PRECISIONS = {"f32": L.PREC_F32, "bf16x3": L.PREC_BF16X3, "bf16": L.PREC_BF16}
 DEFAULT_ATTN_PRECISION = "bf16x3"
+# training objectives: "bce" the reference's pos / neg dot-product BCE with one sampled negative per position (cr_head_fwd_bwd);
+# "ce" softmax cross-entropy over the whole item catalogue (cr_softmax_ce)
+LOSSES = ("bce", "ce")
 
 MODELS = ["cast_1", "cast_2", "cast_3", "cast_4", "cast_5", "cast_6", "cast_7", "cast_8", "cast_9",
           "sasrec", "sasrec_static"]          # main.py:28
@@ -51,7 +54,7 @@ class Hyper:
 
     def __init__(self, args=None, **kw):
         d = dict(maxlen=50, hidden_units=50, num_blocks=2, num_heads=1, dropout_rate=0.5, l2_emb=0.0, lr=1e-3,
-                 max_bins=200, num_context_blocks=2, seed=42)
+                 max_bins=200, num_context_blocks=2, seed=42, loss="bce")
         for k in d:
             if args is not None and hasattr(args, k):
                 d[k] = getattr(args, k)
@@ -180,7 +183,12 @@ class ParamLayout:
 class Engine:
     def __init__(self, model, usernum, itemnum, hp, batch_size, training=True, seed=None, n_slabs=None,
                  share=None, batch_global=None, row_offset=0, want_attn=False, device="cuda", fused=None,
-                 attn_precision=None, lazy_adam=None):
+                 attn_precision=None, lazy_adam=None, loss=None):
+        """loss: the training objective, "bce" (the default: hp.loss, else "bce") or "ce" -- full-catalogue softmax cross-entropy
+        (cr_softmax_ce).  Under "ce" the prediction head is one cr_softmax_ce launch that stores d(seq_emb) and accumulates the item
+        table's gradient into Gt; the occurrence index and the head fusions are off, so the embedding backward scatters with float
+        atomics and bitwise_reproducible is False.  "ce" refuses row-sparse Adam, data parallelism and hidden sizes outside 8..256
+        (ValueError).  Eval engines ignore the option."""
         if model not in MODELS:
             raise ValueError("model must be one of %s" % MODELS)
         if not torch.cuda.is_available():
@@ -200,6 +208,18 @@ class Engine:
         # row-sparse Adam on the item table (DEVIATION from the reference's dense update, for tables like C5's 10 M rows;
         # castrec.h cr_adam_desc.lazy_ids): off unless asked for
         self.lazy_adam = bool(int(os.environ.get("CASTREC_LAZY_ADAM", "0"))) if lazy_adam is None else bool(lazy_adam)
+        if loss is None:
+            loss = getattr(hp, "loss", None) or "bce"
+        if loss not in LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (LOSSES, loss))
+        self.loss = loss if training else "bce"
+        if self.loss == "ce":
+            if self.lazy_adam:
+                raise ValueError("loss='ce' does not take row-sparse Adam (lazy_adam): every item row has a gradient")
+            if (batch_global is not None and batch_global != batch_size) or row_offset:
+                raise ValueError("loss='ce' does not take data parallelism (the item table's gradient is not in the exchanged bucket)")
+            if not 8 <= hp.hidden_units <= 256:
+                raise ValueError("loss='ce' needs 8 <= hidden_units <= 256 (cr_softmax_ce), got %d" % hp.hidden_units)
         self.M = self.B * self.T
         self.usernum, self.itemnum = usernum, itemnum
         self.training = training
@@ -220,7 +240,7 @@ class Engine:
         self._grad2 = {}
         self._grad2_bufs = {}                         # data_ptr -> (activation buffer, second-addend buffer)
         self._block_bwd_ranges = []                   # slab-0 float ranges written by cr_stack_block_bwd (one slab per sequence)
-        self.fuse_head_ln = os.environ.get("CASTREC_NO_HEAD_LN") != "1"
+        self.fuse_head_ln = os.environ.get("CASTREC_NO_HEAD_LN") != "1" and self.loss == "bce"
         self._check_ids = os.environ.get("CASTREC_NO_ID_CHECK") != "1"
         self.fused = (4 <= hp.hidden_units <= 64) if fused is None else bool(fused)
         if self.fused and not 4 <= hp.hidden_units <= 64:
@@ -265,6 +285,9 @@ class Engine:
             self.Gflat = torch.zeros(lay.n_total + 4, **f32)
             self.Gt = self.Gflat[:lay.n_table]
             self.Gs = torch.zeros(n_slabs, max(lay.n_dense, 1), **f32)
+            if self.loss == "ce":
+                nb = O.softmax_ce_workspace_bytes(self.M, itemnum + 1, self.D)
+                self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
         self.drop = O.Drop(hp.dropout_rate if training else 0.0, self.seed, self.state, row_offset)
         self.batch_global = self.B if batch_global is None else batch_global
         self.want_attn = want_attn
@@ -282,7 +305,7 @@ class Engine:
         # head and the embedding backward.  Off (CASTREC_NO_INDEX=1, row-sparse Adam, hidden sizes the gather does not take): the
         # atomics of rounds 1-4.
         ng, ent = C.c_int(0), C.c_int(0)                        # the gather's geometry at this hidden size (0: a size it does not take)
-        self.use_index = bool(training and not self.lazy_adam and os.environ.get("CASTREC_NO_INDEX") != "1"
+        self.use_index = bool(training and not self.lazy_adam and self.loss == "bce" and os.environ.get("CASTREC_NO_INDEX") != "1"
                               and L.lib.cr_tgrad_geometry(self.D, C.byref(ng), C.byref(ent)))
         self.ids_words = 6 * self.M
         self.index_off = (self.ids_words + 3) // 4 * 4
@@ -972,6 +995,17 @@ class Engine:
         M, D = self.M, self.D
         self.seq_emb = seq_emb
         if not self.training:
+            return
+        if self.loss == "ce":
+            # full-catalogue softmax cross-entropy: d(seq_emb) is stored (the final LayerNorm's / the MLP's backward reads it), the
+            # item table's gradient goes into Gt -- the head route of CASTREC_NO_HEAD_LN=1 with CASTREC_NO_INDEX=1
+            ds = self._grad_of(seq_emb)
+            self._grad_written.add(id(ds))
+            prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
+            d = L.SoftmaxCeDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
+                                self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, prec, self.state.data_ptr(), ds.data_ptr(), ds.shape[1],
+                                self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
+            self._call(self.fwd, "cr_softmax_ce", C.byref(d))
             return
         rec = self._ln_recipe.get(seq_emb.data_ptr()) if self.fuse_head_ln else None
         if rec is not None:

@@ -149,6 +149,12 @@ class TopkDesc(C.Structure):
                 ("workspace", c_p), ("workspace_bytes", C.c_size_t)]
 
 
+class SoftmaxCeDesc(C.Structure):
+    _fields_ = [("seq_emb", c_p), ("ld", c_i), ("table", c_p), ("pos", c_p), ("neg", c_p), ("M", c_i), ("D", c_i), ("V", c_i),
+                ("precision", c_i), ("state", c_p), ("d_seq_emb", c_p), ("ldd", c_i), ("table_grad", c_p), ("lse_out", c_p),
+                ("workspace", c_p), ("workspace_bytes", C.c_size_t)]
+
+
 def _sig(name, restype, argtypes):
     f = getattr(_lib, name)
     f.restype = restype
@@ -220,6 +226,8 @@ _sig("cr_index_builder_destroy", None, [c_p])
 _sig("cr_table_grad", c_i, [C.POINTER(TgradDesc), c_p, c_p])
 _sig("cr_score_topk_workspace", C.c_size_t, [c_i, c_i, c_i, c_i])
 _sig("cr_score_topk", c_i, [C.POINTER(TopkDesc), c_p])
+_sig("cr_softmax_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
+_sig("cr_softmax_ce", c_i, [C.POINTER(SoftmaxCeDesc), c_p])
 
 EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "cr_embed_fwd", "cr_embed_bwd", "cr_layernorm_fwd",
            "cr_layernorm_bwd", "cr_gemm_rows", "cr_gemm_wgrad", "cr_eltwise", "cr_attn_fwd", "cr_attn_bwd",
@@ -228,7 +236,7 @@ EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "
            "cr_head_fwd_bwd", "cr_head_fwd_bwd_ln", "cr_stack_fwd_head_supported", "cr_stack_fwd_head", "cr_test_logits", "cr_adam_step", "cr_reduce_slabs", "cr_l2_penalty", "cr_graph_begin", "cr_graph_end", "cr_graph_launch",
            "cr_graph_destroy", "cr_sampler_create", "cr_sampler_next", "cr_sampler_destroy",
            "cr_tgrad_geometry", "cr_batch_index_layout", "cr_index_builder_create", "cr_index_build", "cr_index_builder_destroy", "cr_table_grad",
-           "cr_score_topk_workspace", "cr_score_topk"]
+           "cr_score_topk_workspace", "cr_score_topk", "cr_softmax_ce_workspace", "cr_softmax_ce"]
 
 lib = _lib
 

@@ -149,6 +149,26 @@ def score_topk(query, ld, table, B, K, precision, excl_off, excl_ids, targets, w
     L.call("cr_score_topk", C.byref(d), _stream())
 
 
+def softmax_ce_workspace_bytes(M, V, D):
+    n = L.lib.cr_softmax_ce_workspace(M, V, D)
+    if n == 0:
+        raise ValueError("cr_softmax_ce: unsupported shape M=%d V=%d D=%d (M >= 1, V >= 2, 8 <= D <= 256)" % (M, V, D))
+    return n
+
+
+def softmax_ce(seq_emb, ld, table, pos, state, workspace, M, precision=L.PREC_BF16X3, neg=None, d_seq_emb=None, ldd=0,
+               table_grad=None, lse_out=None):
+    """cr_softmax_ce: rows seq_emb + m * ld (m < M) of a float32 CUDA tensor's storage against table [V, D]; pos / neg int32 [M];
+    state the float32 [CR_STATE_FLOATS] block ([0..2] += the loss / AUC / target sums, snapshot [8..11]); d_seq_emb (rows of pitch
+    ldd) written, table_grad accumulated, lse_out [M] written where given; workspace a uint8 CUDA tensor of at least
+    softmax_ce_workspace_bytes(M, V, D) bytes."""
+    d = L.SoftmaxCeDesc(_p(_f32(seq_emb, "seq_emb")), ld, _p(_f32(table, "table")), _p(_i32(pos, "pos")), _p(_i32(neg, "neg")),
+                        M, table.shape[1], table.shape[0], precision, _p(_f32(state, "state")), _p(_f32(d_seq_emb, "d_seq_emb")), ldd,
+                        _p(_f32(table_grad, "table_grad")), _p(_f32(lse_out, "lse_out")), _p(workspace),
+                        workspace.numel() * workspace.element_size())
+    L.call("cr_softmax_ce", C.byref(d), _stream())
+
+
 def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, state, beta1=0.9, beta2=0.98, eps=1e-8,
               stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None):
     d = L.AdamDesc(_p(p), _p(m), _p(v), _p(table_grad), _p(dense_slabs), n_table, n_dense, n_slabs, lr, beta1, beta2,

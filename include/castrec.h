@@ -56,9 +56,9 @@ typedef struct {
 
 /* ---- per-step device state ---------------------------------------------------- */
 /* state (device, CR_STATE_FLOATS floats):
- *   [0] loss_sum  [1] auc_sum  [2] n_target  (accumulated by cr_head_fwd_bwd)
+ *   [0] loss_sum  [1] auc_sum  [2] n_target  (accumulated by cr_head_fwd_bwd, or cr_softmax_ce)
  *   [3] reserved  [4] step counter (uint32 bits)  [5] loss  [6] auc (written by cr_adam_step)
- *   [8] [9] [10] copies of [0] [1] [2] and [11] a copy of [4], taken by the LAST workgroup of cr_head_fwd_bwd(_ln)
+ *   [8] [9] [10] copies of [0] [1] [2] and [11] a copy of [4], taken by the LAST workgroup of cr_head_fwd_bwd(_ln) (or cr_softmax_ce)
  *   to finish (ticket in [12]): a consistent snapshot that later kernels may read while [0..4] move on.
  * Two ways to drive a step:
  *   - cr_step_begin first (zeroes [0..3], increments [4]), cr_adam_step with step_snapshot == NULL; or
@@ -467,6 +467,42 @@ struct cr_topk_desc {
 };
 size_t cr_score_topk_workspace(int B, int V, int D, int K);    /* 0 for a shape outside the supported range */
 int cr_score_topk(const cr_topk_desc* d, void* stream);
+
+/* ---- full-catalogue softmax cross-entropy (csrc/cr_ce.hip) ----------------------------------------------------------
+ * The training objective over the whole item table, an alternative to cr_head_fwd_bwd's one-negative BCE.  Rows m = 0 .. M-1,
+ * h_m = seq_emb row m, E = table [V, D], istarget_m = (pos[m] != 0):
+ *   s_mv = h_m . E_v for the items v = 1 .. V-1 (row 0 is padding: excluded from the softmax, not a zero score);
+ *   l_m = logsumexp_v s_mv - s_{m,pos_m};  p_mv = softmax_v(s_mv).
+ *   state[0] += sum_m istarget_m l_m, [1] += sum_m istarget_m (sign(s_{m,pos_m} - s_{m,neg_m}) + 1) / 2 (the training AUC of the
+ *   sampled negatives; neg id 0 reads as a zero score; neg == NULL adds 0), [2] += sum_m istarget_m.  Then the snapshot [8..11] as
+ *   cr_head_fwd_bwd takes it (ticket [12] left at 0): cr_adam_step runs unchanged with step_snapshot = state + 11.
+ *   d_seq_emb (optional, WRITTEN): dh_m = istarget_m (sum_v p_mv E_v - E_{pos_m}), zero rows where pos is 0.
+ *   table_grad (optional, ACCUMULATED, rows 1 .. V-1; row 0 is never written): dE_v += sum_m istarget_m (p_mv - [v = pos_m]) h_m.
+ *   Gradients are un-normalised (times n_target), as cr_head_desc's.  `neg` never enters them.
+ *   lse_out (optional, [M]): logsumexp_v s_mv of every row.
+ * The [M, V] scores are never stored: a row sweep forms the log-sum-exp, a second recomputes the scores for dh, an item sweep over
+ * the rows recomputes them for dE (all three from one product sequence, cr_score_topk's: the p of the backward is the p the
+ * log-sum-exp saw).  No float atomics; the partition is fixed by the shape: two calls give the same bits, sums included.
+ *   - precision: CR_PREC_BF16X3 (three bf16 products per term: fp32-grade) or CR_PREC_BF16 (one); CR_PREC_F32 takes the bf16x3 path.
+ *   - ids: pos / neg in [0, V) (not checked on the device).  shapes: 8 <= D <= 256, V >= 2, M >= 1, ld >= D, ldd >= D.
+ *   - workspace: at least cr_softmax_ce_workspace(M, V, D) bytes of device memory, O((M + min(16 V, 32768)) D). */
+typedef struct cr_softmax_ce_desc cr_softmax_ce_desc;
+struct cr_softmax_ce_desc {
+    const float* seq_emb; int ld;     /* [M] rows of D floats, pitch ld */
+    const float* table;               /* [V, D] */
+    const int32_t* pos;               /* device [M]: target ids, 0 = padding row */
+    const int32_t* neg;               /* device [M] or NULL: sampled negatives, for the AUC only */
+    int M, D, V;
+    int precision;                    /* CR_PREC_* */
+    float* state;                     /* CR_STATE_FLOATS: [0..2] +=, snapshot [8..11] */
+    float* d_seq_emb; int ldd;        /* optional [M] rows, pitch ldd */
+    float* table_grad;                /* optional [V, D], accumulated */
+    float* lse_out;                   /* optional [M] */
+    void* workspace;
+    size_t workspace_bytes;
+};
+size_t cr_softmax_ce_workspace(int M, int V, int D);        /* 0 for a shape outside the supported range */
+int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream);
 
 /* ---- occurrence index of a batch (round 5; csrc/cr_index.cpp, csrc/cr_tgrad.hip) ---------------------------------
  * The gradient of a looked-up table row is the sum of the gradient rows of every position that looked it up: the three

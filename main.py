@@ -55,6 +55,9 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=20, help='evaluate + checkpoint every N epochs (reference: 20)')
     parser.add_argument('--eval_full_ranking', action='store_true',
                         help='also log NDCG@10 / HR@10 over the full catalogue (every item outside the user\'s rated set) at each evaluation')
+    parser.add_argument('--loss', default='bce', choices=['bce', 'ce'],
+                        help='training objective: bce = the reference\'s pos / neg BCE with one sampled negative; ce = softmax '
+                             'cross-entropy over the whole item catalogue')
     return parser.parse_args(argv)
 
 
