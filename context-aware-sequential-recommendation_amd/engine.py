@@ -31,6 +31,10 @@ DEFAULT_ATTN_PRECISION = "bf16x3"
 # training objectives: "bce" the reference's pos / neg dot-product BCE with one sampled negative per position (cr_head_fwd_bwd);
 # "ce" softmax cross-entropy over the whole item catalogue (cr_softmax_ce)
 LOSSES = ("bce", "ce")
+# ... and "sampled_ce": softmax cross-entropy over the target and ce_negatives items drawn uniformly for the whole batch
+# (cr_sampled_ce)
+ALL_LOSSES = LOSSES + ("sampled_ce",)
+SOFTMAX_LOSSES = ("ce", "sampled_ce")
 
 MODELS = ["cast_1", "cast_2", "cast_3", "cast_4", "cast_5", "cast_6", "cast_7", "cast_8", "cast_9",
           "sasrec", "sasrec_static"]          # main.py:28
@@ -54,7 +58,7 @@ class Hyper:
 
     def __init__(self, args=None, **kw):
         d = dict(maxlen=50, hidden_units=50, num_blocks=2, num_heads=1, dropout_rate=0.5, l2_emb=0.0, lr=1e-3,
-                 max_bins=200, num_context_blocks=2, seed=42, loss="bce")
+                 max_bins=200, num_context_blocks=2, seed=42, loss="bce", ce_negatives=256)
         for k in d:
             if args is not None and hasattr(args, k):
                 d[k] = getattr(args, k)
@@ -183,12 +187,15 @@ class ParamLayout:
 class Engine:
     def __init__(self, model, usernum, itemnum, hp, batch_size, training=True, seed=None, n_slabs=None,
                  share=None, batch_global=None, row_offset=0, want_attn=False, device="cuda", fused=None,
-                 attn_precision=None, lazy_adam=None, loss=None):
+                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None):
         """loss: the training objective, "bce" (the default: hp.loss, else "bce") or "ce" -- full-catalogue softmax cross-entropy
         (cr_softmax_ce).  Under "ce" the prediction head is one cr_softmax_ce launch that stores d(seq_emb) and accumulates the item
         table's gradient into Gt; the occurrence index and the head fusions are off, so the embedding backward scatters with float
         atomics and bitwise_reproducible is False.  "ce" refuses row-sparse Adam, data parallelism and hidden sizes outside 8..256
-        (ValueError).  Eval engines ignore the option."""
+        (ValueError).  Eval engines ignore the option.
+        "sampled_ce" takes the route of "ce" with one cr_sampled_ce launch: the softmax over each row's target and ce_negatives
+        (default hp.ce_negatives, else 256) item ids drawn uniformly on the device for the whole batch from the engine's seed and step
+        word; eng.samples holds the last step's ids.  It refuses what "ce" refuses and ce_negatives outside 1..CR_SCE_MAX_SAMPLES."""
         if model not in MODELS:
             raise ValueError("model must be one of %s" % MODELS)
         if not torch.cuda.is_available():
@@ -210,16 +217,24 @@ class Engine:
         self.lazy_adam = bool(int(os.environ.get("CASTREC_LAZY_ADAM", "0"))) if lazy_adam is None else bool(lazy_adam)
         if loss is None:
             loss = getattr(hp, "loss", None) or "bce"
-        if loss not in LOSSES:
-            raise ValueError("loss must be one of %s, got %r" % (LOSSES, loss))
+        if loss not in ALL_LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (ALL_LOSSES, loss))
         self.loss = loss if training else "bce"
-        if self.loss == "ce":
+        if ce_negatives is None:
+            ce_negatives = getattr(hp, "ce_negatives", None) or 256
+        self.ce_negatives = int(ce_negatives)
+        if self.loss in SOFTMAX_LOSSES:
+            op = "cr_softmax_ce" if self.loss == "ce" else "cr_sampled_ce"
             if self.lazy_adam:
-                raise ValueError("loss='ce' does not take row-sparse Adam (lazy_adam): every item row has a gradient")
+                raise ValueError("loss='%s' does not take row-sparse Adam (lazy_adam): every item row has a gradient" % self.loss)
             if (batch_global is not None and batch_global != batch_size) or row_offset:
-                raise ValueError("loss='ce' does not take data parallelism (the item table's gradient is not in the exchanged bucket)")
+                raise ValueError("loss='%s' does not take data parallelism (the item table's gradient is not in the exchanged bucket)"
+                                 % self.loss)
             if not 8 <= hp.hidden_units <= 256:
-                raise ValueError("loss='ce' needs 8 <= hidden_units <= 256 (cr_softmax_ce), got %d" % hp.hidden_units)
+                raise ValueError("loss='%s' needs 8 <= hidden_units <= 256 (%s), got %d" % (self.loss, op, hp.hidden_units))
+        if self.loss == "sampled_ce" and not 1 <= self.ce_negatives <= L.CR_SCE_MAX_SAMPLES:
+            raise ValueError("loss='sampled_ce' needs 1 <= ce_negatives <= %d (cr_sampled_ce), got %d"
+                             % (L.CR_SCE_MAX_SAMPLES, self.ce_negatives))
         self.M = self.B * self.T
         self.usernum, self.itemnum = usernum, itemnum
         self.training = training
@@ -288,6 +303,10 @@ class Engine:
             if self.loss == "ce":
                 nb = O.softmax_ce_workspace_bytes(self.M, itemnum + 1, self.D)
                 self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+            elif self.loss == "sampled_ce":
+                nb = O.sampled_ce_workspace_bytes(self.M, self.ce_negatives, self.D)
+                self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+                self.samples = torch.zeros(self.ce_negatives, dtype=torch.int32, device=self.dev)    # the last step's sample ids
         self.drop = O.Drop(hp.dropout_rate if training else 0.0, self.seed, self.state, row_offset)
         self.batch_global = self.B if batch_global is None else batch_global
         self.want_attn = want_attn
@@ -1006,6 +1025,18 @@ class Engine:
                                 self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, prec, self.state.data_ptr(), ds.data_ptr(), ds.shape[1],
                                 self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
             self._call(self.fwd, "cr_softmax_ce", C.byref(d))
+            return
+        if self.loss == "sampled_ce":
+            # the route of "ce"; the N samples are drawn on the device from (seed, state[4]), so every step (captured graphs and the
+            # fed multi-step path included) draws its own
+            ds = self._grad_of(seq_emb)
+            self._grad_written.add(id(ds))
+            prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
+            d = L.SampledCeDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
+                                self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, self.ce_negatives, prec, None,
+                                self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
+                                ds.data_ptr(), ds.shape[1], self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
+            self._call(self.fwd, "cr_sampled_ce", C.byref(d))
             return
         rec = self._ln_recipe.get(seq_emb.data_ptr()) if self.fuse_head_ln else None
         if rec is not None:

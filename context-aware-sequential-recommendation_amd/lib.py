@@ -28,6 +28,8 @@ c_p = C.c_void_p
 
 CR_MAX_BATCH = 4
 CR_STATE_FLOATS = 16
+CR_SCE_MAX_SAMPLES = 16384       # castrec.h: sample ids per cr_sampled_ce call at most
+CR_SCE_SITE = 0x5CE00000         # castrec.h: the cr_site_key site of cr_sampled_ce's device draw
 PREC_F32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
 ELT_COPY, ELT_ADD, ELT_DROPOUT, ELT_RELU_BWD, ELT_ROWMASK, ELT_GRADPREP = 0, 1, 2, 3, 4, 5
 
@@ -155,6 +157,13 @@ class SoftmaxCeDesc(C.Structure):
                 ("workspace", c_p), ("workspace_bytes", C.c_size_t)]
 
 
+class SampledCeDesc(C.Structure):
+    _fields_ = [("seq_emb", c_p), ("ld", c_i), ("table", c_p), ("pos", c_p), ("neg", c_p), ("M", c_i), ("D", c_i), ("V", c_i),
+                ("N", c_i), ("precision", c_i), ("samples", c_p), ("seed", C.c_uint32), ("step", c_p), ("samples_out", c_p),
+                ("state", c_p), ("d_seq_emb", c_p), ("ldd", c_i), ("table_grad", c_p), ("lse_out", c_p), ("workspace", c_p),
+                ("workspace_bytes", C.c_size_t)]
+
+
 def _sig(name, restype, argtypes):
     f = getattr(_lib, name)
     f.restype = restype
@@ -228,6 +237,8 @@ _sig("cr_score_topk_workspace", C.c_size_t, [c_i, c_i, c_i, c_i])
 _sig("cr_score_topk", c_i, [C.POINTER(TopkDesc), c_p])
 _sig("cr_softmax_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_softmax_ce", c_i, [C.POINTER(SoftmaxCeDesc), c_p])
+_sig("cr_sampled_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
+_sig("cr_sampled_ce", c_i, [C.POINTER(SampledCeDesc), c_p])
 
 EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "cr_embed_fwd", "cr_embed_bwd", "cr_layernorm_fwd",
            "cr_layernorm_bwd", "cr_gemm_rows", "cr_gemm_wgrad", "cr_eltwise", "cr_attn_fwd", "cr_attn_bwd",
@@ -236,7 +247,8 @@ EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "
            "cr_head_fwd_bwd", "cr_head_fwd_bwd_ln", "cr_stack_fwd_head_supported", "cr_stack_fwd_head", "cr_test_logits", "cr_adam_step", "cr_reduce_slabs", "cr_l2_penalty", "cr_graph_begin", "cr_graph_end", "cr_graph_launch",
            "cr_graph_destroy", "cr_sampler_create", "cr_sampler_next", "cr_sampler_destroy",
            "cr_tgrad_geometry", "cr_batch_index_layout", "cr_index_builder_create", "cr_index_build", "cr_index_builder_destroy", "cr_table_grad",
-           "cr_score_topk_workspace", "cr_score_topk", "cr_softmax_ce_workspace", "cr_softmax_ce"]
+           "cr_score_topk_workspace", "cr_score_topk", "cr_softmax_ce_workspace", "cr_softmax_ce",
+           "cr_sampled_ce_workspace", "cr_sampled_ce"]
 
 lib = _lib
 

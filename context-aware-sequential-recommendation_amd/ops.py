@@ -169,6 +169,29 @@ def softmax_ce(seq_emb, ld, table, pos, state, workspace, M, precision=L.PREC_BF
     L.call("cr_softmax_ce", C.byref(d), _stream())
 
 
+def sampled_ce_workspace_bytes(M, N, D):
+    n = L.lib.cr_sampled_ce_workspace(M, N, D)
+    if n == 0:
+        raise ValueError("cr_sampled_ce: unsupported shape M=%d N=%d D=%d (M >= 1, 1 <= N <= %d, 8 <= D <= 256)"
+                         % (M, N, D, L.CR_SCE_MAX_SAMPLES))
+    return n
+
+
+def sampled_ce(seq_emb, ld, table, pos, state, workspace, M, N, precision=L.PREC_BF16X3, neg=None, samples=None, seed=0, step=None,
+               samples_out=None, d_seq_emb=None, ldd=0, table_grad=None, lse_out=None):
+    """cr_sampled_ce: the softmax over each row's target and N shared sample ids.  Rows seq_emb + m * ld (m < M) of a float32 CUDA
+    tensor's storage against table [V, D]; pos / neg int32 [M]; samples an int32 [N] tensor of ids in [1, V), or None: drawn on the
+    device from seed and step (a CUDA tensor whose first 4 bytes are the uint32 step word, e.g. state[4:5]); samples_out int32 [N]
+    written where given; state, d_seq_emb, table_grad, lse_out as softmax_ce; workspace a uint8 CUDA tensor of at least
+    sampled_ce_workspace_bytes(M, N, D) bytes."""
+    d = L.SampledCeDesc(_p(_f32(seq_emb, "seq_emb")), ld, _p(_f32(table, "table")), _p(_i32(pos, "pos")), _p(_i32(neg, "neg")),
+                        M, table.shape[1], table.shape[0], N, precision, _p(_i32(samples, "samples")), int(seed) & 0xFFFFFFFF,
+                        _p(step), _p(_i32(samples_out, "samples_out")), _p(_f32(state, "state")), _p(_f32(d_seq_emb, "d_seq_emb")),
+                        ldd, _p(_f32(table_grad, "table_grad")), _p(_f32(lse_out, "lse_out")), _p(workspace),
+                        workspace.numel() * workspace.element_size())
+    L.call("cr_sampled_ce", C.byref(d), _stream())
+
+
 def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, state, beta1=0.9, beta2=0.98, eps=1e-8,
               stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None):
     d = L.AdamDesc(_p(p), _p(m), _p(v), _p(table_grad), _p(dense_slabs), n_table, n_dense, n_slabs, lr, beta1, beta2,

@@ -56,7 +56,7 @@ typedef struct {
 
 /* ---- per-step device state ---------------------------------------------------- */
 /* state (device, CR_STATE_FLOATS floats):
- *   [0] loss_sum  [1] auc_sum  [2] n_target  (accumulated by cr_head_fwd_bwd, or cr_softmax_ce)
+ *   [0] loss_sum  [1] auc_sum  [2] n_target  (accumulated by cr_head_fwd_bwd, cr_softmax_ce or cr_sampled_ce)
  *   [3] reserved  [4] step counter (uint32 bits)  [5] loss  [6] auc (written by cr_adam_step)
  *   [8] [9] [10] copies of [0] [1] [2] and [11] a copy of [4], taken by the LAST workgroup of cr_head_fwd_bwd(_ln) (or cr_softmax_ce)
  *   to finish (ticket in [12]): a consistent snapshot that later kernels may read while [0..4] move on.
@@ -503,6 +503,53 @@ struct cr_softmax_ce_desc {
 };
 size_t cr_softmax_ce_workspace(int M, int V, int D);        /* 0 for a shape outside the supported range */
 int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream);
+
+/* ---- sampled softmax cross-entropy with shared uniform negatives (csrc/cr_sce.hip) --------------------------------
+ * The softmax objective of cr_softmax_ce over the target plus N items drawn for the whole call, at a cost that does not depend on V.
+ * Rows m = 0 .. M-1, h_m = seq_emb row m, E = table [V, D] (row 0 padding), istarget_m = (pos[m] != 0), sample ids s_0 .. s_{N-1}
+ * in [1, V) shared by every row.  Candidates of row m: the target pos_m and every sample j with s_j != pos_m (a sample equal to the
+ * row's target is an "accidental hit", dropped from that row only); samples are drawn with replacement and a duplicate counts as
+ * its own candidate.  The proposal is uniform, so a log-Q correction would shift every logit by one constant: none is applied.
+ *   z_mv = h_m . E_v;  l_m = log(exp z_{m,pos} + sum_{j: s_j != pos_m} exp z_{m,s_j}) - z_{m,pos};  p = softmax over the candidates.
+ *   state: [0] += sum_m istarget_m l_m, [1] += the AUC term of the per-position neg ids exactly as cr_softmax_ce's (neg 0 reads as a
+ *   zero score; neg == NULL adds 0), [2] += sum_m istarget_m; then the snapshot [8..11] (ticket [12] left at 0): cr_adam_step runs
+ *   unchanged with step_snapshot = state + 11.
+ *   d_seq_emb (optional, WRITTEN): dh_m = istarget_m ((p_{m,pos} - 1) E_pos + sum_j p_mj E_{s_j}); zero rows where pos is 0.
+ *   table_grad (optional, ACCUMULATED): dE_{s_j} += sum_m istarget_m p_mj h_m and dE_{pos_m} += istarget_m (p_{m,pos} - 1) h_m.
+ *   Row 0 is never written; rows that are neither a sample nor a target are not touched.
+ *   lse_out (optional, [M]): the log of each row's candidate sum (rows with pos 0 included: their "target" is row 0).
+ *   samples_out (optional, device [N]): the ids used.
+ * Samples: `samples` (device [N], ids in [1, V), not checked on the device), or, when it is NULL, drawn on the device from `seed` and
+ * the device step word `step` (state + 4, as cr_rng reads it), so captured graphs draw new samples every step without host work:
+ *   key = cr_site_key(seed, *step, CR_SCE_SITE);  x_j = cr_fmix32(key + j * CR_PHI);  s_j = 1 + (uint32)(((uint64)x_j * (V - 1)) >> 32).
+ * Reproducibility: the target term of table_grad is added with float atomics (as cr_head_fwd_bwd's table_grad); every other output
+ * (state, lse_out, d_seq_emb, samples_out, table_grad rows that are no row's target) has the same bits on two calls.
+ *   - precision: CR_PREC_BF16X3 or CR_PREC_BF16; CR_PREC_F32 takes the bf16x3 path (as cr_softmax_ce).
+ *   - shapes: 8 <= D <= 256, V >= 2, M >= 1, 1 <= N <= CR_SCE_MAX_SAMPLES, ld >= D, ldd >= D.
+ *   - workspace: at least cr_sampled_ce_workspace(M, N, D) bytes of device memory, O(M + N D); it never decreases as M or N grows. */
+#define CR_SCE_MAX_SAMPLES 16384
+#define CR_SCE_SITE 0x5CE00000u      /* the draw's cr_site_key site (outside the 24-bit dropout site ids) */
+typedef struct cr_sampled_ce_desc cr_sampled_ce_desc;
+struct cr_sampled_ce_desc {
+    const float* seq_emb; int ld;     /* [M] rows of D floats, pitch ld */
+    const float* table;               /* [V, D] */
+    const int32_t* pos;               /* device [M]: target ids, 0 = padding row */
+    const int32_t* neg;               /* device [M] or NULL: sampled negatives, for the AUC only */
+    int M, D, V, N;
+    int precision;                    /* CR_PREC_* */
+    const int32_t* samples;           /* device [N] ids in [1, V), or NULL: drawn from (seed, *step) */
+    uint32_t seed;
+    const uint32_t* step;             /* device step word (state + 4); required when samples is NULL */
+    int32_t* samples_out;             /* optional device [N] */
+    float* state;                     /* CR_STATE_FLOATS: [0..2] +=, snapshot [8..11] */
+    float* d_seq_emb; int ldd;        /* optional [M] rows, pitch ldd */
+    float* table_grad;                /* optional [V, D], accumulated */
+    float* lse_out;                   /* optional [M] */
+    void* workspace;
+    size_t workspace_bytes;
+};
+size_t cr_sampled_ce_workspace(int M, int N, int D);       /* 0 for a shape outside the supported range */
+int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream);
 
 /* ---- occurrence index of a batch (round 5; csrc/cr_index.cpp, csrc/cr_tgrad.hip) ---------------------------------
  * The gradient of a looked-up table row is the sum of the gradient rows of every position that looked it up: the three

@@ -55,9 +55,12 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=20, help='evaluate + checkpoint every N epochs (reference: 20)')
     parser.add_argument('--eval_full_ranking', action='store_true',
                         help='also log NDCG@10 / HR@10 over the full catalogue (every item outside the user\'s rated set) at each evaluation')
-    parser.add_argument('--loss', default='bce', choices=['bce', 'ce'],
+    parser.add_argument('--loss', default='bce', choices=['bce', 'ce', 'sampled_ce'],
                         help='training objective: bce = the reference\'s pos / neg BCE with one sampled negative; ce = softmax '
-                             'cross-entropy over the whole item catalogue')
+                             'cross-entropy over the whole item catalogue; sampled_ce = softmax cross-entropy over the target and '
+                             '--ce_negatives items drawn uniformly for the whole batch')
+    parser.add_argument('--ce_negatives', type=int, default=256,
+                        help='sampled_ce: shared uniform negatives per training step (1 .. 16384)')
     return parser.parse_args(argv)
 
 
