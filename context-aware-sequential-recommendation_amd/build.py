@@ -17,7 +17,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "libcastrec.so")
 LIB_TL = os.path.join(PKG, "libcastrec_tl.so")
 SOURCES = ["cr_base.hip", "cr_embed.hip", "cr_layernorm.hip", "cr_eltwise.hip", "cr_gemm.hip",
-           "cr_attn_fwd.hip", "cr_attn_bwd.hip", "cr_attn_bwd1.hip", "cr_attn_wide.hip", "cr_attn_bf.hip", "cr_gemm_bf.hip", "cr_block.hip", "cr_stack.hip", "cr_stack_bwd.hip", "cr_stack_bwd1.hip", "cr_wide.hip", "cr_head.hip", "cr_adam.hip", "cr_tgrad.hip", "cr_topk.hip", "cr_ce.hip", "cr_sce.hip", "cr_dist.hip", "cr_sampler.cpp", "cr_index.cpp"]
+           "cr_attn_fwd.hip", "cr_attn_bwd.hip", "cr_attn_bwd1.hip", "cr_attn_wide.hip", "cr_attn_bf.hip", "cr_gemm_bf.hip", "cr_block.hip", "cr_stack.hip", "cr_stack_bwd.hip", "cr_stack_bwd1.hip", "cr_wide.hip", "cr_head.hip", "cr_adam.hip", "cr_tgrad.hip", "cr_topk.hip", "cr_ce.hip", "cr_dist.hip", "cr_sampler.cpp", "cr_index.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", os.path.join(ROOT, "include"), "-I", CSRC,
          "-Wall", "-Wno-unused-function",
          # no SLP vectorisation: it packs adjacent scalar fp32 adds / multiplies into v_pk_*_f32.  (a) Beside MFMAs those cost more
@@ -40,7 +40,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-I", os.path.jo
 ISA_CHECKED = ["cr_stack.hip", "cr_stack_bwd.hip", "cr_stack_bwd1.hip", "cr_wide.hip", "cr_attn_bf.hip",
                # (round 5: every source with matrix instructions -- the two-shape rule; each holds ONE shape today)
                "cr_block.hip", "cr_attn_fwd.hip", "cr_attn_bwd.hip", "cr_attn_bwd1.hip", "cr_gemm.hip", "cr_gemm_bf.hip",
-               "cr_topk.hip", "cr_ce.hip", "cr_sce.hip"]
+               "cr_topk.hip", "cr_ce.hip"]
 SLP_PROTECTED = ("cr_stack", "cr_wide")          # file-name prefixes that may never be compiled with SLP vectorisation
 _PK_F32 = ("v_pk_fma_f32", "v_pk_mul_f32", "v_pk_add_f32")
 _LABEL = re.compile(r"^([A-Za-z_$][\w$.]*):")
@@ -188,8 +188,7 @@ def file_flags(source_name, timeline=False):
 HEADERS = [os.path.join(CSRC, h) for h in ("cr_common.hpp", "cr_attn_common.hpp", "cr_bf16.hpp", "cr_rlayout.hpp", "cr_rbwd.hpp")] \
     + [os.path.join(ROOT, "include", "castrec.h")]
 # ... and single sources on these besides
-EXTRA_DEPS = {"cr_adam.hip": ["cr_tgrad.hpp"], "cr_tgrad.hip": ["cr_tgrad.hpp"], "cr_ce.hip": ["cr_ce.hpp"],
-              "cr_sce.hip": ["cr_ce.hpp"]}
+EXTRA_DEPS = {"cr_adam.hip": ["cr_tgrad.hpp"], "cr_tgrad.hip": ["cr_tgrad.hpp"]}
 
 
 def _hipcc():

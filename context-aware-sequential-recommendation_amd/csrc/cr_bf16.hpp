@@ -2,6 +2,8 @@
 // the [rows][64] bf16 LDS image and its two kinds of operand reads, the hi + lo split of fp32 operands, the three-product
 // MFMA, and the branch-free 8-float items global -> register traffic is made of.  See cr_attn_bf.hip for the design notes.
 #pragma once
+#include <type_traits>
+
 #include "cr_common.hpp"
 
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
@@ -174,4 +176,21 @@ __device__ __forceinline__ f32x4 tk_tile(const bf8 (&ah)[NK], const bf8 (&al)[NK
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks) c = mma<SPLIT>(ah[ks], al[ks], bh[ks], bl[ks], c);
     return c;
+}
+
+// The k-steps of tk_tile for a head dim D (8 .. 256): D / 32 rounded up to an instantiated 1, 2, 4 or 8.  Every sweep takes this one
+// choice, so a score has the same bits in cr_score_topk, cr_softmax_ce and cr_sampled_ce.
+static inline int tk_nk(int D) {
+    const int nk = (D + 31) / 32;
+    return nk <= 1 ? 1 : nk <= 2 ? 2 : nk <= 4 ? 4 : 8;
+}
+
+// f(nk, split) with both as std::integral_constant: a sweep's launcher instantiated for tk_nk's choice and the precision
+template <class F>
+void tk_dispatch(int NK, bool split, F&& f) {
+    auto go = [&](auto nk) { split ? f(nk, std::true_type()) : f(nk, std::false_type()); };
+    if (NK == 1) go(std::integral_constant<int, 1>());
+    else if (NK == 2) go(std::integral_constant<int, 2>());
+    else if (NK == 4) go(std::integral_constant<int, 4>());
+    else go(std::integral_constant<int, 8>());
 }

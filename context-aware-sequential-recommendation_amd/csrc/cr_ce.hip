@@ -1,32 +1,58 @@
-// Full-catalogue softmax cross-entropy (castrec.h cr_softmax_ce): per batch row m the loss logsumexp_v s_mv - s_{m,pos_m} over the
-// items v = 1 .. V-1 with s_mv = h_m . E_v, and its un-normalised gradients wrt h and E, without ever writing the [M, V] scores.
-// Up to five launches, each deterministic (no float atomics; every partition is fixed by the shape):
+// Softmax cross-entropy without ever writing the [M, candidates] scores, and its un-normalised gradients wrt h and E (castrec.h):
+//  * cr_softmax_ce, the full catalogue: per batch row m the loss logsumexp_v s_mv - s_{m,pos_m} over the items v = 1 .. V-1 with
+//    s_mv = h_m . E_v;
+//  * cr_sampled_ce, shared uniform negatives: log(exp z_{m,pos} + sum_{j: s_j != pos_m} exp z_{m,s_j}) - z_{m,pos} over the target and
+//    N sample ids shared by the call, against a compact table of the samples' rows, so the cost is O(M N D), independent of V.
+// Both run the same four sweep passes, templated on the candidate kind -- the argument struct: CeArgs, the catalogue, whose candidates
+// are the items 1 .. V-1 of E with the target among them; SceArgs, the sampled, whose candidates are the N gathered rows Es with the
+// target beside them (a sample equal to a row's target is masked; the target's own terms come separately):
 //
 //  * lse    (a workgroup per 64 rows, 256 threads).  Each wave keeps its 16 rows as B fragments in registers; the workgroup streams the
-//           items through an LDS image of 32 rows (bf16 hi / lo, cr_bf16.hpp img_off<2>), filled from registers loaded a block ahead.
-//           A wave scores its rows against the block (tk_tile: the product sequence of cr_topk.hip, so a score has the same bits here
-//           as there) and folds the scores into a running base-2 max / sum per lane (exp2 with log2 e folded into the score); the four
-//           lane groups of a row merge in a fixed butterfly.  Out: lse2 = log2 sum exp2 per row, the row tile's loss / AUC / target sums.
-//  * stats  (one wave).  The row tiles' sums in a fixed order: state[0..2] +=, then the snapshot [8..11] (see cr_softmax_ce below).
-//  * dh     (same grid as lse).  The same sweep recomputes each score, p = exp2(s log2 e - lse2) minus the one-hot of pos, and multiplies
-//           the [16 rows x 32 items] G block by the item block: A = G straight from the two score tiles' accumulators (k slot 8 lg + j
-//           <-> item (j < 4 ? 0 : 16) + 4 lg + (j & 3)), B = the same LDS image read transposed (tr_frag with that k order).
-//  * de     (a workgroup per 64 items x a part of the rows).  Each wave keeps its 16 items as B fragments; the batch rows of the part
-//           stream through the LDS image.  The score tile is computed with the roles swapped (ce_tile_t: rows as A, items as B, the
-//           three products in tk_tile's order), so a lane holds rows against its item -- the A operand of dE = G^T H; B = the row
-//           image read transposed.  One part: += into table_grad; several: each writes its slice of the workspace, and
-//  * de_sum adds the parts into table_grad in part order.
+//           candidates through an LDS image of 32 rows (bf16 hi / lo, cr_bf16.hpp img_off<2>), filled from registers loaded a block
+//           ahead.  A wave scores its rows against the block (tk_tile: the product sequence of cr_topk.hip, so a score has the same bits
+//           here as there) and folds the scores into a running base-2 max / sum per lane (exp2 with log2 e folded into the score); the
+//           four lane groups of a row merge in a fixed butterfly.  Out: lse2 = log2 sum exp2 per row, the row tile's loss / AUC / target
+//           sums.  Catalogue: the target and neg scores are picked up as the sweep passes them.  Sampled: they come from diagonal tiles
+//           of the gathered rows E[pos] / E[neg] against the wave's own rows (tk_tile again; cr_score_topk's ranks use the same trick),
+//           the target enters the running max / sum of lane group 0 before the first block, and gpos = p_pos - 1 is written per row.
+//  * stats  (one wave).  The row tiles' sums in a fixed order: state[0..2] +=, then the snapshot [8..11] (see castrec.h, state block).
+//  * dh     (same grid as lse).  The same sweep recomputes each score, p = exp2(s log2 e - lse2) (catalogue: minus the one-hot of pos;
+//           sampled: 0 at a hit), and multiplies the [16 rows x 32 candidates] G block by the candidate block: A = G straight from the
+//           two score tiles' accumulators (k slot 8 lg + j <-> candidate (j < 4 ? 0 : 16) + 4 lg + (j & 3)), B = the same LDS image
+//           read transposed (tr_frag with that k order).  Sampled: the epilogue adds gpos_m E[pos_m] in fp32.
+//  * de     (a workgroup per 64 candidates x a part of the rows).  Each wave keeps its 16 candidates as B fragments; the batch rows of
+//           the part stream through the LDS image.  The score tile is computed with the roles swapped (ce_tile_t: rows as A, candidates
+//           as B, the three products in tk_tile's order), so a lane holds rows against its candidate -- the A operand of dE = G^T H;
+//           B = the row image read transposed.  Each part writes its slice of the workspace; a catalogue of one part += into table_grad.
+// Around the sweeps, per op:
+//  * de_sum  (catalogue, parts > 1) adds the parts into table_grad in part order.
+//  * ids     (sampled; grid-stride over N x D).  Copy or draw the N ids (castrec.h states the draw), write them and samples_out, and
+//            gather the N rows of E into the compact fp32 table Es [N, D] of the workspace.
+//  * dedup   (sampled, a thread per sample; only with table_grad).  For sample j: whether it is its id's first occurrence, and the next
+//            j' > j with the same id (a linked list in j order).  Each thread compares its id against all N through LDS chunks: O(N^2)
+//            compares, a few microseconds at N = 4096.
+//  * scatter (sampled, a workgroup per sample).  The first occurrence of each id walks its list in j order, adds the parts in part
+//            order and += the sum into table_grad[id]: one writer per distinct id.
+//  * tgt     (sampled; grid-stride over M x D).  dE_{pos_m} += gpos_m h_m with float atomics.
+// Every partition is fixed by the shape; the sampled tgt is the only pass with float atomics (the one non-deterministic output).
 // One MFMA shape in this file (build.py ISA_CHECKED): v_mfma_f32_16x16x32_bf16.
 #include <algorithm>
 
-#include "cr_ce.hpp"
+#include "cr_bf16.hpp"
 
 namespace {
 
-constexpr int CE_PART_ELEMS = 32768;        // parts x V of the de pass's partial sums at most (the workspace reserves min(16 V, this) rows)
-constexpr int CE_MAX_PARTS = 16;
+constexpr float CE_LOG2E = 1.4426950408889634f;
+constexpr float CE_LN2 = 0.6931471805599453f;
+constexpr int CE_BLK = 32;                  // rows of the streamed LDS block (candidates in lse / dh, batch rows in de)
+constexpr int CE_PART_ELEMS = 32768;        // catalogue: parts x V of the de pass's partial sums at most (the workspace reserves
+constexpr int CE_MAX_PARTS = 16;            //   min(16 V, this) rows)
+constexpr int SCE_PART_ROWS = 65536;        // sampled: parts x N of the de pass's partial sums at most
+constexpr int SCE_MAX_PARTS = 64;
+constexpr int SCE_CHUNK = 2048;             // ids per LDS chunk of the dedup pass
 
 struct CeArgs {
+    static constexpr bool SAMPLED = false;
     const float* h; int64_t ldh;
     const float* E;
     const int32_t* pos; const int32_t* neg;
@@ -42,15 +68,206 @@ struct CeArgs {
     int n_rt;
 };
 
-// p - [v = pos] of one score, for a target row (l2: the row's lse2).  The same expression in dh and de: the same bits.
-__device__ __forceinline__ float ce_g(float s, float l2, bool hit) {
-    return ce_exp2(__builtin_fmaf(s, CE_LOG2E, -l2)) - (hit ? 1.0f : 0.0f);
+struct SceArgs {
+    static constexpr bool SAMPLED = true;
+    const float* h; int64_t ldh;
+    const float* E;
+    const int32_t* pos; const int32_t* neg;
+    int M, D, V, N;
+    const int32_t* samples;                 // caller's ids, or NULL: drawn from (seed, *step)
+    uint32_t seed; const uint32_t* step;
+    int32_t* sid;                           // [N] the ids used
+    int32_t* samples_out;
+    int32_t* nxt;                           // [N] next j' > j with the same id (N: none)
+    int32_t* head;                          // [N] 1 where j is its id's first occurrence
+    float* Es;                              // [N, D] gathered rows
+    float* lse2;                            // [M] log2 of the candidate sum (base-2 exponent of the scores)
+    float* gpos;                            // [M] p_pos - 1 for target rows, 0 elsewhere
+    float* stats;                           // [n_rt, 4] loss / auc / target sums per row tile
+    float* dh; int64_t ldd;
+    float* tg;
+    float* part;                            // [parts, N, D]
+    int rpp, parts;                         // batch rows per part of the de pass
+    float* lse_out;
+    float* state;
+    int n_rt;
+};
+
+// ---- the streamed block ---------------------------------------------------------------------------------------------------
+// CE_BLK rows of an fp32 matrix loaded a block ahead into registers, stored as a bf16 hi / lo LDS image, read back as row operands or
+// transposed.  CE_BLK rows x NCB blocks of 64 columns, bf16 hi and lo:
+template <int NCB>
+struct CeImg {
+    __bf16 hi[NCB][CE_BLK * 64];
+    __bf16 lo[NCB][CE_BLK * 64];
+};
+
+// Rows r0 .. r0 + 31 of src into registers: thread t owns the 8-column chunks t + 256 i (row-major over the image's 8 NCB chunks per
+// row).  Rows >= end are read as row 0's last columns and masked to zero (cr_bf16.hpp items); `last`: the matrix's last row.
+template <int NCB>
+__device__ __forceinline__ void blk_issue(float (&v)[NCB][8], const float* src, int64_t ld, int r0, int end, int last, int D) {
+#pragma unroll
+    for (int i = 0; i < NCB; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const int row = idx / (8 * NCB), c = 8 * (idx % (8 * NCB));
+        const int r = r0 + row;
+        const bool rok = r < end;
+        item_issue(v[i], src + (rok ? (int64_t)r * ld : 0), c, D, !rok || item_fix(rok, r == last, c, D));
+    }
+}
+template <int NCB, bool SPLIT>
+__device__ __forceinline__ void blk_store(float (&v)[NCB][8], CeImg<NCB>& img, const float* src, int64_t ld, int r0, int end, int last,
+                                          int D) {
+#pragma unroll
+    for (int i = 0; i < NCB; ++i) {
+        const int idx = threadIdx.x + 256 * i;
+        const int row = idx / (8 * NCB), ch = idx % (8 * NCB), c = 8 * ch;
+        const int r = r0 + row;
+        const bool rok = r < end;
+        const bool fix = item_fix(rok, r == last, c, D);
+        item_mask(v[i], c, D, rok, fix);
+        if (fix) item_refill(v[i], src + (int64_t)r * ld, c, D);
+        bf8 h, l;
+        split8<SPLIT>(v[i], h, l);
+        const int off = img_off<2>(row, ch & 7);
+        *reinterpret_cast<bf8*>(&img.hi[ch >> 3][off]) = h;
+        if (SPLIT) *reinterpret_cast<bf8*>(&img.lo[ch >> 3][off]) = l;
+    }
 }
 
+// rows row0 + li of the image as an operand with k = columns (k-step ks: columns 32 ks + 8 lg .. + 7, as tk_row_finish lays them out)
+template <int NK, int NCB, bool SPLIT>
+__device__ __forceinline__ void img_rows(const CeImg<NCB>& img, int row0, bf8 (&h)[NK], bf8 (&l)[NK]) {
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        h[ks] = row_frag<2>(img.hi[ks >> 1], row0, ks & 1);
+        l[ks] = SPLIT ? row_frag<2>(img.lo[ks >> 1], row0, ks & 1) : h[ks];
+    }
+}
+
+// tk_tile with the operands' roles swapped: register r of lane (li, lg) = row 4 lg + r (A) against item li (B).  Per element the
+// same three products in the same order (item lo x row hi, item hi x row lo, hi x hi): the MFMA's element function is a sum of exact
+// bf16 products in k order, symmetric in its two operands, so an (item, row) pair gets tk_tile's bits.
 template <int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_ce_lse(CeArgs a) {
+__device__ __forceinline__ f32x4 ce_tile_t(const bf8 (&rh)[NK], const bf8 (&rl)[NK], const bf8 (&ih)[NK], const bf8 (&il)[NK]) {
+    f32x4 c = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        if (SPLIT) {
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rh[ks], il[ks], c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rl[ks], ih[ks], c, 0, 0, 0);
+        }
+        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(rh[ks], ih[ks], c, 0, 0, 0);
+    }
+    return c;
+}
+
+// two score tiles' registers (k slots 8 lg + j: tile j >> 2, register j & 3) as one operand of a k = 32 product
+template <bool SPLIT>
+__device__ __forceinline__ void g_frag(const float (&g)[2][4], bf8& h, bf8& l) {
+    const float x[8] = {g[0][0], g[0][1], g[0][2], g[0][3], g[1][0], g[1][1], g[1][2], g[1][3]};
+    split8<SPLIT>(x, h, l);
+    if (!SPLIT) l = h;
+}
+
+// acc[db] += G x (the image read transposed: k = image row in g_frag's order, columns 16 db .. + 15), for the column blocks below D
+template <int NK, int NCB, bool SPLIT>
+__device__ __forceinline__ void g_times_img(f32x4 (&acc)[2 * NK], const bf8& gh, const bf8& gl, const CeImg<NCB>& img, int D) {
+#pragma unroll
+    for (int db = 0; db < 2 * NK; ++db) {
+        if (16 * db < D) {                                          // uniform: every lane reads (ds_read_b64_tr_b16 wants EXEC full)
+            const bf8 bh = tr_frag<2>(img.hi[db >> 2], 0, 16, db & 3);
+            const bf8 bl = SPLIT ? tr_frag<2>(img.lo[db >> 2], 0, 16, db & 3) : bh;
+            acc[db] = mma<SPLIT>(gh, gl, bh, bl, acc[db]);
+        }
+    }
+}
+
+__device__ __forceinline__ float ce_exp2(float x) { return __builtin_amdgcn_exp2f(x); }
+
+// p of one (row, candidate) score for a target row (l2: the row's lse2).  The same expression in dh and de: the same bits.
+__device__ __forceinline__ float ce_p(float s, float l2) { return ce_exp2(__builtin_fmaf(s, CE_LOG2E, -l2)); }
+// catalogue: p - [v = pos] (a sampled hit is masked instead)
+__device__ __forceinline__ float ce_g(float s, float l2, bool hit) { return ce_p(s, l2) - (hit ? 1.0f : 0.0f); }
+
+
+// ---- the sampled-only pieces around the sweeps ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_sce_ids(SceArgs a) {
+    const uint32_t key = a.samples ? 0u : cr_site_key(a.seed, *a.step, CR_SCE_SITE);
+    const int64_t n = (int64_t)a.N * a.D;
+    for (int64_t e = blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int j = (int)(e / a.D), c = (int)(e % a.D);
+        int id;
+        if (a.samples) {
+            id = a.samples[j];
+        } else {
+            const uint32_t x = cr_fmix32(key + (uint32_t)j * CR_PHI);
+            id = 1 + (int)(uint32_t)(((uint64_t)x * (uint32_t)(a.V - 1)) >> 32);
+        }
+        a.Es[e] = a.E[(int64_t)id * a.D + c];
+        if (c == 0) {
+            a.sid[j] = id;
+            if (a.samples_out) a.samples_out[j] = id;
+        }
+    }
+}
+
+// (after k_sce_ids) head / nxt of every sample: compares against the N ids in chunks of SCE_CHUNK staged in LDS
+__global__ __launch_bounds__(256) void k_sce_dedup(SceArgs a) {
+    __shared__ int ids[SCE_CHUNK];
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    const int mine = j < a.N ? a.sid[j] : -1;
+    bool first = true;
+    int nx = a.N;
+    for (int c0 = 0; c0 < a.N; c0 += SCE_CHUNK) {
+        const int n = min(SCE_CHUNK, a.N - c0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += 256) ids[i] = a.sid[c0 + i];
+        __syncthreads();
+        for (int i = 0; i < n; ++i) {
+            const int k = c0 + i;
+            if (ids[i] == mine) {
+                first = first && k >= j;
+                nx = (k > j && k < nx) ? k : nx;
+            }
+        }
+    }
+    if (j < a.N) {
+        a.head[j] = first ? 1 : 0;
+        a.nxt[j] = nx;
+    }
+}
+
+// a wave's diagonal: the score of row (query) li against operand row li of (th, tl), in every lane of the row (tk_tile's bits)
+template <int NK, bool SPLIT>
+__device__ __forceinline__ float sce_diag(const bf8 (&th)[NK], const bf8 (&tl)[NK], const bf8 (&bh)[NK], const bf8 (&bl)[NK]) {
+    const int lane = threadIdx.x & 63, li = lane & 15, lg = lane >> 4;
+    const f32x4 c = tk_tile<NK, SPLIT>(th, tl, bh, bl);       // register r of lane (li, lg): operand row 4 lg + r against query li
+    const int r = li & 3;
+    float x = r == 0 ? c[0] : r == 1 ? c[1] : r == 2 ? c[2] : c[3];
+    x = lg == (li >> 2) ? x : 0.0f;
+    x += __shfl_xor(x, 16, 64);
+    x += __shfl_xor(x, 32, 64);
+    return x;
+}
+
+// score of each lane's row against E[id] (id per lane, rok: the lane's row exists)
+template <int NK, bool SPLIT>
+__device__ __forceinline__ float sce_gathered_score(const SceArgs& a, int id, bool rok, const bf8 (&bh)[NK], const bf8 (&bl)[NK]) {
+    bf8 th[NK], tl[NK];
+    float v[NK][8];
+    tk_row_issue<NK>(v, a.E, a.D, id, rok, id == a.V - 1, a.D);
+    tk_row_finish<NK, SPLIT>(v, a.E, a.D, id, rok, id == a.V - 1, a.D, th, tl);
+    return sce_diag<NK, SPLIT>(th, tl, bh, bl);
+}
+
+// ---- the sweep passes (A: CeArgs or SceArgs) -----------------------------------------------------------------------------
+template <class A, int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_ce_lse(A a) {
+    constexpr bool S = A::SAMPLED;
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
+    __shared__ int s_id[CE_BLK];                                    // (sampled)
     __shared__ float red[3][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int q = blockIdx.x * 64 + wave * 16 + li;
@@ -62,15 +279,38 @@ __global__ __launch_bounds__(256) void k_ce_lse(CeArgs a) {
         tk_row_finish<NK, SPLIT>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D, bh, bl);
     }
     const int pq = qok ? a.pos[q] : 0, nq = (qok && a.neg) ? a.neg[q] : 0;
-    float mx = -INFINITY, s_in = 0.0f, s_out = 0.0f, sp = 0.0f, sn = 0.0f;
-    const int rounds = (a.V - 1 + CE_BLK - 1) / CE_BLK;
+    float sp = 0.0f, sn = 0.0f;
+    if constexpr (S) {
+        sp = sce_gathered_score<NK, SPLIT>(a, pq, qok, bh, bl);
+        if (a.neg) {                                                // (uniform: the tile runs with every lane on)
+            const float x = sce_gathered_score<NK, SPLIT>(a, nq, qok, bh, bl);
+            sn = nq != 0 ? x : 0.0f;                                // neg 0: a zero score, as the catalogue's row 0
+        }
+    }
+    // sampled: the target is lane group 0's first candidate
+    const float tp = sp * CE_LOG2E;
+    float mx = (S && lg == 0) ? tp : -INFINITY, s_in = (S && lg == 0) ? 1.0f : 0.0f, s_out = 0.0f;
+    const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
+    int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
+    if constexpr (S) { src = a.Es; c0 = 0; end = a.N; }
+    else { src = a.E; c0 = 1; end = a.V; }
+    const int rounds = (end - c0 + CE_BLK - 1) / CE_BLK;
     float v[NCB][8];
-    blk_issue<NCB>(v, a.E, a.D, 1, a.V, a.V - 1, a.D);
+    int nid = 0;                                                    // (sampled: the ids of the next block, staged through LDS)
+    blk_issue<NCB>(v, src, a.D, c0, end, end - 1, a.D);
+    if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
     for (int rd = 0; rd < rounds; ++rd) {
-        const int i0 = 1 + rd * CE_BLK;
-        blk_store<NCB, SPLIT>(v, img, a.E, a.D, i0, a.V, a.V - 1, a.D);
+        const int j0 = c0 + rd * CE_BLK;
+        blk_store<NCB, SPLIT>(v, img, src, a.D, j0, end, end - 1, a.D);
+        if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
         __syncthreads();
-        if (rd + 1 < rounds) blk_issue<NCB>(v, a.E, a.D, i0 + CE_BLK, a.V, a.V - 1, a.D);
+        if (rd + 1 < rounds) {
+            blk_issue<NCB>(v, src, a.D, j0 + CE_BLK, end, end - 1, a.D);
+            if constexpr (S) {
+                const int j = j0 + CE_BLK + threadIdx.x;
+                nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
+            }
+        }
         float t[2][4];
         float bm = -INFINITY;
 #pragma unroll
@@ -80,10 +320,16 @@ __global__ __launch_bounds__(256) void k_ce_lse(CeArgs a) {
             const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int id = i0 + 16 * tt + 4 * lg + r;
-                const bool ok = id < a.V;
-                sp = (ok && id == pq) ? c[r] : sp;
-                sn = (ok && id == nq) ? c[r] : sn;
+                const int jl = 16 * tt + 4 * lg + r;
+                bool ok;
+                if constexpr (S) {
+                    ok = j0 + jl < end && s_id[jl] != pq;           // a sample equal to the target is masked
+                } else {
+                    const int id = j0 + 16 * tt + 4 * lg + r;
+                    ok = id < end;
+                    sp = (ok && id == pq) ? c[r] : sp;
+                    sn = (ok && id == nq) ? c[r] : sn;
+                }
                 t[tt][r] = ok ? c[r] * CE_LOG2E : -INFINITY;
                 bm = fmaxf(bm, t[tt][r]);
             }
@@ -112,17 +358,21 @@ __global__ __launch_bounds__(256) void k_ce_lse(CeArgs a) {
         const float m2 = fmaxf(mx, mo);
         s = (mx > -INFINITY ? s * ce_exp2(mx - m2) : 0.0f) + (mo > -INFINITY ? so * ce_exp2(mo - m2) : 0.0f);
         mx = m2;
-        sp += __shfl_xor(sp, o, 64);                                // one lane of the four holds the score, the others 0
-        sn += __shfl_xor(sn, o, 64);
+        if constexpr (!S) {
+            sp += __shfl_xor(sp, o, 64);                            // one lane of the four holds the score, the others 0
+            sn += __shfl_xor(sn, o, 64);
+        }
     }
     const float l2 = mx + __log2f(s);
     const bool ist = qok && pq != 0;
     float lr = 0.0f, ar = 0.0f, nr = 0.0f;
     if (qok && lg == 0) {
         a.lse2[q] = l2;
+        // sampled: relative to the target's own base-2 score, so a row whose every sample is a hit gets l = 0 and p_pos - 1 = 0 exactly
+        if constexpr (S) a.gpos[q] = ist ? ce_exp2(tp - l2) - 1.0f : 0.0f;
         if (a.lse_out) a.lse_out[q] = l2 * CE_LN2;
         if (ist) {
-            lr = l2 * CE_LN2 - sp;
+            lr = S ? (l2 - tp) * CE_LN2 : l2 * CE_LN2 - sp;
             const float dlt = sp - sn;                              // neg 0 (or none): row 0 reads as zeros
             ar = a.neg ? ((dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? 0.0f : 0.5f)) : 0.0f;
             nr = 1.0f;
@@ -138,7 +388,8 @@ __global__ __launch_bounds__(256) void k_ce_lse(CeArgs a) {
 
 // state[0..2] += the row tiles' sums (fixed order), then the snapshot [8..11] the head kernels take (castrec.h, state block).  One
 // workgroup adds and snapshots, so it is the last piece of work by construction; the ticket [12] is left re-armed (0).
-__global__ __launch_bounds__(64) void k_ce_stats(CeArgs a) {
+template <class A>
+__global__ __launch_bounds__(64) void k_ce_stats(A a) {
     const int lane = threadIdx.x;
     float s[3] = {0.0f, 0.0f, 0.0f};
     for (int i = lane; i < a.n_rt; i += 64)
@@ -158,10 +409,12 @@ __global__ __launch_bounds__(64) void k_ce_stats(CeArgs a) {
     }
 }
 
-template <int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_ce_dh(CeArgs a) {
+template <class A, int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_ce_dh(A a) {
+    constexpr bool S = A::SAMPLED;
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
+    __shared__ int s_id[CE_BLK];                                    // (sampled)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int q = blockIdx.x * 64 + wave * 16 + li;
     const bool qok = q < a.M;
@@ -177,14 +430,27 @@ __global__ __launch_bounds__(256) void k_ce_dh(CeArgs a) {
     f32x4 acc[2 * NK];
 #pragma unroll
     for (int i = 0; i < 2 * NK; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const int rounds = (a.V - 1 + CE_BLK - 1) / CE_BLK;
+    const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
+    int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
+    if constexpr (S) { src = a.Es; c0 = 0; end = a.N; }
+    else { src = a.E; c0 = 1; end = a.V; }
+    const int rounds = (end - c0 + CE_BLK - 1) / CE_BLK;
     float v[NCB][8];
-    blk_issue<NCB>(v, a.E, a.D, 1, a.V, a.V - 1, a.D);
+    int nid = 0;                                                    // (sampled: the ids of the next block, staged through LDS)
+    blk_issue<NCB>(v, src, a.D, c0, end, end - 1, a.D);
+    if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
     for (int rd = 0; rd < rounds; ++rd) {
-        const int i0 = 1 + rd * CE_BLK;
-        blk_store<NCB, SPLIT>(v, img, a.E, a.D, i0, a.V, a.V - 1, a.D);
+        const int j0 = c0 + rd * CE_BLK;
+        blk_store<NCB, SPLIT>(v, img, src, a.D, j0, end, end - 1, a.D);
+        if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
         __syncthreads();
-        if (rd + 1 < rounds) blk_issue<NCB>(v, a.E, a.D, i0 + CE_BLK, a.V, a.V - 1, a.D);
+        if (rd + 1 < rounds) {
+            blk_issue<NCB>(v, src, a.D, j0 + CE_BLK, end, end - 1, a.D);
+            if constexpr (S) {
+                const int j = j0 + CE_BLK + threadIdx.x;
+                nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
+            }
+        }
         float g[2][4];
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
@@ -193,8 +459,13 @@ __global__ __launch_bounds__(256) void k_ce_dh(CeArgs a) {
             const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int id = i0 + 16 * tt + 4 * lg + r;
-                g[tt][r] = (ist && id < a.V) ? ce_g(c[r], l2, id == pq) : 0.0f;
+                if constexpr (S) {
+                    const int jl = 16 * tt + 4 * lg + r;
+                    g[tt][r] = (ist && j0 + jl < end && s_id[jl] != pq) ? ce_p(c[r], l2) : 0.0f;     // a hit is masked
+                } else {
+                    const int id = j0 + 16 * tt + 4 * lg + r;
+                    g[tt][r] = (ist && id < end) ? ce_g(c[r], l2, id == pq) : 0.0f;
+                }
             }
         }
         bf8 gh, gl;
@@ -203,31 +474,55 @@ __global__ __launch_bounds__(256) void k_ce_dh(CeArgs a) {
         __syncthreads();
     }
     // acc[db] register r: row 16 wave + 4 lg + r of the tile, column 16 db + li
-#pragma unroll
-    for (int db = 0; db < 2 * NK; ++db) {
-        const int col = 16 * db + li;
+    if constexpr (S) {
+        // plus the target term (p_pos - 1) E_pos
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
-            if (row < a.M && col < a.D) a.dh[(int64_t)row * a.ldd + col] = acc[db][r];
+            if (row >= a.M) continue;
+            const int pr = a.pos[row];
+            const float gp = a.gpos[row];
+            const float* er = a.E + (int64_t)pr * a.D;
+#pragma unroll
+            for (int db = 0; db < 2 * NK; ++db) {
+                const int col = 16 * db + li;
+                if (col < a.D) a.dh[(int64_t)row * a.ldd + col] = pr != 0 ? __builtin_fmaf(gp, er[col], acc[db][r]) : 0.0f;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int db = 0; db < 2 * NK; ++db) {
+            const int col = 16 * db + li;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
+                if (row < a.M && col < a.D) a.dh[(int64_t)row * a.ldd + col] = acc[db][r];
+            }
         }
     }
 }
 
-template <int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_ce_de(CeArgs a) {
+template <class A, int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_ce_de(A a) {
+    constexpr bool S = A::SAMPLED;
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
     __shared__ float s_l2[CE_BLK];
     __shared__ int s_pos[CE_BLK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const int id = 1 + blockIdx.x * 64 + wave * 16 + li;
-    const bool iok = id < a.V;
+    const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
+    int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
+    if constexpr (S) { src = a.Es; c0 = 0; end = a.N; }
+    else { src = a.E; c0 = 1; end = a.V; }
+    const int j = c0 + blockIdx.x * 64 + wave * 16 + li;
+    const bool jok = j < end;
+    int id = j;                                                     // the candidate's item id
+    if constexpr (S) id = jok ? a.sid[j] : -1;
     bf8 bh[NK], bl[NK];
     {
         float v[NK][8];
-        tk_row_issue<NK>(v, a.E, a.D, id, iok, id == a.V - 1, a.D);
-        tk_row_finish<NK, SPLIT>(v, a.E, a.D, id, iok, id == a.V - 1, a.D, bh, bl);
+        tk_row_issue<NK>(v, src, a.D, j, jok, j == end - 1, a.D);
+        tk_row_finish<NK, SPLIT>(v, src, a.D, j, jok, j == end - 1, a.D, bh, bl);
     }
     const int rb = blockIdx.y * a.rpp, re = min(a.M, rb + a.rpp);
     f32x4 acc[2 * NK];
@@ -261,7 +556,8 @@ __global__ __launch_bounds__(256) void k_ce_de(CeArgs a) {
             for (int r = 0; r < 4; ++r) {
                 const int lr = 16 * tt + 4 * lg + r;
                 const int pr = s_pos[lr];
-                g[tt][r] = (iok && pr != 0) ? ce_g(c[r], s_l2[lr], pr == id) : 0.0f;
+                if constexpr (S) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_p(c[r], s_l2[lr]) : 0.0f;
+                else g[tt][r] = (jok && pr != 0) ? ce_g(c[r], s_l2[lr], pr == id) : 0.0f;
             }
         }
         bf8 gh, gl;
@@ -269,22 +565,23 @@ __global__ __launch_bounds__(256) void k_ce_de(CeArgs a) {
         g_times_img<NK, NCB, SPLIT>(acc, gh, gl, img, a.D);
         __syncthreads();
     }
-    // acc[db] register r: item 16 wave + 4 lg + r of the workgroup's 64, column 16 db + li
+    // acc[db] register r: candidate 16 wave + 4 lg + r of the workgroup's 64, column 16 db + li
 #pragma unroll
     for (int db = 0; db < 2 * NK; ++db) {
         const int col = 16 * db + li;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int it = 1 + blockIdx.x * 64 + wave * 16 + 4 * lg + r;
-            if (it < a.V && col < a.D) {
-                if (a.parts == 1) a.tg[(int64_t)it * a.D + col] += acc[db][r];
-                else a.part[((int64_t)blockIdx.y * a.V + it) * a.D + col] = acc[db][r];
+            const int jr = c0 + blockIdx.x * 64 + wave * 16 + 4 * lg + r;
+            if (jr < end && col < a.D) {
+                if (!S && a.parts == 1) a.tg[(int64_t)jr * a.D + col] += acc[db][r];
+                else a.part[((int64_t)blockIdx.y * end + jr) * a.D + col] = acc[db][r];
             }
         }
     }
 }
 
-// table_grad[v, :] += sum of the parts' rows v in part order (rows 1 .. V-1)
+// ---- the op-specific reductions of the de pass -------------------------------------------------------------------------
+// catalogue: table_grad[v, :] += sum of the parts' rows v in part order (rows 1 .. V-1)
 __global__ __launch_bounds__(256) void k_ce_de_sum(CeArgs a) {
     const int64_t n = (int64_t)(a.V - 1) * a.D, stride = (int64_t)a.V * a.D;
     for (int64_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -295,41 +592,89 @@ __global__ __launch_bounds__(256) void k_ce_de_sum(CeArgs a) {
     }
 }
 
+// sampled: table_grad[s_j] += the sum over the id's samples (j order) of the parts (part order); one workgroup per first occurrence
+__global__ __launch_bounds__(256) void k_sce_scatter(SceArgs a) {
+    const int j = blockIdx.x;
+    if (!a.head[j]) return;
+    const int64_t stride = (int64_t)a.N * a.D;
+    const int id = a.sid[j];
+    for (int c = threadIdx.x; c < a.D; c += 256) {
+        float acc = 0.0f;
+        for (int k = j; k < a.N; k = a.nxt[k]) {
+            const int64_t e = (int64_t)k * a.D + c;
+            float s = a.part[e];
+            for (int p = 1; p < a.parts; ++p) s += a.part[p * stride + e];
+            acc += s;
+        }
+        a.tg[(int64_t)id * a.D + c] += acc;
+    }
+}
+
+// sampled: dE_{pos_m} += (p_pos - 1) h_m for the target rows (float atomics: rows repeat)
+__global__ __launch_bounds__(256) void k_sce_tgt(SceArgs a) {
+    const int64_t n = (int64_t)a.M * a.D;
+    for (int64_t e = blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
+        const int m = (int)(e / a.D), c = (int)(e % a.D);
+        const int p = a.pos[m];
+        if (p != 0) atomicAdd(a.tg + (int64_t)p * a.D + c, a.gpos[m] * a.h[(int64_t)m * a.ldh + c]);
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------------------
 struct CeGeom {
-    int NK, n_rt, n_it, parts, rpp;
+    int NK, n_rt, n_ct, parts, rpp;         // n_ct: the de pass's workgroups of 64 candidates
 };
 
-bool ce_geometry(int M, int V, int D, CeGeom& g) {
-    if (M < 1 || V < 2 || D < 8 || D > 256) return false;
-    const int nk = (D + 31) / 32;
-    g.NK = nk <= 1 ? 1 : nk <= 2 ? 2 : nk <= 4 ? 4 : 8;
+// Candidates c0 .. end - 1 (cands()).  The de pass: about 512 workgroups of (64 candidates x a part of the rows) where the candidates
+// are few; its partial sums are at most max_parts slices of `end` rows, parts x end <= part_rows.
+bool ce_geometry(int M, int c0, int end, int D, int max_parts, int part_rows, CeGeom& g) {
+    if (M < 1 || end <= c0 || D < 8 || D > 256) return false;
+    g.NK = tk_nk(D);
     g.n_rt = (M + 63) / 64;
-    g.n_it = (V - 1 + 63) / 64;
-    // the de pass: about 512 workgroups of (64 items x a part of the rows) where the table is short; parts x V <= CE_PART_ELEMS
-    int parts = std::min(CE_MAX_PARTS, CE_PART_ELEMS / V);
+    g.n_ct = (end - c0 + 63) / 64;
+    int parts = std::min(max_parts, part_rows / end);
     parts = std::max(1, std::min(parts, (M + CE_BLK - 1) / CE_BLK));
     g.rpp = ((M + parts - 1) / parts + CE_BLK - 1) / CE_BLK * CE_BLK;
     g.parts = (M + g.rpp - 1) / g.rpp;
     return true;
 }
 
-size_t ce_align(size_t x) { return (x + 255) / 256 * 256; }
-
-// workspace: [lse2 M | row-tile sums n_rt x 4 | de partial rows min(16 V, CE_PART_ELEMS) x D] floats (the last section is reserved for
-// every shape so that the size never shrinks as V grows; it is used where parts > 1)
-size_t ce_workspace(int M, int V, int D, const CeGeom& g) {
+// catalogue workspace: [lse2 M | row-tile sums n_rt x 4 | de partial rows min(16 V, CE_PART_ELEMS) x D] floats (the last section is
+// reserved for every shape so that the size never shrinks as V grows; it is used where parts > 1).  0: an unsupported shape.
+size_t ce_workspace(int M, int V, int D, CeGeom& g) {
+    if (!ce_geometry(M, 1, V, D, CE_MAX_PARTS, CE_PART_ELEMS, g)) return 0;
     const size_t part_rows = std::min<size_t>((size_t)CE_MAX_PARTS * V, CE_PART_ELEMS);
-    return ce_align(4 * (size_t)M) + ce_align(16 * (size_t)g.n_rt) + ce_align(4 * part_rows * D);
+    return cr_align256(4 * (size_t)M) + cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * part_rows * D);
 }
 
-template <int NK, bool SPLIT>
-void ce_launch(const CeArgs& a, const CeGeom& g, hipStream_t st) {
-    hipLaunchKernelGGL((k_ce_lse<NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ce_stats, dim3(1), dim3(64), 0, st, a);
-    if (a.dh) hipLaunchKernelGGL((k_ce_dh<NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
+size_t sce_part_rows(int N) { return std::min<size_t>((size_t)SCE_MAX_PARTS * N, std::max<size_t>(N, SCE_PART_ROWS)); }
+
+// sampled workspace: [sid | nxt | head: N ints each | Es N x D | lse2 M | gpos M | row-tile sums n_rt x 4 | de parts min(64 N, 65536)
+// x D] (the parts section is sized by N alone, so the total never decreases as M or N grows).  0: an unsupported shape.
+size_t sce_workspace(int M, int N, int D, CeGeom& g) {
+    if (N > CR_SCE_MAX_SAMPLES || !ce_geometry(M, 0, N, D, SCE_MAX_PARTS, SCE_PART_ROWS, g)) return 0;
+    return 3 * cr_align256(4 * (size_t)N) + cr_align256(4 * (size_t)N * D) + 2 * cr_align256(4 * (size_t)M) +
+           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D);
+}
+
+int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 255) / 256)); }
+
+template <class A, int NK, bool SPLIT>
+void ce_launch(const A& a, const CeGeom& g, hipStream_t st) {
+    constexpr bool S = A::SAMPLED;
+    if constexpr (S) {
+        hipLaunchKernelGGL(k_sce_ids, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
+        if (a.tg) hipLaunchKernelGGL(k_sce_dedup, dim3((a.N + 255) / 256), dim3(256), 0, st, a);
+    }
+    hipLaunchKernelGGL((k_ce_lse<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ce_stats<A>, dim3(1), dim3(64), 0, st, a);
+    if (a.dh) hipLaunchKernelGGL((k_ce_dh<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
     if (a.tg) {
-        hipLaunchKernelGGL((k_ce_de<NK, SPLIT>), dim3(g.n_it, g.parts), dim3(256), 0, st, a);
-        if (g.parts > 1) {
+        hipLaunchKernelGGL((k_ce_de<A, NK, SPLIT>), dim3(g.n_ct, g.parts), dim3(256), 0, st, a);
+        if constexpr (S) {
+            hipLaunchKernelGGL(k_sce_scatter, dim3(a.N), dim3(std::min(256, (a.D + 63) / 64 * 64)), 0, st, a);
+            hipLaunchKernelGGL(k_sce_tgt, dim3(grid_for((int64_t)a.M * a.D)), dim3(256), 0, st, a);
+        } else if (g.parts > 1) {
             const int64_t n = (int64_t)(a.V - 1) * a.D;
             const int grid = (int)std::min<int64_t>(2048, (n + 255) / 256);
             hipLaunchKernelGGL(k_ce_de_sum, dim3(grid), dim3(256), 0, st, a);
@@ -337,11 +682,16 @@ void ce_launch(const CeArgs& a, const CeGeom& g, hipStream_t st) {
     }
 }
 
+// the passes for the descriptor's precision (CR_PREC_F32: the bf16x3 products, fp32-grade) and tk_nk's k-steps
+template <class A>
+void ce_run(const A& a, const CeGeom& g, int precision, hipStream_t st) {
+    tk_dispatch(g.NK, precision != CR_PREC_BF16, [&](auto nk, auto split) { ce_launch<A, nk, split>(a, g, st); });
+}
+
 }  // namespace
 
 extern "C" size_t cr_softmax_ce_workspace(int M, int V, int D) {
     CeGeom g;
-    if (!ce_geometry(M, V, D, g)) return 0;
     return ce_workspace(M, V, D, g);
 }
 
@@ -356,8 +706,8 @@ extern "C" int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream) {
     CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
                "cr_softmax_ce: unknown precision %d", d->precision);
     CeGeom g;
-    CR_REQUIRE(ce_geometry(d->M, d->V, d->D, g), "cr_softmax_ce: unsupported shape");
     const size_t need = ce_workspace(d->M, d->V, d->D, g);
+    CR_REQUIRE(need, "cr_softmax_ce: unsupported shape");
     CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_softmax_ce: workspace of %zu bytes, cr_softmax_ce_workspace says %zu",
                d->workspace ? d->workspace_bytes : (size_t)0, need);
 
@@ -365,19 +715,55 @@ extern "C" int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream) {
     CeArgs a;
     a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
     a.M = d->M; a.D = d->D; a.V = d->V;
-    a.lse2 = reinterpret_cast<float*>(w); w += ce_align(4 * (size_t)d->M);
-    a.stats = reinterpret_cast<float*>(w); w += ce_align(16 * (size_t)g.n_rt);
+    a.lse2 = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
+    a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
     a.part = reinterpret_cast<float*>(w);
     a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
     a.rpp = g.rpp; a.parts = g.parts;
     a.lse_out = d->lse_out; a.state = d->state; a.n_rt = g.n_rt;
-    hipStream_t st = cr_stream(stream);
-    const bool split = d->precision != CR_PREC_BF16;       // CR_PREC_F32: the bf16x3 products (fp32-grade)
-#define CE_NK(NK) (split ? ce_launch<NK, true>(a, g, st) : ce_launch<NK, false>(a, g, st))
-    if (g.NK == 1) CE_NK(1);
-    else if (g.NK == 2) CE_NK(2);
-    else if (g.NK == 4) CE_NK(4);
-    else CE_NK(8);
-#undef CE_NK
+    ce_run(a, g, d->precision, cr_stream(stream));
     return cr_check_launch("cr_softmax_ce");
+}
+
+extern "C" size_t cr_sampled_ce_workspace(int M, int N, int D) {
+    CeGeom g;
+    return sce_workspace(M, N, D, g);
+}
+
+extern "C" int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream) {
+    CR_REQUIRE(d, "cr_sampled_ce: NULL descriptor");
+    CR_REQUIRE(d->seq_emb && d->table && d->pos && d->state, "cr_sampled_ce: NULL seq_emb, table, pos or state");
+    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_sampled_ce: D=%d outside 8 .. 256", d->D);
+    CR_REQUIRE(d->V >= 2, "cr_sampled_ce: V=%d < 2 (row 0 is padding: no item to sample)", d->V);
+    CR_REQUIRE(d->M >= 1, "cr_sampled_ce: M=%d <= 0", d->M);
+    CR_REQUIRE(d->N >= 1 && d->N <= CR_SCE_MAX_SAMPLES, "cr_sampled_ce: N=%d outside 1 .. %d", d->N, CR_SCE_MAX_SAMPLES);
+    CR_REQUIRE(d->ld >= d->D, "cr_sampled_ce: ld=%d < D=%d", d->ld, d->D);
+    CR_REQUIRE(!d->d_seq_emb || d->ldd >= d->D, "cr_sampled_ce: ldd=%d < D=%d", d->ldd, d->D);
+    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
+               "cr_sampled_ce: unknown precision %d", d->precision);
+    CR_REQUIRE(d->samples || d->step, "cr_sampled_ce: NULL step with NULL samples (the device draw reads the step word)");
+    CeGeom g;
+    const size_t need = sce_workspace(d->M, d->N, d->D, g);
+    CR_REQUIRE(need, "cr_sampled_ce: unsupported shape");
+    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_sampled_ce: workspace of %zu bytes, cr_sampled_ce_workspace says %zu",
+               d->workspace ? d->workspace_bytes : (size_t)0, need);
+
+    unsigned char* w = static_cast<unsigned char*>(d->workspace);
+    SceArgs a;
+    a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
+    a.M = d->M; a.D = d->D; a.V = d->V; a.N = d->N;
+    a.samples = d->samples; a.seed = d->seed; a.step = d->step; a.samples_out = d->samples_out;
+    a.sid = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
+    a.nxt = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
+    a.head = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
+    a.Es = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->N * d->D);
+    a.lse2 = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
+    a.gpos = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
+    a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
+    a.part = reinterpret_cast<float*>(w);
+    a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
+    a.rpp = g.rpp; a.parts = g.parts;
+    a.lse_out = d->lse_out; a.state = d->state; a.n_rt = g.n_rt;
+    ce_run(a, g, d->precision, cr_stream(stream));
+    return cr_check_launch("cr_sampled_ce");
 }

@@ -174,6 +174,8 @@ __device__ __forceinline__ void head_snapshot(float* state, unsigned total_workg
 }
 
 static inline int cr_ceil_div(int a, int b) { return (a + b - 1) / b; }
+// a workspace section's size rounded up to 256 bytes (the sections of cr_score_topk, cr_softmax_ce and cr_sampled_ce)
+static inline size_t cr_align256(size_t x) { return (x + 255) / 256 * 256; }
 
 // Kernels with more than 64 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised, and that
 // attribute belongs to the CURRENT device: each launcher keeps one mask per kernel, one bit per device ordinal, so a

@@ -373,8 +373,7 @@ struct TkGeom {
 
 bool tk_geometry(int B, int V, int D, int K, TkGeom& g) {
     if (B < 1 || V < 1 || D < 8 || D > 256 || K < 1 || K > CR_TOPK_MAX) return false;
-    const int nk = (D + 31) / 32;
-    g.NK = nk <= 1 ? 1 : nk <= 2 ? 2 : nk <= 4 ? 4 : 8;
+    g.NK = tk_nk(D);
     g.QB = 4;
     while (g.QB > 1 && (tk_lds_bytes(16 * g.QB, g.NK, K) > 160 * 1024 || 16 * (g.QB / 2) >= B)) g.QB /= 2;
     g.lds = tk_lds_bytes(16 * g.QB, g.NK, K);
@@ -389,12 +388,10 @@ bool tk_geometry(int B, int V, int D, int K, TkGeom& g) {
     return true;
 }
 
-size_t tk_align(size_t x) { return (x + 255) / 256 * 256; }
-
 // workspace: [offsets (B + 1) int64 | target scores B | chunk lists n_chunks B K (float, int32) | chunk counts n_chunks B]
 size_t tk_workspace(int B, const TkGeom& g, int K) {
     const size_t nb = (size_t)g.n_chunks * B;
-    return tk_align(8 * ((size_t)B + 1)) + tk_align(4 * (size_t)B) + 2 * tk_align(nb * K * 4) + tk_align(nb * 4);
+    return cr_align256(8 * ((size_t)B + 1)) + cr_align256(4 * (size_t)B) + 2 * cr_align256(nb * K * 4) + cr_align256(nb * 4);
 }
 
 template <int NK, bool SPLIT>
@@ -451,20 +448,15 @@ extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
         if (e != hipSuccess) return cr_set_error(CR_ERR_HIP, "cr_score_topk: offsets copy: %s", hipGetErrorString(e));
         a.off = off;
     }
-    w += tk_align(8 * ((size_t)d->B + 1));
-    a.st_ws = reinterpret_cast<float*>(w); w += tk_align(4 * (size_t)d->B);
-    a.part_s = reinterpret_cast<float*>(w); w += tk_align(nb * d->K * 4);
-    a.part_id = reinterpret_cast<int32_t*>(w); w += tk_align(nb * d->K * 4);
+    w += cr_align256(8 * ((size_t)d->B + 1));
+    a.st_ws = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->B);
+    a.part_s = reinterpret_cast<float*>(w); w += cr_align256(nb * d->K * 4);
+    a.part_id = reinterpret_cast<int32_t*>(w); w += cr_align256(nb * d->K * 4);
     a.part_cnt = reinterpret_cast<int32_t*>(w);
     a.excl = d->excl_ids; a.tgt = d->targets;
     a.top_ids = d->top_ids; a.top_scores = d->top_scores; a.rank = d->rank;
     a.chunk = g.chunk; a.n_chunks = g.n_chunks;
     const bool split = d->precision != CR_PREC_BF16;       // CR_PREC_F32: the bf16x3 products (fp32-grade)
-#define TK_NK(NK) (split ? tk_launch<NK, true>(a, g, st) : tk_launch<NK, false>(a, g, st))
-    if (g.NK == 1) TK_NK(1);
-    else if (g.NK == 2) TK_NK(2);
-    else if (g.NK == 4) TK_NK(4);
-    else TK_NK(8);
-#undef TK_NK
+    tk_dispatch(g.NK, split, [&](auto nk, auto sp) { tk_launch<nk, sp>(a, g, st); });
     return cr_check_launch("cr_score_topk");
 }

@@ -300,12 +300,11 @@ class Engine:
             self.Gflat = torch.zeros(lay.n_total + 4, **f32)
             self.Gt = self.Gflat[:lay.n_table]
             self.Gs = torch.zeros(n_slabs, max(lay.n_dense, 1), **f32)
-            if self.loss == "ce":
-                nb = O.softmax_ce_workspace_bytes(self.M, itemnum + 1, self.D)
+            if self.loss in SOFTMAX_LOSSES:
+                nb = (O.softmax_ce_workspace_bytes(self.M, itemnum + 1, self.D) if self.loss == "ce"
+                      else O.sampled_ce_workspace_bytes(self.M, self.ce_negatives, self.D))
                 self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-            elif self.loss == "sampled_ce":
-                nb = O.sampled_ce_workspace_bytes(self.M, self.ce_negatives, self.D)
-                self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
+            if self.loss == "sampled_ce":
                 self.samples = torch.zeros(self.ce_negatives, dtype=torch.int32, device=self.dev)    # the last step's sample ids
         self.drop = O.Drop(hp.dropout_rate if training else 0.0, self.seed, self.state, row_offset)
         self.batch_global = self.B if batch_global is None else batch_global
@@ -1015,28 +1014,25 @@ class Engine:
         self.seq_emb = seq_emb
         if not self.training:
             return
-        if self.loss == "ce":
-            # full-catalogue softmax cross-entropy: d(seq_emb) is stored (the final LayerNorm's / the MLP's backward reads it), the
-            # item table's gradient goes into Gt -- the head route of CASTREC_NO_HEAD_LN=1 with CASTREC_NO_INDEX=1
-            ds = self._grad_of(seq_emb)
-            self._grad_written.add(id(ds))
-            prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
-            d = L.SoftmaxCeDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
-                                self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, prec, self.state.data_ptr(), ds.data_ptr(), ds.shape[1],
-                                self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
-            self._call(self.fwd, "cr_softmax_ce", C.byref(d))
-            return
-        if self.loss == "sampled_ce":
-            # the route of "ce"; the N samples are drawn on the device from (seed, state[4]), so every step (captured graphs and the
+        if self.loss in SOFTMAX_LOSSES:
+            # softmax cross-entropy: d(seq_emb) is stored (the final LayerNorm's / the MLP's backward reads it), the item table's
+            # gradient goes into Gt -- the head route of CASTREC_NO_HEAD_LN=1 with CASTREC_NO_INDEX=1.  "ce" takes the whole
+            # catalogue; "sampled_ce" draws its N samples on the device from (seed, state[4]), so every step (captured graphs and the
             # fed multi-step path included) draws its own
             ds = self._grad_of(seq_emb)
             self._grad_written.add(id(ds))
             prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
-            d = L.SampledCeDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
-                                self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, self.ce_negatives, prec, None,
-                                self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
-                                ds.data_ptr(), ds.shape[1], self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
-            self._call(self.fwd, "cr_sampled_ce", C.byref(d))
+            row, pos, neg, V = seq_emb.data_ptr(), self.ids["pos"].data_ptr(), self.ids["neg"].data_ptr(), self.itemnum + 1
+            tail = (ds.data_ptr(), ds.shape[1], self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
+            if self.loss == "ce":
+                op = "cr_softmax_ce"
+                d = L.SoftmaxCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, prec, self.state.data_ptr(), *tail)
+            else:
+                op = "cr_sampled_ce"
+                d = L.SampledCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, self.ce_negatives, prec, None,
+                                    self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
+                                    *tail)
+            self._call(self.fwd, op, C.byref(d))
             return
         rec = self._ln_recipe.get(seq_emb.data_ptr()) if self.fuse_head_ln else None
         if rec is not None:

@@ -504,7 +504,7 @@ struct cr_softmax_ce_desc {
 size_t cr_softmax_ce_workspace(int M, int V, int D);        /* 0 for a shape outside the supported range */
 int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream);
 
-/* ---- sampled softmax cross-entropy with shared uniform negatives (csrc/cr_sce.hip) --------------------------------
+/* ---- sampled softmax cross-entropy with shared uniform negatives (csrc/cr_ce.hip) ---------------------------------
  * The softmax objective of cr_softmax_ce over the target plus N items drawn for the whole call, at a cost that does not depend on V.
  * Rows m = 0 .. M-1, h_m = seq_emb row m, E = table [V, D] (row 0 padding), istarget_m = (pos[m] != 0), sample ids s_0 .. s_{N-1}
  * in [1, V) shared by every row.  Candidates of row m: the target pos_m and every sample j with s_j != pos_m (a sample equal to the

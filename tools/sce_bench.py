@@ -1,4 +1,4 @@
-"""Times cr_sampled_ce (sampled softmax cross-entropy with shared uniform negatives, csrc/cr_sce.hip) with HIP events at the shapes of
+"""Times cr_sampled_ce (sampled softmax cross-entropy with shared uniform negatives, csrc/cr_ce.hip) with HIP events at the shapes of
 DESIGN.md section 12, against the MFMA roof, beside cr_softmax_ce at the same shape (where it is affordable) and a torch fp32
 composition of the same loss (gather -> matmul -> mask -> logsumexp -> the two gradient matmuls), and the CAST1 training step at the
 headline shape with loss "bce", "ce" and "sampled_ce" (N = 256).
