@@ -3,7 +3,10 @@
 //    s_mv = h_m . E_v;
 //  * cr_sampled_ce, shared uniform negatives: log(exp z_{m,pos} + sum_{j: s_j != pos_m} exp z_{m,s_j}) - z_{m,pos} over the target and
 //    N sample ids shared by the call, against a compact table of the samples' rows, so the cost is O(M N D), independent of V.
-// Both run the same four sweep passes, templated on the candidate kind -- the argument struct: CeArgs, the catalogue, whose candidates
+//  * cr_gbce, gSASRec's generalised binary cross-entropy over the same shared negatives: beta softplus(-z_{m,pos}) + sum_{j: s_j !=
+//    pos_m} softplus(z_{m,s_j}).  A pointwise objective has no normaliser, so one row sweep gives the loss and dh (gbce_row below) and
+//    the item sweep is de without a per-row statistic; ids, dedup, stats, scatter and tgt are the sampled op's.
+// The two softmax ops run the same four sweep passes, templated on the candidate kind -- the argument struct: CeArgs, the catalogue, whose candidates
 // are the items 1 .. V-1 of E with the target among them; SceArgs, the sampled, whose candidates are the N gathered rows Es with the
 // target beside them (a sample equal to a row's target is masked; the target's own terms come separately):
 //
@@ -34,6 +37,9 @@
 //  * scatter (sampled, a workgroup per sample).  The first occurrence of each id walks its list in j order, adds the parts in part
 //            order and += the sum into table_grad[id]: one writer per distinct id.
 //  * tgt     (sampled; grid-stride over M x D).  dE_{pos_m} += gpos_m h_m with float atomics.
+//  * gbce_row (gBCE; the grid of lse).  The sweep of dh with g = sigma(score) (0 at a hit) from one exp2 per score, the softplus of the
+//            same exponential summed per lane in sweep order, and lse's prologue / epilogue: the target's score from the diagonal
+//            tile, gpos = beta (sigma_pos - 1), the row's loss, the row tile's sums, dh += gpos E[pos] in fp32.
 // Every partition is fixed by the shape; the sampled tgt is the only pass with float atomics (the one non-deterministic output).
 // One MFMA shape in this file (build.py ISA_CHECKED): v_mfma_f32_16x16x32_bf16.
 #include <algorithm>
@@ -52,7 +58,7 @@ constexpr int SCE_MAX_PARTS = 64;
 constexpr int SCE_CHUNK = 2048;             // ids per LDS chunk of the dedup pass
 
 struct CeArgs {
-    static constexpr bool SAMPLED = false;
+    static constexpr bool SAMPLED = false, GBCE = false;
     const float* h; int64_t ldh;
     const float* E;
     const int32_t* pos; const int32_t* neg;
@@ -69,7 +75,7 @@ struct CeArgs {
 };
 
 struct SceArgs {
-    static constexpr bool SAMPLED = true;
+    static constexpr bool SAMPLED = true, GBCE = false;
     const float* h; int64_t ldh;
     const float* E;
     const int32_t* pos; const int32_t* neg;
@@ -91,6 +97,12 @@ struct SceArgs {
     float* lse_out;
     float* state;
     int n_rt;
+};
+
+// gBCE: the sampled op's candidates and buffers (lse2 unused; lse_out takes the per-row loss), g = sigma instead of the softmax's p
+struct GbceArgs : SceArgs {
+    static constexpr bool GBCE = true;
+    float beta;                             // weight of the positive term, (0, 1]
 };
 
 // ---- the streamed block ---------------------------------------------------------------------------------------------------
@@ -190,10 +202,22 @@ __device__ __forceinline__ float ce_p(float s, float l2) { return ce_exp2(__buil
 // catalogue: p - [v = pos] (a sampled hit is masked instead)
 __device__ __forceinline__ float ce_g(float s, float l2, bool hit) { return ce_p(s, l2) - (hit ? 1.0f : 0.0f); }
 
+// gBCE: e = exp(-|s|) serves both sigma(s) and softplus(s) = max(s, 0) + log(1 + e).  Below 2^-12 the log is the series e - e^2 / 2
+// (1 + e would round e away: truncation e^3 / 3 < 2^-25 e); above it 1 + e carries e to 2^-12 relative at worst, 2^-24 absolute.
+__device__ __forceinline__ float gb_e(float s) { return ce_exp2(-fabsf(s) * CE_LOG2E); }
+__device__ __forceinline__ float gb_sigma(float s, float e) {
+    const float r = __builtin_amdgcn_rcpf(1.0f + e);
+    return s >= 0.0f ? r : e * r;
+}
+__device__ __forceinline__ float gb_softplus(float s, float e) {
+    const float l = e < 0x1p-12f ? __builtin_fmaf(-0.5f * e, e, e) : __log2f(1.0f + e) * CE_LN2;
+    return fmaxf(s, 0.0f) + l;
+}
 
 // ---- the sampled-only pieces around the sweeps ---------------------------------------------------------------------------
+template <uint32_t SITE>
 __global__ __launch_bounds__(256) void k_sce_ids(SceArgs a) {
-    const uint32_t key = a.samples ? 0u : cr_site_key(a.seed, *a.step, CR_SCE_SITE);
+    const uint32_t key = a.samples ? 0u : cr_site_key(a.seed, *a.step, SITE);
     const int64_t n = (int64_t)a.N * a.D;
     for (int64_t e = blockIdx.x * 256 + threadIdx.x; e < n; e += (int64_t)gridDim.x * 256) {
         const int j = (int)(e / a.D), c = (int)(e % a.D);
@@ -502,12 +526,119 @@ __global__ __launch_bounds__(256) void k_ce_dh(A a) {
     }
 }
 
-template <class A, int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_ce_de(A a) {
-    constexpr bool S = A::SAMPLED;
+// gBCE: loss and dh from one sweep of the candidates (the sweep of k_ce_dh<SceArgs>, the prologue and epilogue of k_ce_lse<SceArgs>)
+template <int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_gbce_row(GbceArgs a) {
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
-    __shared__ float s_l2[CE_BLK];
+    __shared__ int s_id[CE_BLK];
+    __shared__ float red[3][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
+    const int q = blockIdx.x * 64 + wave * 16 + li;
+    const bool qok = q < a.M;
+    bf8 bh[NK], bl[NK];
+    {
+        float v[NK][8];
+        tk_row_issue<NK>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D);
+        tk_row_finish<NK, SPLIT>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D, bh, bl);
+    }
+    const int pq = qok ? a.pos[q] : 0, nq = (qok && a.neg) ? a.neg[q] : 0;
+    const bool ist = qok && pq != 0;
+    const float sp = sce_gathered_score<NK, SPLIT>(a, pq, qok, bh, bl);
+    float sn = 0.0f;
+    if (a.neg) {                                                    // (uniform: the tile runs with every lane on)
+        const float x = sce_gathered_score<NK, SPLIT>(a, nq, qok, bh, bl);
+        sn = nq != 0 ? x : 0.0f;                                    // neg 0: a zero score, as the catalogue's row 0
+    }
+    f32x4 acc[2 * NK];
+#pragma unroll
+    for (int i = 0; i < 2 * NK; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    float ls = 0.0f;                                                // softplus of this lane's candidates, in sweep order
+    const int end = a.N;
+    const int rounds = (end + CE_BLK - 1) / CE_BLK;
+    float v[NCB][8];
+    int nid = 0;                                                    // the ids of the next block, staged through LDS
+    blk_issue<NCB>(v, a.Es, a.D, 0, end, end - 1, a.D);
+    if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
+    for (int rd = 0; rd < rounds; ++rd) {
+        const int j0 = rd * CE_BLK;
+        blk_store<NCB, SPLIT>(v, img, a.Es, a.D, j0, end, end - 1, a.D);
+        if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
+        __syncthreads();
+        if (rd + 1 < rounds) {
+            blk_issue<NCB>(v, a.Es, a.D, j0 + CE_BLK, end, end - 1, a.D);
+            const int j = j0 + CE_BLK + threadIdx.x;
+            nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
+        }
+        float g[2][4];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+            bf8 ah[NK], al[NK];
+            img_rows<NK, NCB, SPLIT>(img, 16 * tt, ah, al);
+            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int jl = 16 * tt + 4 * lg + r;
+                const bool live = ist && j0 + jl < end && s_id[jl] != pq;       // a hit is masked
+                const float e = gb_e(c[r]);
+                g[tt][r] = live ? gb_sigma(c[r], e) : 0.0f;
+                ls += live ? gb_softplus(c[r], e) : 0.0f;
+            }
+        }
+        if (a.dh) {
+            bf8 gh, gl;
+            g_frag<SPLIT>(g, gh, gl);
+            g_times_img<NK, NCB, SPLIT>(acc, gh, gl, img, a.D);
+        }
+        __syncthreads();
+    }
+    // the row's four lane groups: a butterfly symmetric in the two partners (every lane ends with the same bits)
+    ls += __shfl_xor(ls, 16, 64);
+    ls += __shfl_xor(ls, 32, 64);
+    // the target: beta softplus(-z_pos), coefficient beta (sigma(z_pos) - 1) = -beta sigma(-z_pos)
+    const float et = gb_e(sp);
+    const float gp = ist ? -a.beta * gb_sigma(-sp, et) : 0.0f;
+    const float l = ist ? __builtin_fmaf(a.beta, gb_softplus(-sp, et), ls) : 0.0f;
+    float lr = 0.0f, ar = 0.0f, nr = 0.0f;
+    if (qok && lg == 0) {
+        a.gpos[q] = gp;
+        if (a.lse_out) a.lse_out[q] = l;
+        if (ist) {
+            lr = l;
+            const float dlt = sp - sn;                              // neg 0 (or none): row 0 reads as zeros
+            ar = a.neg ? ((dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? 0.0f : 0.5f)) : 0.0f;
+            nr = 1.0f;
+        }
+    }
+    lr = wave_sum(lr);
+    ar = wave_sum(ar);
+    nr = wave_sum(nr);
+    if (lane == 0) { red[0][wave] = lr; red[1][wave] = ar; red[2][wave] = nr; }
+    __syncthreads();
+    if (threadIdx.x < 3) a.stats[blockIdx.x * 4 + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+    if (!a.dh) return;
+    // acc[db] register r: row 16 wave + 4 lg + r of the tile (its gpos sits in lane 4 lg + r), column 16 db + li; plus gpos E_pos
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const float gpr = __shfl(gp, 4 * lg + r, 64);
+        const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
+        if (row >= a.M) continue;
+        const int pr = a.pos[row];
+        const float* er = a.E + (int64_t)pr * a.D;
+#pragma unroll
+        for (int db = 0; db < 2 * NK; ++db) {
+            const int col = 16 * db + li;
+            if (col < a.D) a.dh[(int64_t)row * a.ldd + col] = pr != 0 ? __builtin_fmaf(gpr, er[col], acc[db][r]) : 0.0f;
+        }
+    }
+}
+
+template <class A, int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_ce_de(A a) {
+    constexpr bool S = A::SAMPLED, G = A::GBCE;                     // (gBCE: no per-row statistic, so no s_l2)
+    constexpr int NCB = (NK + 1) / 2;
+    __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
+    __shared__ float s_l2[G ? 1 : CE_BLK];
     __shared__ int s_pos[CE_BLK];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
@@ -533,18 +664,27 @@ __global__ __launch_bounds__(256) void k_ce_de(A a) {
     int npos = 0;
     float nl2 = 0.0f;
     blk_issue<NCB>(v, a.h, a.ldh, rb, re, a.M - 1, a.D);
-    if (threadIdx.x < CE_BLK && rb + (int)threadIdx.x < re) { npos = a.pos[rb + threadIdx.x]; nl2 = a.lse2[rb + threadIdx.x]; }
+    if (threadIdx.x < CE_BLK && rb + (int)threadIdx.x < re) {
+        npos = a.pos[rb + threadIdx.x];
+        if constexpr (!G) nl2 = a.lse2[rb + threadIdx.x];
+    }
     for (int rd = 0; rd < rounds; ++rd) {
         const int r0 = rb + rd * CE_BLK;
         blk_store<NCB, SPLIT>(v, img, a.h, a.ldh, r0, re, a.M - 1, a.D);
-        if (threadIdx.x < CE_BLK) { s_pos[threadIdx.x] = npos; s_l2[threadIdx.x] = nl2; }
+        if (threadIdx.x < CE_BLK) {
+            s_pos[threadIdx.x] = npos;
+            if constexpr (!G) s_l2[threadIdx.x] = nl2;
+        }
         __syncthreads();
         if (rd + 1 < rounds) {
             blk_issue<NCB>(v, a.h, a.ldh, r0 + CE_BLK, re, a.M - 1, a.D);
             const int r = r0 + CE_BLK + threadIdx.x;
             npos = 0;
             nl2 = 0.0f;
-            if (threadIdx.x < CE_BLK && r < re) { npos = a.pos[r]; nl2 = a.lse2[r]; }
+            if (threadIdx.x < CE_BLK && r < re) {
+                npos = a.pos[r];
+                if constexpr (!G) nl2 = a.lse2[r];
+            }
         }
         float g[2][4];
 #pragma unroll
@@ -556,7 +696,8 @@ __global__ __launch_bounds__(256) void k_ce_de(A a) {
             for (int r = 0; r < 4; ++r) {
                 const int lr = 16 * tt + 4 * lg + r;
                 const int pr = s_pos[lr];
-                if constexpr (S) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_p(c[r], s_l2[lr]) : 0.0f;
+                if constexpr (G) g[tt][r] = (jok && pr != 0 && pr != id) ? gb_sigma(c[r], gb_e(c[r])) : 0.0f;
+                else if constexpr (S) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_p(c[r], s_l2[lr]) : 0.0f;
                 else g[tt][r] = (jok && pr != 0) ? ce_g(c[r], s_l2[lr], pr == id) : 0.0f;
             }
         }
@@ -657,13 +798,20 @@ size_t sce_workspace(int M, int N, int D, CeGeom& g) {
            cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D);
 }
 
+// gBCE workspace: the sampled one without lse2
+size_t gbce_workspace(int M, int N, int D, CeGeom& g) {
+    if (N > CR_SCE_MAX_SAMPLES || !ce_geometry(M, 0, N, D, SCE_MAX_PARTS, SCE_PART_ROWS, g)) return 0;
+    return 3 * cr_align256(4 * (size_t)N) + cr_align256(4 * (size_t)N * D) + cr_align256(4 * (size_t)M) +
+           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D);
+}
+
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 255) / 256)); }
 
 template <class A, int NK, bool SPLIT>
 void ce_launch(const A& a, const CeGeom& g, hipStream_t st) {
     constexpr bool S = A::SAMPLED;
     if constexpr (S) {
-        hipLaunchKernelGGL(k_sce_ids, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_sce_ids<CR_SCE_SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
         if (a.tg) hipLaunchKernelGGL(k_sce_dedup, dim3((a.N + 255) / 256), dim3(256), 0, st, a);
     }
     hipLaunchKernelGGL((k_ce_lse<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
@@ -679,6 +827,21 @@ void ce_launch(const A& a, const CeGeom& g, hipStream_t st) {
             const int grid = (int)std::min<int64_t>(2048, (n + 255) / 256);
             hipLaunchKernelGGL(k_ce_de_sum, dim3(grid), dim3(256), 0, st, a);
         }
+    }
+}
+
+// gBCE: seven launches (no lse / dh pair: one row sweep)
+template <int NK, bool SPLIT>
+void gbce_launch(const GbceArgs& a, const CeGeom& g, hipStream_t st) {
+    const SceArgs& s = a;
+    hipLaunchKernelGGL(k_sce_ids<CR_GBCE_SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, s);
+    if (a.tg) hipLaunchKernelGGL(k_sce_dedup, dim3((a.N + 255) / 256), dim3(256), 0, st, s);
+    hipLaunchKernelGGL((k_gbce_row<NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ce_stats<SceArgs>, dim3(1), dim3(64), 0, st, s);
+    if (a.tg) {
+        hipLaunchKernelGGL((k_ce_de<GbceArgs, NK, SPLIT>), dim3(g.n_ct, g.parts), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(k_sce_scatter, dim3(a.N), dim3(std::min(256, (a.D + 63) / 64 * 64)), 0, st, s);
+        hipLaunchKernelGGL(k_sce_tgt, dim3(grid_for((int64_t)a.M * a.D)), dim3(256), 0, st, s);
     }
 }
 
@@ -766,4 +929,48 @@ extern "C" int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream) {
     a.lse_out = d->lse_out; a.state = d->state; a.n_rt = g.n_rt;
     ce_run(a, g, d->precision, cr_stream(stream));
     return cr_check_launch("cr_sampled_ce");
+}
+
+extern "C" size_t cr_gbce_workspace(int M, int N, int D) {
+    CeGeom g;
+    return gbce_workspace(M, N, D, g);
+}
+
+extern "C" int cr_gbce(const cr_gbce_desc* d, void* stream) {
+    CR_REQUIRE(d, "cr_gbce: NULL descriptor");
+    CR_REQUIRE(d->seq_emb && d->table && d->pos && d->state, "cr_gbce: NULL seq_emb, table, pos or state");
+    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_gbce: D=%d outside 8 .. 256", d->D);
+    CR_REQUIRE(d->V >= 2, "cr_gbce: V=%d < 2 (row 0 is padding: no item to sample)", d->V);
+    CR_REQUIRE(d->M >= 1, "cr_gbce: M=%d <= 0", d->M);
+    CR_REQUIRE(d->N >= 1 && d->N <= CR_SCE_MAX_SAMPLES, "cr_gbce: N=%d outside 1 .. %d", d->N, CR_SCE_MAX_SAMPLES);
+    CR_REQUIRE(d->ld >= d->D, "cr_gbce: ld=%d < D=%d", d->ld, d->D);
+    CR_REQUIRE(!d->d_seq_emb || d->ldd >= d->D, "cr_gbce: ldd=%d < D=%d", d->ldd, d->D);
+    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
+               "cr_gbce: unknown precision %d", d->precision);
+    CR_REQUIRE(d->beta > 0.0f && d->beta <= 1.0f, "cr_gbce: beta=%g outside (0, 1]", (double)d->beta);     // (NaN fails both)
+    CR_REQUIRE(d->samples || d->step, "cr_gbce: NULL step with NULL samples (the device draw reads the step word)");
+    CeGeom g;
+    const size_t need = gbce_workspace(d->M, d->N, d->D, g);
+    CR_REQUIRE(need, "cr_gbce: unsupported shape");
+    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_gbce: workspace of %zu bytes, cr_gbce_workspace says %zu",
+               d->workspace ? d->workspace_bytes : (size_t)0, need);
+
+    unsigned char* w = static_cast<unsigned char*>(d->workspace);
+    GbceArgs a;
+    a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
+    a.M = d->M; a.D = d->D; a.V = d->V; a.N = d->N; a.beta = d->beta;
+    a.samples = d->samples; a.seed = d->seed; a.step = d->step; a.samples_out = d->samples_out;
+    a.sid = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
+    a.nxt = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
+    a.head = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
+    a.Es = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->N * d->D);
+    a.lse2 = nullptr;
+    a.gpos = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
+    a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
+    a.part = reinterpret_cast<float*>(w);
+    a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
+    a.rpp = g.rpp; a.parts = g.parts;
+    a.lse_out = d->loss_out; a.state = d->state; a.n_rt = g.n_rt;
+    tk_dispatch(g.NK, d->precision != CR_PREC_BF16, [&](auto nk, auto split) { gbce_launch<nk, split>(a, g, cr_stream(stream)); });
+    return cr_check_launch("cr_gbce");
 }

@@ -33,8 +33,11 @@ DEFAULT_ATTN_PRECISION = "bf16x3"
 LOSSES = ("bce", "ce")
 # ... and "sampled_ce": softmax cross-entropy over the target and ce_negatives items drawn uniformly for the whole batch
 # (cr_sampled_ce)
-ALL_LOSSES = LOSSES + ("sampled_ce",)
-SOFTMAX_LOSSES = ("ce", "sampled_ce")
+# ... and "gbce": gSASRec's generalised binary cross-entropy over the target and the same kind of shared negatives, the positive
+# term weighted by beta from the sampling rate and gbce_t (cr_gbce)
+ALL_LOSSES = LOSSES + ("sampled_ce", "gbce")
+SOFTMAX_LOSSES = ("ce", "sampled_ce", "gbce")     # the losses that take the route of "ce" (one launch in op_head, d(seq_emb) stored)
+SAMPLED_LOSSES = ("sampled_ce", "gbce")
 
 MODELS = ["cast_1", "cast_2", "cast_3", "cast_4", "cast_5", "cast_6", "cast_7", "cast_8", "cast_9",
           "sasrec", "sasrec_static"]          # main.py:28
@@ -58,7 +61,7 @@ class Hyper:
 
     def __init__(self, args=None, **kw):
         d = dict(maxlen=50, hidden_units=50, num_blocks=2, num_heads=1, dropout_rate=0.5, l2_emb=0.0, lr=1e-3,
-                 max_bins=200, num_context_blocks=2, seed=42, loss="bce", ce_negatives=256)
+                 max_bins=200, num_context_blocks=2, seed=42, loss="bce", ce_negatives=256, gbce_t=0.75)
         for k in d:
             if args is not None and hasattr(args, k):
                 d[k] = getattr(args, k)
@@ -187,7 +190,7 @@ class ParamLayout:
 class Engine:
     def __init__(self, model, usernum, itemnum, hp, batch_size, training=True, seed=None, n_slabs=None,
                  share=None, batch_global=None, row_offset=0, want_attn=False, device="cuda", fused=None,
-                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None):
+                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None, gbce_t=None):
         """loss: the training objective, "bce" (the default: hp.loss, else "bce") or "ce" -- full-catalogue softmax cross-entropy
         (cr_softmax_ce).  Under "ce" the prediction head is one cr_softmax_ce launch that stores d(seq_emb) and accumulates the item
         table's gradient into Gt; the occurrence index and the head fusions are off, so the embedding backward scatters with float
@@ -195,7 +198,11 @@ class Engine:
         (ValueError).  Eval engines ignore the option.
         "sampled_ce" takes the route of "ce" with one cr_sampled_ce launch: the softmax over each row's target and ce_negatives
         (default hp.ce_negatives, else 256) item ids drawn uniformly on the device for the whole batch from the engine's seed and step
-        word; eng.samples holds the last step's ids.  It refuses what "ce" refuses and ce_negatives outside 1..CR_SCE_MAX_SAMPLES."""
+        word; eng.samples holds the last step's ids.  It refuses what "ce" refuses and ce_negatives outside 1..CR_SCE_MAX_SAMPLES.
+        "gbce" takes the route of "sampled_ce" with one cr_gbce launch: binary cross-entropy over the target and ce_negatives shared
+        uniform negatives, the positive term weighted by eng.gbce_beta = 1 - t (1 - alpha), alpha = min(1, ce_negatives / max(1,
+        itemnum - 1)) the sampling rate over the items that are not the target and t = gbce_t (default hp.gbce_t, else 0.75; the
+        calibration parameter of gSASRec: 0 is plain BCE, 1 is fully calibrated).  It also refuses gbce_t outside [0, 1]."""
         if model not in MODELS:
             raise ValueError("model must be one of %s" % MODELS)
         if not torch.cuda.is_available():
@@ -223,8 +230,12 @@ class Engine:
         if ce_negatives is None:
             ce_negatives = getattr(hp, "ce_negatives", None) or 256
         self.ce_negatives = int(ce_negatives)
+        if gbce_t is None:
+            gbce_t = getattr(hp, "gbce_t", None)
+            gbce_t = 0.75 if gbce_t is None else gbce_t
+        self.gbce_t = float(gbce_t)
         if self.loss in SOFTMAX_LOSSES:
-            op = "cr_softmax_ce" if self.loss == "ce" else "cr_sampled_ce"
+            op = {"ce": "cr_softmax_ce", "sampled_ce": "cr_sampled_ce", "gbce": "cr_gbce"}[self.loss]
             if self.lazy_adam:
                 raise ValueError("loss='%s' does not take row-sparse Adam (lazy_adam): every item row has a gradient" % self.loss)
             if (batch_global is not None and batch_global != batch_size) or row_offset:
@@ -232,9 +243,15 @@ class Engine:
                                  % self.loss)
             if not 8 <= hp.hidden_units <= 256:
                 raise ValueError("loss='%s' needs 8 <= hidden_units <= 256 (%s), got %d" % (self.loss, op, hp.hidden_units))
-        if self.loss == "sampled_ce" and not 1 <= self.ce_negatives <= L.CR_SCE_MAX_SAMPLES:
-            raise ValueError("loss='sampled_ce' needs 1 <= ce_negatives <= %d (cr_sampled_ce), got %d"
-                             % (L.CR_SCE_MAX_SAMPLES, self.ce_negatives))
+        if self.loss in SAMPLED_LOSSES and not 1 <= self.ce_negatives <= L.CR_SCE_MAX_SAMPLES:
+            raise ValueError("loss='%s' needs 1 <= ce_negatives <= %d (%s), got %d"
+                             % (self.loss, L.CR_SCE_MAX_SAMPLES, op, self.ce_negatives))
+        if self.loss == "gbce":
+            if not 0.0 <= self.gbce_t <= 1.0:                      # (NaN fails too)
+                raise ValueError("loss='gbce' needs 0 <= gbce_t <= 1, got %r" % (gbce_t,))
+            # the sampling rate over the pool of negatives (the itemnum - 1 items that are not the target), gSASRec eq. for beta
+            alpha = min(1.0, self.ce_negatives / max(1, itemnum - 1))
+            self.gbce_beta = 1.0 - self.gbce_t * (1.0 - alpha)
         self.M = self.B * self.T
         self.usernum, self.itemnum = usernum, itemnum
         self.training = training
@@ -302,9 +319,10 @@ class Engine:
             self.Gs = torch.zeros(n_slabs, max(lay.n_dense, 1), **f32)
             if self.loss in SOFTMAX_LOSSES:
                 nb = (O.softmax_ce_workspace_bytes(self.M, itemnum + 1, self.D) if self.loss == "ce"
-                      else O.sampled_ce_workspace_bytes(self.M, self.ce_negatives, self.D))
+                      else O.sampled_ce_workspace_bytes(self.M, self.ce_negatives, self.D) if self.loss == "sampled_ce"
+                      else O.gbce_workspace_bytes(self.M, self.ce_negatives, self.D))
                 self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
-            if self.loss == "sampled_ce":
+            if self.loss in SAMPLED_LOSSES:
                 self.samples = torch.zeros(self.ce_negatives, dtype=torch.int32, device=self.dev)    # the last step's sample ids
         self.drop = O.Drop(hp.dropout_rate if training else 0.0, self.seed, self.state, row_offset)
         self.batch_global = self.B if batch_global is None else batch_global
@@ -1027,6 +1045,11 @@ class Engine:
             if self.loss == "ce":
                 op = "cr_softmax_ce"
                 d = L.SoftmaxCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, prec, self.state.data_ptr(), *tail)
+            elif self.loss == "gbce":
+                op = "cr_gbce"
+                d = L.GbceDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, self.ce_negatives, prec, self.gbce_beta,
+                               None, self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
+                               *tail)
             else:
                 op = "cr_sampled_ce"
                 d = L.SampledCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, self.ce_negatives, prec, None,

@@ -30,6 +30,7 @@ CR_MAX_BATCH = 4
 CR_STATE_FLOATS = 16
 CR_SCE_MAX_SAMPLES = 16384       # castrec.h: sample ids per cr_sampled_ce call at most
 CR_SCE_SITE = 0x5CE00000         # castrec.h: the cr_site_key site of cr_sampled_ce's device draw
+CR_GBCE_SITE = 0x6BCE0000        # castrec.h: the cr_site_key site of cr_gbce's device draw
 PREC_F32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
 ELT_COPY, ELT_ADD, ELT_DROPOUT, ELT_RELU_BWD, ELT_ROWMASK, ELT_GRADPREP = 0, 1, 2, 3, 4, 5
 
@@ -164,6 +165,13 @@ class SampledCeDesc(C.Structure):
                 ("workspace_bytes", C.c_size_t)]
 
 
+class GbceDesc(C.Structure):
+    _fields_ = [("seq_emb", c_p), ("ld", c_i), ("table", c_p), ("pos", c_p), ("neg", c_p), ("M", c_i), ("D", c_i), ("V", c_i),
+                ("N", c_i), ("precision", c_i), ("beta", c_f), ("samples", c_p), ("seed", C.c_uint32), ("step", c_p),
+                ("samples_out", c_p), ("state", c_p), ("d_seq_emb", c_p), ("ldd", c_i), ("table_grad", c_p), ("loss_out", c_p),
+                ("workspace", c_p), ("workspace_bytes", C.c_size_t)]
+
+
 def _sig(name, restype, argtypes):
     f = getattr(_lib, name)
     f.restype = restype
@@ -239,6 +247,8 @@ _sig("cr_softmax_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_softmax_ce", c_i, [C.POINTER(SoftmaxCeDesc), c_p])
 _sig("cr_sampled_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_sampled_ce", c_i, [C.POINTER(SampledCeDesc), c_p])
+_sig("cr_gbce_workspace", C.c_size_t, [c_i, c_i, c_i])
+_sig("cr_gbce", c_i, [C.POINTER(GbceDesc), c_p])
 
 EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "cr_embed_fwd", "cr_embed_bwd", "cr_layernorm_fwd",
            "cr_layernorm_bwd", "cr_gemm_rows", "cr_gemm_wgrad", "cr_eltwise", "cr_attn_fwd", "cr_attn_bwd",
@@ -248,7 +258,7 @@ EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "
            "cr_graph_destroy", "cr_sampler_create", "cr_sampler_next", "cr_sampler_destroy",
            "cr_tgrad_geometry", "cr_batch_index_layout", "cr_index_builder_create", "cr_index_build", "cr_index_builder_destroy", "cr_table_grad",
            "cr_score_topk_workspace", "cr_score_topk", "cr_softmax_ce_workspace", "cr_softmax_ce",
-           "cr_sampled_ce_workspace", "cr_sampled_ce"]
+           "cr_sampled_ce_workspace", "cr_sampled_ce", "cr_gbce_workspace", "cr_gbce"]
 
 lib = _lib
 

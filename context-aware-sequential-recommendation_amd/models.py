@@ -41,7 +41,7 @@ class _Model(object):
         exchange for large tables) before an identical Adam step on every rank.  Call before the first train_step."""
         if self._train is not None:
             raise RuntimeError("data_parallel() must be called before the first train_step")
-        if getattr(self.hp, "loss", "bce") in ("ce", "sampled_ce") and int(world) > 1:
+        if getattr(self.hp, "loss", "bce") in ("ce", "sampled_ce", "gbce") and int(world) > 1:
             raise ValueError("loss='%s' does not take data parallelism (castrec_amd.engine.Engine)" % self.hp.loss)
         self._dp_cfg = (int(rank), int(world), process_group, sparse)
 

@@ -192,6 +192,27 @@ def sampled_ce(seq_emb, ld, table, pos, state, workspace, M, N, precision=L.PREC
     L.call("cr_sampled_ce", C.byref(d), _stream())
 
 
+def gbce_workspace_bytes(M, N, D):
+    n = L.lib.cr_gbce_workspace(M, N, D)
+    if n == 0:
+        raise ValueError("cr_gbce: unsupported shape M=%d N=%d D=%d (M >= 1, 1 <= N <= %d, 8 <= D <= 256)"
+                         % (M, N, D, L.CR_SCE_MAX_SAMPLES))
+    return n
+
+
+def gbce(seq_emb, ld, table, pos, state, workspace, M, N, beta=1.0, precision=L.PREC_BF16X3, neg=None, samples=None, seed=0, step=None,
+         samples_out=None, d_seq_emb=None, ldd=0, table_grad=None, loss_out=None):
+    """cr_gbce: gSASRec's generalised binary cross-entropy over each row's target (weight beta in (0, 1]) and N shared sample ids.
+    Arguments as sampled_ce; loss_out float32 [M] takes each row's loss where given; workspace a uint8 CUDA tensor of at least
+    gbce_workspace_bytes(M, N, D) bytes."""
+    d = L.GbceDesc(_p(_f32(seq_emb, "seq_emb")), ld, _p(_f32(table, "table")), _p(_i32(pos, "pos")), _p(_i32(neg, "neg")),
+                   M, table.shape[1], table.shape[0], N, precision, float(beta), _p(_i32(samples, "samples")), int(seed) & 0xFFFFFFFF,
+                   _p(step), _p(_i32(samples_out, "samples_out")), _p(_f32(state, "state")), _p(_f32(d_seq_emb, "d_seq_emb")),
+                   ldd, _p(_f32(table_grad, "table_grad")), _p(_f32(loss_out, "loss_out")), _p(workspace),
+                   workspace.numel() * workspace.element_size())
+    L.call("cr_gbce", C.byref(d), _stream())
+
+
 def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, state, beta1=0.9, beta2=0.98, eps=1e-8,
               stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None):
     d = L.AdamDesc(_p(p), _p(m), _p(v), _p(table_grad), _p(dense_slabs), n_table, n_dense, n_slabs, lr, beta1, beta2,

@@ -551,6 +551,55 @@ struct cr_sampled_ce_desc {
 size_t cr_sampled_ce_workspace(int M, int N, int D);       /* 0 for a shape outside the supported range */
 int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream);
 
+/* ---- gBCE: generalised binary cross-entropy over shared uniform negatives (gSASRec; csrc/cr_ce.hip) ---------------
+ * The objective Petrov & Macdonald (RecSys 2023) give for training on a sampled candidate set: binary cross-entropy over the target
+ * and N negatives with the positive probability raised to a power beta (its log term weighted by beta), which undoes the
+ * overconfidence a sampled softmax learns.  Rows, ids, samples, accidental hits and duplicates are cr_sampled_ce's: a sample equal to a
+ * row's target is dropped from that row only; a duplicate counts as its own candidate.  With sigma the logistic function and
+ * softplus(x) = log(1 + exp x):
+ *   z_mv = h_m . E_v;  l_m = beta softplus(-z_{m,pos}) + sum_{j: s_j != pos_m} softplus(z_{m,s_j}).
+ *   state: [0] += sum_m istarget_m l_m; [1], [2] and the snapshot [8..11] exactly as cr_sampled_ce (the AUC reads the per-position
+ *   neg ids only); cr_adam_step runs unchanged.
+ *   d_seq_emb (optional, WRITTEN): dh_m = istarget_m (beta (sigma_{m,pos} - 1) E_pos + sum_j sigma_mj E_{s_j}); zero rows where pos is 0.
+ *   table_grad (optional, ACCUMULATED): dE_{s_j} += sum_m istarget_m sigma_mj h_m and dE_{pos_m} += istarget_m beta (sigma_{m,pos} - 1)
+ *   h_m (sigma_mj = 0 at a hit).  Row 0 is never written; rows that are neither a sample nor a target are not touched.
+ *   loss_out (optional, [M]): istarget_m l_m.   samples_out (optional, device [N]): the ids used.
+ * Gradients are un-normalised, like the other heads'.  beta in (0, 1] is the caller's (1: plain BCE over many negatives); the engine
+ * sets it from the sampling rate.
+ * Samples: as cr_sampled_ce, with a site of its own in the device draw -- key = cr_site_key(seed, *step, CR_GBCE_SITE), then the same
+ * x_j and s_j -- so a gBCE run and a sampled-CE run with one seed do not share negatives.
+ * A pointwise objective has no normaliser: one sweep of the candidates per row gives the loss and d_seq_emb (cr_sampled_ce takes two),
+ * seven launches against eight.  softplus is evaluated in fp32 as max(z, 0) + log(1 + e), e = exp(-|z|), with the series e - e^2 / 2
+ * below e = 2^-12, so a row of very negative scores loses nothing to 1 + e rounding to 1.
+ * Reproducibility: as cr_sampled_ce -- only the target term of table_grad uses float atomics.
+ *   - precision: CR_PREC_BF16X3 or CR_PREC_BF16; CR_PREC_F32 takes the bf16x3 path.
+ *   - shapes: 8 <= D <= 256, V >= 2, M >= 1, 1 <= N <= CR_SCE_MAX_SAMPLES, ld >= D, ldd >= D.
+ *   - workspace: at least cr_gbce_workspace(M, N, D) bytes of device memory, O(M + N D), independent of V; it never decreases as M or
+ *     N grows. */
+#define CR_GBCE_SITE 0x6BCE0000u     /* the draw's cr_site_key site (outside the 24-bit dropout site ids, not CR_SCE_SITE) */
+typedef struct cr_gbce_desc cr_gbce_desc;
+struct cr_gbce_desc {
+    const float* seq_emb; int ld;     /* [M] rows of D floats, pitch ld */
+    const float* table;               /* [V, D] */
+    const int32_t* pos;               /* device [M]: target ids, 0 = padding row */
+    const int32_t* neg;               /* device [M] or NULL: sampled negatives, for the AUC only */
+    int M, D, V, N;
+    int precision;                    /* CR_PREC_* */
+    float beta;                       /* weight of the positive term, 0 < beta <= 1 */
+    const int32_t* samples;           /* device [N] ids in [1, V), or NULL: drawn from (seed, *step) */
+    uint32_t seed;
+    const uint32_t* step;             /* device step word (state + 4); required when samples is NULL */
+    int32_t* samples_out;             /* optional device [N] */
+    float* state;                     /* CR_STATE_FLOATS: [0..2] +=, snapshot [8..11] */
+    float* d_seq_emb; int ldd;        /* optional [M] rows, pitch ldd */
+    float* table_grad;                /* optional [V, D], accumulated */
+    float* loss_out;                  /* optional [M] */
+    void* workspace;
+    size_t workspace_bytes;
+};
+size_t cr_gbce_workspace(int M, int N, int D);             /* 0 for a shape outside the supported range */
+int cr_gbce(const cr_gbce_desc* d, void* stream);
+
 /* ---- occurrence index of a batch (round 5; csrc/cr_index.cpp, csrc/cr_tgrad.hip) ---------------------------------
  * The gradient of a looked-up table row is the sum of the gradient rows of every position that looked it up: the three
  * lookups of the item table (seq ids: modules.py:157 through sasrec.py:27; pos / neg ids: sasrec.py:89-90) and the learned

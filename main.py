@@ -55,12 +55,16 @@ def parse_args(argv=None):
     parser.add_argument('--eval_every', type=int, default=20, help='evaluate + checkpoint every N epochs (reference: 20)')
     parser.add_argument('--eval_full_ranking', action='store_true',
                         help='also log NDCG@10 / HR@10 over the full catalogue (every item outside the user\'s rated set) at each evaluation')
-    parser.add_argument('--loss', default='bce', choices=['bce', 'ce', 'sampled_ce'],
+    parser.add_argument('--loss', default='bce', choices=['bce', 'ce', 'sampled_ce', 'gbce'],
                         help='training objective: bce = the reference\'s pos / neg BCE with one sampled negative; ce = softmax '
                              'cross-entropy over the whole item catalogue; sampled_ce = softmax cross-entropy over the target and '
-                             '--ce_negatives items drawn uniformly for the whole batch')
+                             '--ce_negatives items drawn uniformly for the whole batch; gbce = gSASRec\'s generalised binary cross-entropy '
+                             'over the same kind of negatives, calibrated by --gbce_t')
     parser.add_argument('--ce_negatives', type=int, default=256,
-                        help='sampled_ce: shared uniform negatives per training step (1 .. 16384)')
+                        help='sampled_ce, gbce: shared uniform negatives per training step (1 .. 16384)')
+    parser.add_argument('--gbce_t', type=float, default=0.75,
+                        help='gbce: calibration parameter t in [0, 1] (0 = plain BCE over the negatives, 1 = fully calibrated); the '
+                             'positive term\'s weight is beta = 1 - t (1 - sampling rate)')
     return parser.parse_args(argv)
 
 
