@@ -8,7 +8,9 @@
 //    the item sweep is de without a per-row statistic; ids, dedup, stats, scatter and tgt are the sampled op's.
 // The two softmax ops run the same four sweep passes, templated on the candidate kind -- the argument struct: CeArgs, the catalogue, whose candidates
 // are the items 1 .. V-1 of E with the target among them; SceArgs, the sampled, whose candidates are the N gathered rows Es with the
-// target beside them (a sample equal to a row's target is masked; the target's own terms come separately):
+// target beside them (a sample equal to a row's target is masked; the target's own terms come separately); ScePopArgs, the sampled
+// under a popularity proposal, whose every candidate score carries the log-Q correction -logq[id] (castrec.h) as a base-2 bias that
+// travels beside the ids:
 //
 //  * lse    (a workgroup per 64 rows, 256 threads).  Each wave keeps its 16 rows as B fragments in registers; the workgroup streams the
 //           candidates through an LDS image of 32 rows (bf16 hi / lo, cr_bf16.hpp img_off<2>), filled from registers loaded a block
@@ -30,7 +32,9 @@
 // Around the sweeps, per op:
 //  * de_sum  (catalogue, parts > 1) adds the parts into table_grad in part order.
 //  * ids     (sampled; grid-stride over N x D).  Copy or draw the N ids (castrec.h states the draw), write them and samples_out, and
-//            gather the N rows of E into the compact fp32 table Es [N, D] of the workspace.
+//            gather the N rows of E into the compact fp32 table Es [N, D] of the workspace.  Popularity proposal (ids_pop): the id of
+//            a sample is found once, by the workgroup that holds its first element -- a copy, or the binary search of the cdf -- and
+//            handed to the gathering threads through LDS; the same thread writes the sample's bias -logq[id] log2 e.
 //  * dedup   (sampled, a thread per sample; only with table_grad).  For sample j: whether it is its id's first occurrence, and the next
 //            j' > j with the same id (a linked list in j order).  Each thread compares its id against all N through LDS chunks: O(N^2)
 //            compares, a few microseconds at N = 4096.
@@ -58,7 +62,7 @@ constexpr int SCE_MAX_PARTS = 64;
 constexpr int SCE_CHUNK = 2048;             // ids per LDS chunk of the dedup pass
 
 struct CeArgs {
-    static constexpr bool SAMPLED = false, GBCE = false;
+    static constexpr bool SAMPLED = false, GBCE = false, POP = false;
     const float* h; int64_t ldh;
     const float* E;
     const int32_t* pos; const int32_t* neg;
@@ -75,7 +79,7 @@ struct CeArgs {
 };
 
 struct SceArgs {
-    static constexpr bool SAMPLED = true, GBCE = false;
+    static constexpr bool SAMPLED = true, GBCE = false, POP = false;
     const float* h; int64_t ldh;
     const float* E;
     const int32_t* pos; const int32_t* neg;
@@ -103,6 +107,14 @@ struct SceArgs {
 struct GbceArgs : SceArgs {
     static constexpr bool GBCE = true;
     float beta;                             // weight of the positive term, (0, 1]
+};
+
+// sampled softmax under a popularity proposal: z' = z - logq[id] for every candidate, the target included (castrec.h)
+struct ScePopArgs : SceArgs {
+    static constexpr bool POP = true;
+    const uint32_t* cdf;                    // [V] the proposal's cumulative masses in units of 2^-32 (device draw), or NULL
+    const float* logq;                      // [V] log Q(v); [0] = 0
+    float* sb;                              // [N] the samples' base-2 biases -logq[s_j] log2 e
 };
 
 // ---- the streamed block ---------------------------------------------------------------------------------------------------
@@ -199,6 +211,8 @@ __device__ __forceinline__ float ce_exp2(float x) { return __builtin_amdgcn_exp2
 
 // p of one (row, candidate) score for a target row (l2: the row's lse2).  The same expression in dh and de: the same bits.
 __device__ __forceinline__ float ce_p(float s, float l2) { return ce_exp2(__builtin_fmaf(s, CE_LOG2E, -l2)); }
+// ... of a corrected score (b: the candidate's base-2 bias)
+__device__ __forceinline__ float ce_pb(float s, float b, float l2) { return ce_exp2(__builtin_fmaf(s, CE_LOG2E, b) - l2); }
 // catalogue: p - [v = pos] (a sampled hit is masked instead)
 __device__ __forceinline__ float ce_g(float s, float l2, bool hit) { return ce_p(s, l2) - (hit ? 1.0f : 0.0f); }
 
@@ -232,6 +246,49 @@ __global__ __launch_bounds__(256) void k_sce_ids(SceArgs a) {
         if (c == 0) {
             a.sid[j] = id;
             if (a.samples_out) a.samples_out[j] = id;
+        }
+    }
+}
+
+// Popularity proposal.  A workgroup takes 256 consecutive elements of [N, D] per round: they span at most 256 / 8 + 1 samples, whose
+// ids the first threads copy or draw -- s_j = the smallest s in [1, V-1] with x_j < cdf[s], cdf[V-1] read as 2^32: ceil(log2 V)
+// dependent loads, once per sample -- and leave in LDS for the gather.  The workgroup that holds a sample's column 0 writes its id,
+// samples_out and bias (one writer per sample).
+constexpr int SCE_POP_IDS = 256 / 8 + 1;
+__global__ __launch_bounds__(256) void k_sce_ids_pop(ScePopArgs a) {
+    __shared__ int s_ids[SCE_POP_IDS];
+    const uint32_t key = a.samples ? 0u : cr_site_key(a.seed, *a.step, CR_SCE_SITE);
+    const int64_t n = (int64_t)a.N * a.D;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < n; base += (int64_t)gridDim.x * 256) {
+        const int jf = (int)(base / a.D), jl = (int)(std::min<int64_t>(base + 255, n - 1) / a.D);
+        __syncthreads();                                            // (the round before has read s_ids)
+        if ((int)threadIdx.x <= jl - jf) {
+            const int j = jf + threadIdx.x;
+            int id;
+            if (a.samples) {
+                id = a.samples[j];
+            } else {
+                const uint32_t x = cr_fmix32(key + (uint32_t)j * CR_PHI);
+                int lo = 1, hi = a.V - 1;                           // (cdf[V-1] is never read: it stands for 2^32 > x)
+                while (lo < hi) {
+                    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+                    if (x < a.cdf[mid]) hi = mid;
+                    else lo = mid + 1;
+                }
+                id = lo;
+            }
+            s_ids[threadIdx.x] = id;
+            if ((int64_t)j * a.D >= base) {
+                a.sid[j] = id;
+                if (a.samples_out) a.samples_out[j] = id;
+                a.sb[j] = -a.logq[id] * CE_LOG2E;
+            }
+        }
+        __syncthreads();
+        const int64_t e = base + threadIdx.x;
+        if (e < n) {
+            const int j = (int)(e / a.D), c = (int)(e % a.D);
+            a.Es[e] = a.E[(int64_t)s_ids[j - jf] * a.D + c];
         }
     }
 }
@@ -285,13 +342,21 @@ __device__ __forceinline__ float sce_gathered_score(const SceArgs& a, int id, bo
     return sce_diag<NK, SPLIT>(th, tl, bh, bl);
 }
 
-// ---- the sweep passes (A: CeArgs or SceArgs) -----------------------------------------------------------------------------
+// popularity: what a thread stages for the block of samples j0 .. j0 + 31 -- threads 0 .. 31 the ids, threads 32 .. 63 the biases'
+// bits (one register for both, as the ids alone take)
+__device__ __forceinline__ int sce_pop_stage(const ScePopArgs& a, int j0) {
+    const int j = j0 + (threadIdx.x & (CE_BLK - 1));
+    if (threadIdx.x >= 2 * CE_BLK || j >= a.N) return 0;
+    return threadIdx.x < CE_BLK ? a.sid[j] : __float_as_int(a.sb[j]);
+}
+
+// ---- the sweep passes (A: CeArgs, SceArgs or ScePopArgs) ------------------------------------------------------------------
 template <class A, int NK, bool SPLIT>
 __global__ __launch_bounds__(256) void k_ce_lse(A a) {
-    constexpr bool S = A::SAMPLED;
+    constexpr bool S = A::SAMPLED, P = A::POP;
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
-    __shared__ int s_id[CE_BLK];                                    // (sampled)
+    __shared__ int s_id[P ? 2 * CE_BLK : CE_BLK];                   // (sampled; popularity: the biases' bits behind the ids)
     __shared__ float red[3][4];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int q = blockIdx.x * 64 + wave * 16 + li;
@@ -311,8 +376,9 @@ __global__ __launch_bounds__(256) void k_ce_lse(A a) {
             sn = nq != 0 ? x : 0.0f;                                // neg 0: a zero score, as the catalogue's row 0
         }
     }
-    // sampled: the target is lane group 0's first candidate
-    const float tp = sp * CE_LOG2E;
+    // sampled: the target is lane group 0's first candidate (popularity: corrected as every candidate; a padded row reads logq[0] = 0)
+    float tp = sp * CE_LOG2E;
+    if constexpr (P) tp = __builtin_fmaf(sp, CE_LOG2E, -a.logq[pq] * CE_LOG2E);
     float mx = (S && lg == 0) ? tp : -INFINITY, s_in = (S && lg == 0) ? 1.0f : 0.0f, s_out = 0.0f;
     const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
     int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
@@ -322,15 +388,19 @@ __global__ __launch_bounds__(256) void k_ce_lse(A a) {
     float v[NCB][8];
     int nid = 0;                                                    // (sampled: the ids of the next block, staged through LDS)
     blk_issue<NCB>(v, src, a.D, c0, end, end - 1, a.D);
-    if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
+    if constexpr (P) nid = sce_pop_stage(a, 0);
+    else if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
     for (int rd = 0; rd < rounds; ++rd) {
         const int j0 = c0 + rd * CE_BLK;
         blk_store<NCB, SPLIT>(v, img, src, a.D, j0, end, end - 1, a.D);
-        if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
+        if constexpr (P) { if (threadIdx.x < 2 * CE_BLK) s_id[threadIdx.x] = nid; }
+        else if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
         __syncthreads();
         if (rd + 1 < rounds) {
             blk_issue<NCB>(v, src, a.D, j0 + CE_BLK, end, end - 1, a.D);
-            if constexpr (S) {
+            if constexpr (P) {
+                nid = sce_pop_stage(a, j0 + CE_BLK);
+            } else if constexpr (S) {
                 const int j = j0 + CE_BLK + threadIdx.x;
                 nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
             }
@@ -354,7 +424,8 @@ __global__ __launch_bounds__(256) void k_ce_lse(A a) {
                     sp = (ok && id == pq) ? c[r] : sp;
                     sn = (ok && id == nq) ? c[r] : sn;
                 }
-                t[tt][r] = ok ? c[r] * CE_LOG2E : -INFINITY;
+                if constexpr (P) t[tt][r] = ok ? __builtin_fmaf(c[r], CE_LOG2E, __int_as_float(s_id[CE_BLK + jl])) : -INFINITY;
+                else t[tt][r] = ok ? c[r] * CE_LOG2E : -INFINITY;
                 bm = fmaxf(bm, t[tt][r]);
             }
         }
@@ -435,10 +506,10 @@ __global__ __launch_bounds__(64) void k_ce_stats(A a) {
 
 template <class A, int NK, bool SPLIT>
 __global__ __launch_bounds__(256) void k_ce_dh(A a) {
-    constexpr bool S = A::SAMPLED;
+    constexpr bool S = A::SAMPLED, P = A::POP;
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
-    __shared__ int s_id[CE_BLK];                                    // (sampled)
+    __shared__ int s_id[P ? 2 * CE_BLK : CE_BLK];                   // (sampled; popularity: the biases' bits behind the ids)
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int q = blockIdx.x * 64 + wave * 16 + li;
     const bool qok = q < a.M;
@@ -462,15 +533,19 @@ __global__ __launch_bounds__(256) void k_ce_dh(A a) {
     float v[NCB][8];
     int nid = 0;                                                    // (sampled: the ids of the next block, staged through LDS)
     blk_issue<NCB>(v, src, a.D, c0, end, end - 1, a.D);
-    if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
+    if constexpr (P) nid = sce_pop_stage(a, 0);
+    else if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
     for (int rd = 0; rd < rounds; ++rd) {
         const int j0 = c0 + rd * CE_BLK;
         blk_store<NCB, SPLIT>(v, img, src, a.D, j0, end, end - 1, a.D);
-        if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
+        if constexpr (P) { if (threadIdx.x < 2 * CE_BLK) s_id[threadIdx.x] = nid; }
+        else if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
         __syncthreads();
         if (rd + 1 < rounds) {
             blk_issue<NCB>(v, src, a.D, j0 + CE_BLK, end, end - 1, a.D);
-            if constexpr (S) {
+            if constexpr (P) {
+                nid = sce_pop_stage(a, j0 + CE_BLK);
+            } else if constexpr (S) {
                 const int j = j0 + CE_BLK + threadIdx.x;
                 nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
             }
@@ -483,7 +558,10 @@ __global__ __launch_bounds__(256) void k_ce_dh(A a) {
             const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (S) {
+                if constexpr (P) {
+                    const int jl = 16 * tt + 4 * lg + r;
+                    g[tt][r] = (ist && j0 + jl < end && s_id[jl] != pq) ? ce_pb(c[r], __int_as_float(s_id[CE_BLK + jl]), l2) : 0.0f;
+                } else if constexpr (S) {
                     const int jl = 16 * tt + 4 * lg + r;
                     g[tt][r] = (ist && j0 + jl < end && s_id[jl] != pq) ? ce_p(c[r], l2) : 0.0f;     // a hit is masked
                 } else {
@@ -635,7 +713,7 @@ __global__ __launch_bounds__(256) void k_gbce_row(GbceArgs a) {
 
 template <class A, int NK, bool SPLIT>
 __global__ __launch_bounds__(256) void k_ce_de(A a) {
-    constexpr bool S = A::SAMPLED, G = A::GBCE;                     // (gBCE: no per-row statistic, so no s_l2)
+    constexpr bool S = A::SAMPLED, G = A::GBCE, P = A::POP;         // (gBCE: no per-row statistic, so no s_l2)
     constexpr int NCB = (NK + 1) / 2;
     __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
     __shared__ float s_l2[G ? 1 : CE_BLK];
@@ -649,6 +727,8 @@ __global__ __launch_bounds__(256) void k_ce_de(A a) {
     const bool jok = j < end;
     int id = j;                                                     // the candidate's item id
     if constexpr (S) id = jok ? a.sid[j] : -1;
+    float bj = 0.0f;                                                // (popularity: the candidate's base-2 bias)
+    if constexpr (P) bj = jok ? a.sb[j] : 0.0f;
     bf8 bh[NK], bl[NK];
     {
         float v[NK][8];
@@ -696,7 +776,8 @@ __global__ __launch_bounds__(256) void k_ce_de(A a) {
             for (int r = 0; r < 4; ++r) {
                 const int lr = 16 * tt + 4 * lg + r;
                 const int pr = s_pos[lr];
-                if constexpr (G) g[tt][r] = (jok && pr != 0 && pr != id) ? gb_sigma(c[r], gb_e(c[r])) : 0.0f;
+                if constexpr (P) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_pb(c[r], bj, s_l2[lr]) : 0.0f;
+                else if constexpr (G) g[tt][r] = (jok && pr != 0 && pr != id) ? gb_sigma(c[r], gb_e(c[r])) : 0.0f;
                 else if constexpr (S) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_p(c[r], s_l2[lr]) : 0.0f;
                 else g[tt][r] = (jok && pr != 0) ? ce_g(c[r], s_l2[lr], pr == id) : 0.0f;
             }
@@ -791,11 +872,12 @@ size_t ce_workspace(int M, int V, int D, CeGeom& g) {
 size_t sce_part_rows(int N) { return std::min<size_t>((size_t)SCE_MAX_PARTS * N, std::max<size_t>(N, SCE_PART_ROWS)); }
 
 // sampled workspace: [sid | nxt | head: N ints each | Es N x D | lse2 M | gpos M | row-tile sums n_rt x 4 | de parts min(64 N, 65536)
-// x D] (the parts section is sized by N alone, so the total never decreases as M or N grows).  0: an unsupported shape.
+// x D | the samples' biases N (popularity proposal)] (the parts section is sized by N alone, so the total never decreases as M or N
+// grows).  0: an unsupported shape.
 size_t sce_workspace(int M, int N, int D, CeGeom& g) {
     if (N > CR_SCE_MAX_SAMPLES || !ce_geometry(M, 0, N, D, SCE_MAX_PARTS, SCE_PART_ROWS, g)) return 0;
     return 3 * cr_align256(4 * (size_t)N) + cr_align256(4 * (size_t)N * D) + 2 * cr_align256(4 * (size_t)M) +
-           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D);
+           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D) + cr_align256(4 * (size_t)N);
 }
 
 // gBCE workspace: the sampled one without lse2
@@ -811,7 +893,8 @@ template <class A, int NK, bool SPLIT>
 void ce_launch(const A& a, const CeGeom& g, hipStream_t st) {
     constexpr bool S = A::SAMPLED;
     if constexpr (S) {
-        hipLaunchKernelGGL(k_sce_ids<CR_SCE_SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
+        if constexpr (A::POP) hipLaunchKernelGGL(k_sce_ids_pop, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_sce_ids<CR_SCE_SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
         if (a.tg) hipLaunchKernelGGL(k_sce_dedup, dim3((a.N + 255) / 256), dim3(256), 0, st, a);
     }
     hipLaunchKernelGGL((k_ce_lse<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
@@ -905,6 +988,8 @@ extern "C" int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream) {
     CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
                "cr_sampled_ce: unknown precision %d", d->precision);
     CR_REQUIRE(d->samples || d->step, "cr_sampled_ce: NULL step with NULL samples (the device draw reads the step word)");
+    CR_REQUIRE(!d->cdf || d->logq, "cr_sampled_ce: cdf without logq (a proposal is both: the draw and its log-Q correction)");
+    CR_REQUIRE(d->samples || !d->logq || d->cdf, "cr_sampled_ce: logq with NULL samples needs the cdf (the device draw searches it)");
     CeGeom g;
     const size_t need = sce_workspace(d->M, d->N, d->D, g);
     CR_REQUIRE(need, "cr_sampled_ce: unsupported shape");
@@ -923,11 +1008,19 @@ extern "C" int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream) {
     a.lse2 = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
     a.gpos = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
     a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
-    a.part = reinterpret_cast<float*>(w);
+    a.part = reinterpret_cast<float*>(w); w += cr_align256(4 * sce_part_rows(d->N) * d->D);
     a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
     a.rpp = g.rpp; a.parts = g.parts;
     a.lse_out = d->lse_out; a.state = d->state; a.n_rt = g.n_rt;
-    ce_run(a, g, d->precision, cr_stream(stream));
+    if (d->logq) {                                                  // popularity proposal: the corrected candidates
+        ScePopArgs p;
+        static_cast<SceArgs&>(p) = a;
+        p.cdf = d->cdf; p.logq = d->logq;
+        p.sb = reinterpret_cast<float*>(w);
+        ce_run(p, g, d->precision, cr_stream(stream));
+    } else {
+        ce_run(a, g, d->precision, cr_stream(stream));
+    }
     return cr_check_launch("cr_sampled_ce");
 }
 

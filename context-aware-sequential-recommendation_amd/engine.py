@@ -38,6 +38,10 @@ LOSSES = ("bce", "ce")
 ALL_LOSSES = LOSSES + ("sampled_ce", "gbce")
 SOFTMAX_LOSSES = ("ce", "sampled_ce", "gbce")     # the losses that take the route of "ce" (one launch in op_head, d(seq_emb) stored)
 SAMPLED_LOSSES = ("sampled_ce", "gbce")
+# the proposal "sampled_ce" draws its shared negatives from: "uniform", or "popularity" -- item weights handed over with
+# Engine.set_item_weights, the draw by a search of their cumulative masses and the log-Q correction on every candidate's logit
+# (castrec.h cr_sampled_ce)
+CE_PROPOSALS = ("uniform", "popularity")
 
 MODELS = ["cast_1", "cast_2", "cast_3", "cast_4", "cast_5", "cast_6", "cast_7", "cast_8", "cast_9",
           "sasrec", "sasrec_static"]          # main.py:28
@@ -61,7 +65,8 @@ class Hyper:
 
     def __init__(self, args=None, **kw):
         d = dict(maxlen=50, hidden_units=50, num_blocks=2, num_heads=1, dropout_rate=0.5, l2_emb=0.0, lr=1e-3,
-                 max_bins=200, num_context_blocks=2, seed=42, loss="bce", ce_negatives=256, gbce_t=0.75)
+                 max_bins=200, num_context_blocks=2, seed=42, loss="bce", ce_negatives=256, gbce_t=0.75, ce_proposal="uniform",
+                 ce_pop_power=1.0)
         for k in d:
             if args is not None and hasattr(args, k):
                 d[k] = getattr(args, k)
@@ -190,7 +195,7 @@ class ParamLayout:
 class Engine:
     def __init__(self, model, usernum, itemnum, hp, batch_size, training=True, seed=None, n_slabs=None,
                  share=None, batch_global=None, row_offset=0, want_attn=False, device="cuda", fused=None,
-                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None, gbce_t=None):
+                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None, gbce_t=None, ce_proposal=None):
         """loss: the training objective, "bce" (the default: hp.loss, else "bce") or "ce" -- full-catalogue softmax cross-entropy
         (cr_softmax_ce).  Under "ce" the prediction head is one cr_softmax_ce launch that stores d(seq_emb) and accumulates the item
         table's gradient into Gt; the occurrence index and the head fusions are off, so the embedding backward scatters with float
@@ -202,7 +207,12 @@ class Engine:
         "gbce" takes the route of "sampled_ce" with one cr_gbce launch: binary cross-entropy over the target and ce_negatives shared
         uniform negatives, the positive term weighted by eng.gbce_beta = 1 - t (1 - alpha), alpha = min(1, ce_negatives / max(1,
         itemnum - 1)) the sampling rate over the items that are not the target and t = gbce_t (default hp.gbce_t, else 0.75; the
-        calibration parameter of gSASRec: 0 is plain BCE, 1 is fully calibrated).  It also refuses gbce_t outside [0, 1]."""
+        calibration parameter of gSASRec: 0 is plain BCE, 1 is fully calibrated).  It also refuses gbce_t outside [0, 1].
+        ce_proposal: "uniform" (the default: hp.ce_proposal, else "uniform") or "popularity", for "sampled_ce" only (gBCE's beta is
+        derived for uniform sampling).  Under "popularity" the samples are drawn from the item weights of set_item_weights() -- a step
+        before the first call raises RuntimeError -- and every candidate's logit, the target's included, is corrected by -log Q; the
+        device arrays item_cdf / item_logq [itemnum + 1] are allocated here and rewritten in place, so a captured graph follows a new
+        set of weights.  Still one cr_sampled_ce launch: the launch list is "sampled_ce"'s.  Eval engines ignore the option."""
         if model not in MODELS:
             raise ValueError("model must be one of %s" % MODELS)
         if not torch.cuda.is_available():
@@ -234,6 +244,14 @@ class Engine:
             gbce_t = getattr(hp, "gbce_t", None)
             gbce_t = 0.75 if gbce_t is None else gbce_t
         self.gbce_t = float(gbce_t)
+        if ce_proposal is None:
+            ce_proposal = getattr(hp, "ce_proposal", None) or "uniform"
+        if ce_proposal not in CE_PROPOSALS:
+            raise ValueError("ce_proposal must be one of %s, got %r" % (CE_PROPOSALS, ce_proposal))
+        self.ce_proposal = ce_proposal if training else "uniform"
+        if self.ce_proposal == "popularity" and self.loss != "sampled_ce":
+            raise ValueError("ce_proposal='popularity' needs loss='sampled_ce', got loss=%r (gbce's beta is derived for uniform "
+                             "sampling; bce and ce draw no shared negatives)" % self.loss)
         if self.loss in SOFTMAX_LOSSES:
             op = {"ce": "cr_softmax_ce", "sampled_ce": "cr_sampled_ce", "gbce": "cr_gbce"}[self.loss]
             if self.lazy_adam:
@@ -324,6 +342,11 @@ class Engine:
                 self._ce_ws = torch.empty(nb, dtype=torch.uint8, device=self.dev)
             if self.loss in SAMPLED_LOSSES:
                 self.samples = torch.zeros(self.ce_negatives, dtype=torch.int32, device=self.dev)    # the last step's sample ids
+            if self.ce_proposal == "popularity":
+                # the proposal's two arrays (castrec.h): written in place by set_item_weights, read by every later step
+                self.item_cdf = torch.zeros(itemnum + 1, dtype=torch.int32, device=self.dev)         # (the bits of the uint32 masses)
+                self.item_logq = torch.zeros(itemnum + 1, **f32)
+                self._have_item_weights = False
         self.drop = O.Drop(hp.dropout_rate if training else 0.0, self.seed, self.state, row_offset)
         self.batch_global = self.B if batch_global is None else batch_global
         self.want_attn = want_attn
@@ -1052,9 +1075,10 @@ class Engine:
                                *tail)
             else:
                 op = "cr_sampled_ce"
+                pop = self.ce_proposal == "popularity"
                 d = L.SampledCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, self.ce_negatives, prec, None,
                                     self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
-                                    *tail)
+                                    *tail, self.item_cdf.data_ptr() if pop else None, self.item_logq.data_ptr() if pop else None)
             self._call(self.fwd, op, C.byref(d))
             return
         rec = self._ln_recipe.get(seq_emb.data_ptr()) if self.fuse_head_ln else None
@@ -1331,6 +1355,22 @@ class Engine:
             # step number (counter moved back, checkpoint loaded) would read as "already claimed" and skip the row
             self.lazy_flags.zero_()
 
+    def set_item_weights(self, w):
+        """ce_proposal="popularity": the proposal of the coming steps from non-negative item weights w [itemnum + 1] (w[0] ignored;
+        castrec_amd.proposal.build_proposal states the construction and what it refuses).  The arrays are copied into the buffers the
+        launches read (item_cdf, item_logq), behind the steps already queued on the current stream: a captured graph stays valid."""
+        if getattr(self, "ce_proposal", "uniform") != "popularity":
+            raise RuntimeError("set_item_weights(): this engine was not built with ce_proposal='popularity'")
+        from .proposal import build_proposal
+        cdf, logq = build_proposal(w, self.itemnum + 1)
+        self.item_cdf.copy_(torch.from_numpy(cdf.view(np.int32)))
+        self.item_logq.copy_(torch.from_numpy(logq))
+        self._have_item_weights = True
+
+    def _need_item_weights(self):
+        if self.ce_proposal == "popularity" and not self._have_item_weights:
+            raise RuntimeError("ce_proposal='popularity': call set_item_weights() before the first training step")
+
     def step_number(self):
         """Number of the step the next launch will run (1 + completed optimiser steps)."""
         return int(self.state[4:5].view(torch.int32)[0])
@@ -1341,11 +1381,13 @@ class Engine:
             if rc != 0:
                 raise RuntimeError("castrec %s failed (%d): %s" % (name, rc, L.lib.cr_last_error().decode()))
 
-    def launch_step(self, apply=True, between=None):
+    def launch_step(self, apply=True, between=None, capturing=False):
         """forward -> backward -> [between()] -> Adam, on the current stream.  state[4] holds the number of the step
         being run; Adam ends the step (zeroes the loss sums, advances the counter).  Without Adam (apply=False) the
-        state is left as the kernels wrote it: call set_step() before running again."""
+        state is left as the kernels wrote it: call set_step() before running again.  (capturing: recorded into a graph, not run.)"""
         s = torch.cuda.current_stream().cuda_stream
+        if self.training and not capturing:
+            self._need_item_weights()
         self._run(self.fwd, s)
         if self.training:
             self._run(self.bwd, s)
@@ -1469,6 +1511,7 @@ class Engine:
         wait (and max_steps allows it), those G steps in one launch.  Returns the number of steps run."""
         if self._feed_have < 1:
             raise RuntimeError("train_fed(): no batch has been fed")
+        self._need_item_weights()
         n = self._feed_ring.shape[0]
         k = self._feed_next - self._feed_have
         G = self.graph_steps if (getattr(self, "graph_multi", None) is not None and self.graph is not None) else 1
@@ -1555,7 +1598,7 @@ class Engine:
             if dp:
                 self.launch_backward_to_flat()
             else:
-                self.launch_step()
+                self.launch_step(capturing=True)
             g.end()
         self.graph_multi, self.graph_steps = None, 1
         if n_steps > 1:
@@ -1564,7 +1607,7 @@ class Engine:
             with torch.cuda.stream(side):
                 gm.begin()
                 for _ in range(n_steps):
-                    self.launch_step()
+                    self.launch_step(capturing=True)
                 gm.end()
             self.graph_multi, self.graph_steps = gm, int(n_steps)
         torch.cuda.current_stream().wait_stream(side)
@@ -1574,6 +1617,7 @@ class Engine:
     def train_step(self, seq, pos, neg, time=None, hours=None, days=None):
         self.set_batch(seq, pos, neg, time, hours, days)
         if self.graph is not None:
+            self._need_item_weights()
             self.graph.launch()
         else:
             self.launch_step()

@@ -162,7 +162,7 @@ class SampledCeDesc(C.Structure):
     _fields_ = [("seq_emb", c_p), ("ld", c_i), ("table", c_p), ("pos", c_p), ("neg", c_p), ("M", c_i), ("D", c_i), ("V", c_i),
                 ("N", c_i), ("precision", c_i), ("samples", c_p), ("seed", C.c_uint32), ("step", c_p), ("samples_out", c_p),
                 ("state", c_p), ("d_seq_emb", c_p), ("ldd", c_i), ("table_grad", c_p), ("lse_out", c_p), ("workspace", c_p),
-                ("workspace_bytes", C.c_size_t)]
+                ("workspace_bytes", C.c_size_t), ("cdf", c_p), ("logq", c_p)]
 
 
 class GbceDesc(C.Structure):

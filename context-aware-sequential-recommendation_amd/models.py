@@ -26,6 +26,7 @@ class _Model(object):
         self._n_slabs, self._batch_global, self._row_offset = n_slabs, batch_global, row_offset
         self._train = None
         self._pending_opt = None              # optimiser state loaded before the training engine exists (load / load_tf_checkpoint)
+        self._item_weights = None             # ce_proposal="popularity": the weights of set_item_counts, until the training engine exists
         self._eval = {}
         self._fed = []                        # data parallel: batches handed over by feed() wait here
         self._graph = bool(int(os.environ.get("CASTREC_GRAPH", "1")))
@@ -88,6 +89,8 @@ class _Model(object):
             if self._pending_opt is not None:          # a checkpoint's Adam slots and step count (saver.restore, main.py:165-175)
                 self._apply_opt(*self._pending_opt)
                 self._pending_opt = None
+            if self._item_weights is not None:
+                self._train.set_item_weights(self._item_weights)
         if getattr(self, "_dp", None) is not None:
             if self._dp_rows[2] != B:
                 raise ValueError("global batch size changed from %d to %d (static graph)" % (self._dp_rows[2], B))
@@ -95,6 +98,23 @@ class _Model(object):
         if self._train.B != B:
             raise ValueError("batch size changed from %d to %d (static graph)" % (self._train.B, B))
         return self._train
+
+    def set_item_counts(self, counts, power=None):
+        """--ce_proposal popularity: the sampled softmax draws its negatives with probability proportional to (counts_v + 1)^power
+        (counts [itemnum + 1], e.g. each item's occurrences in the training split; power defaults to hp.ce_pop_power; the + 1 gives
+        every item mass) and corrects every logit by -log Q (Engine.set_item_weights).  May be called again while training."""
+        if getattr(self.hp, "ce_proposal", "uniform") != "popularity":
+            raise RuntimeError("set_item_counts(): the model was not built with ce_proposal='popularity'")
+        counts = np.asarray(counts, np.float64)
+        if counts.shape != (self.itemnum + 1,):
+            raise ValueError("counts must have itemnum + 1 = %d entries, got shape %s" % (self.itemnum + 1, counts.shape))
+        power = float(getattr(self.hp, "ce_pop_power", 1.0) if power is None else power)
+        from .proposal import build_proposal
+        w = (counts + 1.0) ** power
+        build_proposal(w, self.itemnum + 1)              # (refuses bad counts now, not at the first step)
+        self._item_weights = w
+        if self._train is not None:
+            self._train.set_item_weights(w)
 
     def train_step(self, u, seq, pos, neg, time_seq=None, hours=None, days=None, fetch=True):
         """One optimisation step (main.py:212-219).  Returns (auc, loss) of the batch like the reference's fetch."""

@@ -178,17 +178,20 @@ def sampled_ce_workspace_bytes(M, N, D):
 
 
 def sampled_ce(seq_emb, ld, table, pos, state, workspace, M, N, precision=L.PREC_BF16X3, neg=None, samples=None, seed=0, step=None,
-               samples_out=None, d_seq_emb=None, ldd=0, table_grad=None, lse_out=None):
+               samples_out=None, d_seq_emb=None, ldd=0, table_grad=None, lse_out=None, cdf=None, logq=None):
     """cr_sampled_ce: the softmax over each row's target and N shared sample ids.  Rows seq_emb + m * ld (m < M) of a float32 CUDA
     tensor's storage against table [V, D]; pos / neg int32 [M]; samples an int32 [N] tensor of ids in [1, V), or None: drawn on the
     device from seed and step (a CUDA tensor whose first 4 bytes are the uint32 step word, e.g. state[4:5]); samples_out int32 [N]
     written where given; state, d_seq_emb, table_grad, lse_out as softmax_ce; workspace a uint8 CUDA tensor of at least
-    sampled_ce_workspace_bytes(M, N, D) bytes."""
+    sampled_ce_workspace_bytes(M, N, D) bytes.  cdf (int32 or uint32 [V], the bits of the uint32 cumulative masses) and logq (float32
+    [V]): a popularity proposal and its log-Q correction (castrec_amd.util.build_proposal); both None: the uniform proposal."""
+    if cdf is not None and (cdf.dtype not in (torch.int32, getattr(torch, "uint32", torch.int32)) or not cdf.is_cuda):
+        raise TypeError("cdf must be an int32 / uint32 CUDA tensor")
     d = L.SampledCeDesc(_p(_f32(seq_emb, "seq_emb")), ld, _p(_f32(table, "table")), _p(_i32(pos, "pos")), _p(_i32(neg, "neg")),
                         M, table.shape[1], table.shape[0], N, precision, _p(_i32(samples, "samples")), int(seed) & 0xFFFFFFFF,
                         _p(step), _p(_i32(samples_out, "samples_out")), _p(_f32(state, "state")), _p(_f32(d_seq_emb, "d_seq_emb")),
                         ldd, _p(_f32(table_grad, "table_grad")), _p(_f32(lse_out, "lse_out")), _p(workspace),
-                        workspace.numel() * workspace.element_size())
+                        workspace.numel() * workspace.element_size(), _p(cdf), _p(_f32(logq, "logq")))
     L.call("cr_sampled_ce", C.byref(d), _stream())
 
 

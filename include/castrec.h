@@ -504,12 +504,13 @@ struct cr_softmax_ce_desc {
 size_t cr_softmax_ce_workspace(int M, int V, int D);        /* 0 for a shape outside the supported range */
 int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream);
 
-/* ---- sampled softmax cross-entropy with shared uniform negatives (csrc/cr_ce.hip) ---------------------------------
+/* ---- sampled softmax cross-entropy with shared negatives (csrc/cr_ce.hip) -----------------------------------------
  * The softmax objective of cr_softmax_ce over the target plus N items drawn for the whole call, at a cost that does not depend on V.
  * Rows m = 0 .. M-1, h_m = seq_emb row m, E = table [V, D] (row 0 padding), istarget_m = (pos[m] != 0), sample ids s_0 .. s_{N-1}
  * in [1, V) shared by every row.  Candidates of row m: the target pos_m and every sample j with s_j != pos_m (a sample equal to the
  * row's target is an "accidental hit", dropped from that row only); samples are drawn with replacement and a duplicate counts as
- * its own candidate.  The proposal is uniform, so a log-Q correction would shift every logit by one constant: none is applied.
+ * its own candidate.  With cdf and logq NULL the proposal is uniform, so a log-Q correction would shift every logit by one constant:
+ * none is applied (a popularity proposal and its correction: below).
  *   z_mv = h_m . E_v;  l_m = log(exp z_{m,pos} + sum_{j: s_j != pos_m} exp z_{m,s_j}) - z_{m,pos};  p = softmax over the candidates.
  *   state: [0] += sum_m istarget_m l_m, [1] += the AUC term of the per-position neg ids exactly as cr_softmax_ce's (neg 0 reads as a
  *   zero score; neg == NULL adds 0), [2] += sum_m istarget_m; then the snapshot [8..11] (ticket [12] left at 0): cr_adam_step runs
@@ -522,11 +523,26 @@ int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream);
  * Samples: `samples` (device [N], ids in [1, V), not checked on the device), or, when it is NULL, drawn on the device from `seed` and
  * the device step word `step` (state + 4, as cr_rng reads it), so captured graphs draw new samples every step without host work:
  *   key = cr_site_key(seed, *step, CR_SCE_SITE);  x_j = cr_fmix32(key + j * CR_PHI);  s_j = 1 + (uint32)(((uint64)x_j * (V - 1)) >> 32).
+ * Popularity proposal (optional; cdf and logq both NULL: everything above, bit for bit).  A proposal Q over the items 1 .. V-1 is two
+ * device arrays built on the host from non-negative weights w[V] (w[0] ignored; float64, W_v = sum_{1 <= u <= v} w_u in index order):
+ *   cdf  uint32 [V]: cdf[0] = 0, cdf[v] = min(floor(2^32 W_v / W_{V-1}), 2^32 - 1), non-decreasing; cdf[V-1] is READ AS 2^32;
+ *   logq float  [V]: logq[0] = 0, logq[v] = (float) log Q(v) with Q(v) = mass_v / 2^32, mass_v = cdf[v] - cdf[v-1] >= 1 (the
+ *        quantised masses, so the correction is that of the draw exactly; every item can be a target, so every item has mass).
+ *   Draw (samples == NULL and cdf != NULL): x_j as above -- the same key, the same site -- and s_j = the smallest s in [1, V-1] with
+ *   x_j < cdf[s], i.e. s_j = 1 + #{v in [1, V-2] : cdf[v] <= x_j}: a binary search, done once per sample.
+ *   Objective (logq != NULL): z'_mv = z_mv - logq[v] for every candidate, the target included, replaces z_mv in l_m, p, d_seq_emb and
+ *   table_grad above; lse_out is the log of the corrected candidate sum.  Samples are drawn with replacement and a duplicate is its own
+ *   candidate, so the expected count N Q(v) of an item among the candidates differs from Q(v) by a constant of the row: log Q is the
+ *   whole correction (Bengio & Senecal 2008; Jean et al. 2015).  Accidental hits are masked as before; the AUC term stays on the raw
+ *   scores; padded rows read logq[0] = 0; a row whose every sample is a hit still has loss 0 and zero gradients exactly.
+ *   cdf without logq is refused; logq without cdf is refused for a device draw and allowed with caller-supplied samples (cdf is
+ *   then not read).
  * Reproducibility: the target term of table_grad is added with float atomics (as cr_head_fwd_bwd's table_grad); every other output
  * (state, lse_out, d_seq_emb, samples_out, table_grad rows that are no row's target) has the same bits on two calls.
  *   - precision: CR_PREC_BF16X3 or CR_PREC_BF16; CR_PREC_F32 takes the bf16x3 path (as cr_softmax_ce).
  *   - shapes: 8 <= D <= 256, V >= 2, M >= 1, 1 <= N <= CR_SCE_MAX_SAMPLES, ld >= D, ldd >= D.
- *   - workspace: at least cr_sampled_ce_workspace(M, N, D) bytes of device memory, O(M + N D); it never decreases as M or N grows. */
+ *   - workspace: at least cr_sampled_ce_workspace(M, N, D) bytes of device memory, O(M + N D); it never decreases as M or N grows
+ *     (the same size with and without a proposal). */
 #define CR_SCE_MAX_SAMPLES 16384
 #define CR_SCE_SITE 0x5CE00000u      /* the draw's cr_site_key site (outside the 24-bit dropout site ids) */
 typedef struct cr_sampled_ce_desc cr_sampled_ce_desc;
@@ -547,6 +563,8 @@ struct cr_sampled_ce_desc {
     float* lse_out;                   /* optional [M] */
     void* workspace;
     size_t workspace_bytes;
+    const uint32_t* cdf;              /* optional device [V]: the proposal's cumulative masses (device draw); NULL: uniform */
+    const float* logq;                /* optional device [V]: log Q(v), the correction; required with cdf */
 };
 size_t cr_sampled_ce_workspace(int M, int N, int D);       /* 0 for a shape outside the supported range */
 int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream);

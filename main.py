@@ -65,6 +65,11 @@ def parse_args(argv=None):
     parser.add_argument('--gbce_t', type=float, default=0.75,
                         help='gbce: calibration parameter t in [0, 1] (0 = plain BCE over the negatives, 1 = fully calibrated); the '
                              'positive term\'s weight is beta = 1 - t (1 - sampling rate)')
+    parser.add_argument('--ce_proposal', default='uniform', choices=['uniform', 'popularity'],
+                        help='sampled_ce: the proposal the shared negatives are drawn from; popularity = proportional to (an item\'s '
+                             'occurrences in the training split + 1)^ce_pop_power, with the log-Q correction on every logit')
+    parser.add_argument('--ce_pop_power', type=float, default=1.0,
+                        help='popularity proposal: the exponent on the item counts (1 = unigram, 0.75 = word2vec\'s, 0 = uniform)')
     return parser.parse_args(argv)
 
 
@@ -105,6 +110,15 @@ def main(argv=None):
     model = build_model(args.model, usernum, itemnum, ratingnum, args)
     if world > 1:
         model.data_parallel(rank, world)
+    if args.ce_proposal == 'popularity':
+        from castrec_amd.proposal import build_proposal, effective_items
+        counts = np.zeros(itemnum + 1, np.int64)
+        for events in train.values():
+            np.add.at(counts, np.asarray([e[0] if isinstance(e, (tuple, list)) else e.item for e in events], np.int64), 1)
+        model.set_item_counts(counts)
+        cdf, _ = build_proposal((counts + 1.0) ** args.ce_pop_power)
+        logger.info('popularity proposal: power %g, effective number of items %.1f of %d' % (
+            args.ce_pop_power, effective_items(cdf), itemnum))
     sampler = WarpSampler(args, train_corpus(train, usernum, itemnum), usernum, itemnum,
                           batch_size=args.batch_size, maxlen=args.maxlen, n_workers=1)
     model_path = os.path.abspath('saved_models')

@@ -102,11 +102,14 @@ def run(key, reps, with_torch):
     return res
 
 
-def train_step_ms(loss, reps):
-    """CAST1 at the headline shape (bench.py HEADLINE: B 128, maxlen 200, D 50, 2 blocks), one captured step per launch."""
+def train_step_ms(loss, reps, prepare=None, **engine_kw):
+    """CAST1 at the headline shape (bench.py HEADLINE: B 128, maxlen 200, D 50, 2 blocks), one captured step per launch.
+    engine_kw: further Engine options; prepare(eng): what the engine needs before its first step."""
     B, T, itemnum = 128, 200, 3416
     hp = E.Hyper(maxlen=T, hidden_units=50, num_blocks=2, num_heads=1, dropout_rate=0.2, max_bins=200, lr=1e-3, seed=42)
-    eng = E.Engine("cast_1", 6040, itemnum, hp, B, training=True, loss=loss)
+    eng = E.Engine("cast_1", 6040, itemnum, hp, B, training=True, loss=loss, **engine_kw)
+    if prepare is not None:
+        prepare(eng)
     rs = np.random.RandomState(0)
     seq = rs.randint(1, itemnum + 1, (B, T)); seq[:, :20] = 0
     pos = rs.randint(1, itemnum + 1, (B, T)) * (seq != 0); neg = rs.randint(1, itemnum + 1, (B, T)) * (seq != 0)
@@ -121,7 +124,7 @@ def train_step_ms(loss, reps):
             eng.graph.launch()
     t, _ = _time(steps, reps)
     r = dict(model="cast_1", B=B, T=T, D=50, loss=loss, ms_per_step=1e3 * t / n, launches=eng.n_kernel_launches(),
-             loss_after=eng.loss_auc()[0])
+             loss_after=eng.loss_auc()[0], **engine_kw)
     print(json.dumps(r), flush=True)
     return r
 

@@ -6,7 +6,7 @@ shape with loss "bce", "ce", "sampled_ce" and "gbce" (N = 256).
 
     python tools/gbce_bench.py [--shapes a,b,c] [--reps 7] [--out DIR/gbce_bench.json] [--no-torch] [--no-step]
 
---dump DIR writes what cr_softmax_ce and cr_sampled_ce compute at one fixed case per precision (state, lse_out, d_seq_emb, samples
+--dump DIR writes what cr_softmax_ce, cr_sampled_ce (uniform proposal) and cr_gbce compute at one fixed case per precision (state, lse_out, d_seq_emb, samples
 and the table_grad rows that are no row's target: the outputs that have the same bits on every call) as .npy files, and exits;
 --lib PATH runs that through another build of libcastrec.so (loaded beside this one: lib.py binds every symbol of this header on
 import, so an older build cannot stand in through CASTREC_LIB); --compare DIR_A DIR_B says whether two dumps hold the same bits.
@@ -114,11 +114,14 @@ def run(key, reps, with_torch, beta=0.5):
 
 # ---- the existing losses, bit for bit ------------------------------------------------------------------------------------------
 def dump(out_dir, lib_path):
-    """cr_softmax_ce and cr_sampled_ce at one fixed case per precision through `lib_path` (None: this build)."""
+    """cr_softmax_ce, cr_sampled_ce and cr_gbce at one fixed case per precision through `lib_path` (None: this build; a build from
+    before cr_gbce: without it)."""
     lib = L.lib
     if lib_path:
         lib = C.CDLL(os.path.abspath(lib_path))
-        for n, desc in (("cr_softmax_ce", L.SoftmaxCeDesc), ("cr_sampled_ce", L.SampledCeDesc)):
+        for n, desc in (("cr_softmax_ce", L.SoftmaxCeDesc), ("cr_sampled_ce", L.SampledCeDesc), ("cr_gbce", L.GbceDesc)):
+            if not hasattr(lib, n):
+                continue
             getattr(lib, n).restype, getattr(lib, n).argtypes = C.c_int, [C.POINTER(desc), C.c_void_p]
             getattr(lib, n + "_workspace").restype, getattr(lib, n + "_workspace").argtypes = C.c_size_t, [C.c_int] * 3
         lib.cr_last_error.restype = C.c_char_p
@@ -135,7 +138,7 @@ def dump(out_dir, lib_path):
     keep = np.ones(V, bool)
     keep[pos_h] = False                                   # the sampled op's target rows take float atomics
     for prec, pname in ((L.PREC_BF16X3, "bf16x3"), (L.PREC_BF16, "bf16")):
-        for op in ("cr_softmax_ce", "cr_sampled_ce"):
+        for op in [o for o in ("cr_softmax_ce", "cr_sampled_ce", "cr_gbce") if hasattr(lib, o)]:
             st = torch.zeros(L.CR_STATE_FLOATS, device="cuda")
             st[4:5].view(torch.int32)[0] = 3
             dh = torch.zeros(M, D, device="cuda")
@@ -146,6 +149,10 @@ def dump(out_dir, lib_path):
             if op == "cr_softmax_ce":
                 ws = torch.empty(lib.cr_softmax_ce_workspace(M, V, D), dtype=torch.uint8, device="cuda")
                 d = L.SoftmaxCeDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, prec, p(st), p(dh), D, p(tg), p(lse), p(ws), ws.numel())
+            elif op == "cr_gbce":
+                ws = torch.empty(lib.cr_gbce_workspace(M, N, D), dtype=torch.uint8, device="cuda")
+                d = L.GbceDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, N, prec, 0.4, None, 42, p(st) + 16, p(so), p(st), p(dh), D,
+                               p(tg), p(lse), p(ws), ws.numel())
             else:
                 ws = torch.empty(lib.cr_sampled_ce_workspace(M, N, D), dtype=torch.uint8, device="cuda")
                 d = L.SampledCeDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, N, prec, None, 42, p(st) + 16, p(so), p(st), p(dh), D,
@@ -154,7 +161,7 @@ def dump(out_dir, lib_path):
             if rc != 0:
                 raise RuntimeError("%s failed: %s" % (op, lib.cr_last_error().decode()))
             torch.cuda.synchronize()
-            outs = dict(state=st, lse_out=lse, d_seq_emb=dh, table_grad=tg.cpu()[torch.from_numpy(keep)] if op == "cr_sampled_ce" else tg,
+            outs = dict(state=st, lse_out=lse, d_seq_emb=dh, table_grad=tg.cpu()[torch.from_numpy(keep)] if op != "cr_softmax_ce" else tg,
                         samples=so)
             for k, v in outs.items():
                 np.save(os.path.join(out_dir, "%s_%s_%s.npy" % (op, pname, k)), v.cpu().numpy())

@@ -4,12 +4,17 @@ composition of the same loss (gather -> matmul -> mask -> logsumexp -> the two g
 headline shape with loss "bce", "ce" and "sampled_ce" (N = 256).
 
     python tools/sce_bench.py [--shapes a,b,c] [--reps 7] [--out DIR/sce_bench.json] [--no-torch] [--no-ce] [--no-step]
+
+--proposal popularity draws the negatives from Zipf item weights (seeded) and applies the log-Q correction.
+--ab times that proposal (B) against the uniform one (A) in this process, interleaved A B A B, and reports the ratio of the medians;
+with --proposal uniform both sides are the uniform path: the A/A spread such a ratio has to be read against.
 """
 import argparse
 import json
 import os
 import sys
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,13 +52,40 @@ def torch_sce(h, table, pos, s):
     return ((lse - st) * ist).sum(), dh, dE
 
 
+def zipf_proposal(V, seed=0):
+    """Device (cdf, logq) of the weights floor(10^6 / rank^1.1) + 1 dealt to the ids by RandomState(seed)."""
+    from castrec_amd.proposal import build_proposal
+    w = np.floor(1e6 / np.arange(1, V + 1, dtype=np.float64) ** 1.1) + 1.0
+    np.random.RandomState(seed).shuffle(w)
+    cdf, logq = build_proposal(w, V)
+    return torch.from_numpy(cdf.view(np.int32)).cuda(), torch.from_numpy(logq).cuda()
+
+
+def _time_ab(fa, fb, reps, warm=2):
+    """Medians and sorted times of fa and fb timed in turn (A B A B ...), HIP events."""
+    for _ in range(warm):
+        fa(); fb()
+    torch.cuda.synchronize()
+    out = ([], [])
+    for _ in range(reps):
+        for k, fn in enumerate((fa, fb)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record()
+            torch.cuda.synchronize()
+            out[k].append(a.elapsed_time(b) * 1e-3)
+    for o in out:
+        o.sort()
+    return out[0][reps // 2], out[0], out[1][reps // 2], out[1]
+
+
 def _dpad(D):
     d = (D + 31) // 32 * 32
     return 32 if d <= 32 else 64 if d <= 64 else 128 if d <= 128 else 256
 
 
-def run(key, reps, with_torch, with_ce):
+def run(key, reps, with_torch, with_ce, proposal="uniform", ab=False):
     name, M, V, D, Ns = SHAPES[key]
+    cdf, logq = zipf_proposal(V) if proposal == "popularity" else (None, None)
     g = torch.Generator(device="cuda").manual_seed(0)
     table = torch.randn(V, D, device="cuda", generator=g) * 0.5
     h = torch.randn(M, D, device="cuda", generator=g) * (1.0 / D ** 0.5)
@@ -76,11 +108,18 @@ def run(key, reps, with_torch, with_ce):
         so = torch.empty(N, dtype=torch.int32, device="cuda")
         for prec, pname, nprod in ((L.PREC_BF16X3, "bf16x3", 3), (L.PREC_BF16, "bf16", 1)):
             fn = lambda: O.sampled_ce(h, D, table, pos, st, ws, M, N, precision=prec, neg=neg, seed=42, step=st[4:5], samples_out=so,
-                                      d_seq_emb=dh, ldd=D, table_grad=tg)
-            t, all_t = _time(fn, reps)
+                                      d_seq_emb=dh, ldd=D, table_grad=tg, cdf=cdf, logq=logq)
+            if ab:
+                fu = lambda: O.sampled_ce(h, D, table, pos, st, ws, M, N, precision=prec, neg=neg, seed=42, step=st[4:5],
+                                          samples_out=so, d_seq_emb=dh, ldd=D, table_grad=tg)
+                tu, all_u, t, all_t = _time_ab(fu, fn, reps)
+            else:
+                t, all_t = _time(fn, reps)
             flop = 3 * nprod * 2.0 * M * N * dpad                     # three passes, each a [M, N] x D product (padded k)
             r = dict(shape=key, name=name, M=M, V=V, D=D, N=N, D_padded=dpad, precision=pname, time_s=t, times_s=all_t, mfma_flop=flop,
-                     mfma_roof_s=flop / BF16_PEAK, mfma_fraction=flop / BF16_PEAK / t, workspace_bytes=ws.numel())
+                     mfma_roof_s=flop / BF16_PEAK, mfma_fraction=flop / BF16_PEAK / t, workspace_bytes=ws.numel(), proposal=proposal)
+            if ab:
+                r.update(uniform_time_s=tu, uniform_times_s=all_u, ratio_to_uniform=t / tu)
             if ce_t is not None:
                 r.update(softmax_ce_bf16x3_s=ce_t, speedup_vs_softmax_ce=ce_t / t)
             res.append(r)
@@ -91,7 +130,7 @@ def run(key, reps, with_torch, with_ce):
                 loss_t, dh_t, dE_t = torch_sce(h, table, pos, s)
                 st[:4].zero_(); tg.zero_()
                 O.sampled_ce(h, D, table, pos, st, ws, M, N, precision=L.PREC_BF16X3, neg=neg, samples=s, d_seq_emb=dh, ldd=D,
-                             table_grad=tg)
+                             table_grad=tg)                             # (the uniform objective: what torch_sce states)
                 torch.cuda.synchronize()
                 agree = dict(loss_rel=float(abs(st[0] - loss_t) / abs(loss_t)),
                              dh_rel=float((dh - dh_t).abs().max() / dh_t.abs().max()),
@@ -117,12 +156,18 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--no-ce", action="store_true")
     ap.add_argument("--no-step", action="store_true")
+    ap.add_argument("--proposal", choices=["uniform", "popularity"], default="uniform")
+    ap.add_argument("--ab", action="store_true", help="time --proposal against the uniform path, interleaved (uniform: the A/A spread)")
     a = ap.parse_args()
     res = []
     for k in a.shapes.split(","):
-        res += run(k, a.reps, not a.no_torch, not a.no_ce)
+        res += run(k, a.reps, not a.no_torch, not a.no_ce, a.proposal, a.ab)
         torch.cuda.empty_cache()
     steps = [] if a.no_step else [train_step_ms(l, a.reps) for l in ("bce", "ce", "sampled_ce")]
+    if not a.no_step and a.proposal == "popularity":
+        w = np.floor(1e6 / np.arange(1, 3418, dtype=np.float64) ** 1.1) + 1.0
+        np.random.RandomState(0).shuffle(w)
+        steps.append(train_step_ms("sampled_ce", a.reps, prepare=lambda eng: eng.set_item_weights(w), ce_proposal="popularity"))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
