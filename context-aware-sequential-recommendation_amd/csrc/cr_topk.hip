@@ -16,6 +16,12 @@
 // Determinism: a chunk's top-K is the exact top-K of its eligible items under the total order (score desc, id asc), whatever the
 // order in which candidates reached the buffer; the chunk partition is fixed by the shape; counts are integers.
 // One MFMA shape in this file (build.py ISA_CHECKED): v_mfma_f32_16x16x32_bf16.
+//
+// Item index (castrec.h cr_topk_index_build, cr_topk_desc.index): the catalogue as the A fragments the sweep forms from the table, made
+// once by k_topk_index_build with the same tk_row_issue / tk_row_finish and stored in fragment order -- a wave's 64 lanes of one
+// (tile of 16 rows, k-step) are 1 KB contiguous, the lo halves a second plane.  The IDX instantiations of both kernels load those
+// fragments (whole tiles in the sweep, one row per lane for the targets and the excluded rows) where the others load, mask and split
+// table rows; everything after the A operand is the same code, so a score has the same bits either way.
 #include <algorithm>
 
 #include "cr_bf16.hpp"
@@ -40,10 +46,47 @@ struct TkArgs {
     int chunk, n_chunks;
 };
 
+// the index forms: the blob in 16-byte groups, the lo plane `plane` groups after the hi plane (unused by a plain index)
+struct TkIdxArgs : TkArgs {
+    const bf8* idx;
+    int64_t plane;
+    int n_tiles;
+};
+template <bool IDX>
+using TkA = std::conditional_t<IDX, TkIdxArgs, TkArgs>;
+
 // a better than b: higher score, equal scores -> smaller id (empty entries carry TK_PAD, the largest id)
 __device__ __forceinline__ bool tk_better(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
 
 // (tk_row_issue / tk_row_finish / tk_tile: cr_bf16.hpp, shared with cr_ce.hip)
+
+// A fragments of the 16 rows of tile `tile` from the index: group ((h n_tiles + tile) NK + ks) 64 + lane.  A tile past the table (the
+// idle waves of a chunk's last round) reads tile 0: its ids are not eligible, its scores are dropped.
+template <int NK, bool SPLIT>
+__device__ __forceinline__ void tk_idx_tile(const TkIdxArgs& a, int tile, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
+    const bf8* p = a.idx + (int64_t)(tile < a.n_tiles ? tile : 0) * (NK * 64) + (threadIdx.x & 63);
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        hi[ks] = p[ks * 64];
+        if (SPLIT) lo[ks] = p[a.plane + ks * 64];
+    }
+}
+// One row per lane (li), as tk_row_issue / tk_row_finish give it: 16-byte gathers; a lane without a row gets zeros.
+template <int NK, bool SPLIT>
+__device__ __forceinline__ void tk_idx_row(const TkIdxArgs& a, int row, bool rok, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
+    const int lg = (threadIdx.x & 63) >> 4, r = rok ? row : 0;
+    const bf8* p = a.idx + (int64_t)(r >> 4) * (NK * 64) + (lg * 16 + (r & 15));
+    const bf8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        const bf8 h = p[ks * 64];
+        hi[ks] = rok ? h : z;
+        if (SPLIT) {
+            const bf8 l = p[a.plane + ks * 64];
+            lo[ks] = rok ? l : z;
+        }
+    }
+}
 
 __device__ __forceinline__ float tk_pick(const f32x4& c, int r) { return r == 0 ? c[0] : r == 1 ? c[1] : r == 2 ? c[2] : c[3]; }
 
@@ -133,8 +176,8 @@ __device__ void tk_fold(const TkLds& l, int qi, int n, int K, const TkArgs& a, i
     tk_wave_sync();
 }
 
-template <int NK, int QB, bool SPLIT>
-__global__ __launch_bounds__(256) void k_topk_sweep(TkArgs a) {
+template <int NK, int QB, bool SPLIT, bool IDX>
+__global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QT = 16 * QB;
     const int K = a.K;
@@ -173,10 +216,14 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkArgs a) {
     if (a.tgt) {
         for (int qb = wave; qb < QB; qb += 4) {
             const int t = l.tq[qb * 16 + li];
-            float v[NK][8];
             bf8 ah[NK], al[NK], bh[NK], bl[NK];
-            tk_row_issue<NK>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D);
-            tk_row_finish<NK, SPLIT>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D, ah, al);
+            if constexpr (IDX) {
+                tk_idx_row<NK, SPLIT>(a, t, t > 0, ah, al);
+            } else {
+                float v[NK][8];
+                tk_row_issue<NK>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D);
+                tk_row_finish<NK, SPLIT>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D, ah, al);
+            }
 #pragma unroll
             for (int ks = 0; ks < NK; ++ks) {
                 bh[ks] = l.img_hi[(qb * NK + ks) * 64 + lane];
@@ -196,21 +243,33 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkArgs a) {
 #pragma unroll
     for (int qb = 0; qb < QB; ++qb) rk[qb] = 0;
     const int n_rounds = (c1 - c0 + 63) / 64;
-    float v[NK][8];
-    {
+    float v[NK][8];                                        // the round ahead: table rows in flight, or (IDX) the fragments themselves
+    bf8 nh[NK], nl[NK];
+    if constexpr (IDX) {
+        tk_idx_tile<NK, SPLIT>(a, (c0 + wave * 16) >> 4, nh, nl);           // chunks start at multiples of 64 rows
+    } else {
         const int row = c0 + wave * 16 + li;
         tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
     }
     for (int round = 0; round < n_rounds; ++round) {
         const int it0 = c0 + round * 64 + wave * 16;
         bf8 ah[NK], al[NK];
-        {
-            const int row = it0 + li;
-            tk_row_finish<NK, SPLIT>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D, ah, al);
-        }
-        if (round + 1 < n_rounds) {
-            const int row = it0 + 64 + li;
-            tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
+        if constexpr (IDX) {
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                ah[ks] = nh[ks];
+                if (SPLIT) al[ks] = nl[ks];
+            }
+            if (round + 1 < n_rounds) tk_idx_tile<NK, SPLIT>(a, (it0 + 64) >> 4, nh, nl);
+        } else {
+            {
+                const int row = it0 + li;
+                tk_row_finish<NK, SPLIT>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D, ah, al);
+            }
+            if (round + 1 < n_rounds) {
+                const int row = it0 + 64 + li;
+                tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
+            }
         }
 #pragma unroll
         for (int qb = 0; qb < QB; ++qb) {
@@ -274,8 +333,8 @@ __device__ __forceinline__ void tk_wave_best(float& s, int& id) {
     }
 }
 
-template <int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_topk_merge(TkArgs a) {
+template <int NK, bool SPLIT, bool IDX>
+__global__ __launch_bounds__(256) void k_topk_merge(TkA<IDX> a) {
     __shared__ float sc[4][16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int b = blockIdx.x * 4 + wave;
@@ -340,10 +399,14 @@ __global__ __launch_bounds__(256) void k_topk_merge(TkArgs a) {
             const int64_t p = p0 + li;
             const int e = p < e1 ? a.excl[p] : 0;
             const bool rok = e >= 1 && e < a.V;
-            float v[NK][8];
             bf8 ah[NK], al[NK];
-            tk_row_issue<NK>(v, a.table, a.D, e, rok, e == a.V - 1, a.D);
-            tk_row_finish<NK, SPLIT>(v, a.table, a.D, e, rok, e == a.V - 1, a.D, ah, al);
+            if constexpr (IDX) {
+                tk_idx_row<NK, SPLIT>(a, e, rok, ah, al);
+            } else {
+                float v[NK][8];
+                tk_row_issue<NK>(v, a.table, a.D, e, rok, e == a.V - 1, a.D);
+                tk_row_finish<NK, SPLIT>(v, a.table, a.D, e, rok, e == a.V - 1, a.D, ah, al);
+            }
             const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
             if (li == 0) {
 #pragma unroll
@@ -364,6 +427,30 @@ __global__ __launch_bounds__(256) void k_topk_merge(TkArgs a) {
         }
     }
     if (lane == 0) a.rank[b] = raw - sub;
+}
+
+// The index of a table: a wave per tile of 16 rows, the fragments exactly as the sweep forms them (rows >= V and columns >= D: +0).
+template <int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_topk_index_build(const float* table, int V, int D, bf8* idx, int64_t plane, int n_tiles) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15;
+    const int tile = blockIdx.x * 4 + wave;
+    if (tile >= n_tiles) return;                           // wave-uniform
+    const int row = tile * 16 + li;
+    float v[NK][8];
+    bf8 h[NK], lo[NK];
+    tk_row_issue<NK>(v, table, D, row, row < V, row == V - 1, D);
+    tk_row_finish<NK, SPLIT>(v, table, D, row, row < V, row == V - 1, D, h, lo);
+    bf8* p = idx + (int64_t)tile * (NK * 64) + lane;
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        p[ks * 64] = h[ks];
+        if (SPLIT) p[plane + ks * 64] = lo[ks];
+    }
+}
+
+// planes of an index of `precision`: 2 (hi + lo; CR_PREC_F32 as CR_PREC_BF16X3), 1 (plain bf16), 0 for anything else
+int tk_index_planes(int precision) {
+    return (precision == CR_PREC_BF16X3 || precision == CR_PREC_F32) ? 2 : precision == CR_PREC_BF16 ? 1 : 0;
 }
 
 struct TkGeom {
@@ -394,16 +481,39 @@ size_t tk_workspace(int B, const TkGeom& g, int K) {
     return cr_align256(8 * ((size_t)B + 1)) + cr_align256(4 * (size_t)B) + 2 * cr_align256(nb * K * 4) + cr_align256(nb * 4);
 }
 
-template <int NK, bool SPLIT>
-void tk_launch(const TkArgs& a, const TkGeom& g, hipStream_t st) {
+template <int NK, bool SPLIT, bool IDX>
+void tk_launch(const TkA<IDX>& a, const TkGeom& g, hipStream_t st) {
     const dim3 grid(g.n_qt, g.n_chunks);
-    if (g.QB == 4) hipLaunchKernelGGL((k_topk_sweep<NK, 4, SPLIT>), grid, dim3(256), g.lds, st, a);
-    else if (g.QB == 2) hipLaunchKernelGGL((k_topk_sweep<NK, 2, SPLIT>), grid, dim3(256), g.lds, st, a);
-    else hipLaunchKernelGGL((k_topk_sweep<NK, 1, SPLIT>), grid, dim3(256), g.lds, st, a);
-    hipLaunchKernelGGL((k_topk_merge<NK, SPLIT>), dim3((a.B + 3) / 4), dim3(256), 0, st, a);
+    if (g.QB == 4) hipLaunchKernelGGL((k_topk_sweep<NK, 4, SPLIT, IDX>), grid, dim3(256), g.lds, st, a);
+    else if (g.QB == 2) hipLaunchKernelGGL((k_topk_sweep<NK, 2, SPLIT, IDX>), grid, dim3(256), g.lds, st, a);
+    else hipLaunchKernelGGL((k_topk_sweep<NK, 1, SPLIT, IDX>), grid, dim3(256), g.lds, st, a);
+    hipLaunchKernelGGL((k_topk_merge<NK, SPLIT, IDX>), dim3((a.B + 3) / 4), dim3(256), 0, st, a);
 }
 
 }  // namespace
+
+extern "C" size_t cr_topk_index_bytes(int V, int D, int precision) {
+    const int planes = tk_index_planes(precision);
+    if (V < 1 || D < 8 || D > 256 || planes == 0) return 0;
+    return (size_t)planes * (((size_t)V + 15) / 16) * (size_t)tk_nk(D) * 1024;
+}
+
+extern "C" int cr_topk_index_build(const float* table, int V, int D, int precision, void* index, size_t index_bytes, void* stream) {
+    CR_REQUIRE(table && index, "cr_topk_index_build: NULL table or index");
+    CR_REQUIRE(D >= 8 && D <= 256, "cr_topk_index_build: D=%d outside 8 .. 256", D);
+    CR_REQUIRE(V >= 1, "cr_topk_index_build: V=%d must be >= 1", V);
+    CR_REQUIRE(tk_index_planes(precision) != 0, "cr_topk_index_build: unknown precision %d", precision);
+    const size_t need = cr_topk_index_bytes(V, D, precision);
+    CR_REQUIRE(index_bytes >= need, "cr_topk_index_build: index of %zu bytes, cr_topk_index_bytes says %zu", index_bytes, need);
+    const int NK = tk_nk(D), n_tiles = (int)(((int64_t)V + 15) / 16);
+    const int64_t plane = (int64_t)n_tiles * NK * 64;
+    bf8* idx = static_cast<bf8*>(index);
+    hipStream_t st = cr_stream(stream);
+    tk_dispatch(NK, tk_index_planes(precision) == 2, [&](auto nk, auto sp) {
+        hipLaunchKernelGGL((k_topk_index_build<nk, sp>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, V, D, idx, plane, n_tiles);
+    });
+    return cr_check_launch("cr_topk_index_build");
+}
 
 extern "C" size_t cr_score_topk_workspace(int B, int V, int D, int K) {
     TkGeom g;
@@ -417,11 +527,21 @@ extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
     CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_score_topk: D=%d outside 8 .. 256", d->D);
     CR_REQUIRE(d->B >= 1 && d->V >= 1, "cr_score_topk: B=%d, V=%d must be >= 1", d->B, d->V);
     CR_REQUIRE(d->ld >= d->D, "cr_score_topk: ld=%d < D=%d", d->ld, d->D);
-    CR_REQUIRE(d->query && d->table, "cr_score_topk: NULL query or table");
+    if (d->index) CR_REQUIRE(d->query, "cr_score_topk: NULL query");
+    else CR_REQUIRE(d->query && d->table, "cr_score_topk: NULL query or table");
     CR_REQUIRE(d->top_ids && d->top_scores, "cr_score_topk: NULL output (top_ids / top_scores)");
     CR_REQUIRE(!d->targets || d->rank, "cr_score_topk: targets given but rank is NULL");
     CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
                "cr_score_topk: unknown precision %d", d->precision);
+    if (d->index) {
+        const int planes = tk_index_planes(d->index_precision);
+        CR_REQUIRE(planes != 0, "cr_score_topk: unknown index_precision %d", d->index_precision);
+        CR_REQUIRE(planes == 2 || d->precision == CR_PREC_BF16,
+                   "cr_score_topk: a plain bf16 index serves precision CR_PREC_BF16 only, not %d", d->precision);
+        const size_t ib = cr_topk_index_bytes(d->V, d->D, d->index_precision);
+        CR_REQUIRE(d->index_bytes == ib, "cr_score_topk: index_bytes=%zu, cr_topk_index_bytes(V=%d, D=%d) says %zu", d->index_bytes,
+                   d->V, d->D, ib);
+    }
     if (d->excl_off) {
         CR_REQUIRE(d->excl_off[0] >= 0, "cr_score_topk: excl_off[0]=%lld < 0", (long long)d->excl_off[0]);
         for (int b = 0; b < d->B; ++b)
@@ -457,6 +577,15 @@ extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
     a.top_ids = d->top_ids; a.top_scores = d->top_scores; a.rank = d->rank;
     a.chunk = g.chunk; a.n_chunks = g.n_chunks;
     const bool split = d->precision != CR_PREC_BF16;       // CR_PREC_F32: the bf16x3 products (fp32-grade)
-    tk_dispatch(g.NK, split, [&](auto nk, auto sp) { tk_launch<nk, sp>(a, g, st); });
+    if (d->index) {
+        TkIdxArgs ia;
+        static_cast<TkArgs&>(ia) = a;
+        ia.idx = static_cast<const bf8*>(d->index);
+        ia.n_tiles = (int)(((int64_t)d->V + 15) / 16);
+        ia.plane = (int64_t)ia.n_tiles * g.NK * 64;
+        tk_dispatch(g.NK, split, [&](auto nk, auto sp) { tk_launch<nk, sp, true>(ia, g, st); });
+    } else {
+        tk_dispatch(g.NK, split, [&](auto nk, auto sp) { tk_launch<nk, sp, false>(a, g, st); });
+    }
     return cr_check_launch("cr_score_topk");
 }

@@ -1637,12 +1637,13 @@ class Engine:
         O.test_logits(self.seq_emb, self.seq_emb.shape[1], self.p("item_emb"), cand, self.B, self.T, self.D, out)
         return out
 
-    def topk(self, k, excl_off=None, excl_ids=None, targets=None):
+    def topk(self, k, excl_off=None, excl_ids=None, targets=None, index=None):
         """Full-catalogue top-k of the last position of every sequence (after forward_eval): (ids [B, k] int32, scores [B, k] fp32,
         rank [B] int32 or None) as device tensors.  excl_off: host int64 [B + 1] CSR offsets into excl_ids (int32, host or device) --
         the items each row must not return nor count in its target's rank; targets: [B] ids whose rank among the eligible items is
         wanted (-1: excluded).  Scores come from bf16x3 products (fp32-grade; plain bf16 on an engine at attn_precision 'bf16');
-        test_logits keeps its exact fp32 form.  castrec.h cr_score_topk."""
+        test_logits keeps its exact fp32 form.  index: an ItemIndex of this engine's item table (castrec_amd.index): the scores come
+        from it instead of the table, with the same bits.  castrec.h cr_score_topk."""
         B, V, D = self.B, self.itemnum + 1, self.D
         need = O.topk_workspace_bytes(B, V, D, int(k))
         ws = getattr(self, "_topk_ws", None)
@@ -1664,6 +1665,12 @@ class Engine:
         se = self.seq_emb
         ld = se.shape[1]
         query = se[self.T - 1:]                           # row b of the queries: seq_emb row b * T + T - 1
+        if index is not None:
+            if (index.V, index.D) != (V, D):
+                raise ValueError("index of a [%d, %d] table, the engine's item table is [%d, %d]" % (index.V, index.D, V, D))
+            O.score_topk(query, self.T * ld, (V, D), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank,
+                         index=index.blob, index_precision=index.prec)
+            return ids, scores, rank
         O.score_topk(query, self.T * ld, self.p("item_emb"), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank)
         return ids, scores, rank
 

@@ -33,6 +33,7 @@ class _Model(object):
         # parameters exist from construction on (tf.global_variables_initializer, main.py:150)
         self._owner = Engine(self.name, usernum, itemnum, self.hp, 1, training=False)
         self.attention_weights = None
+        self._param_version = 0               # bumped by whatever changes the parameters: an ItemIndex records the one it was built at
 
     # -- training ---------------------------------------------------------------------------------
     def data_parallel(self, rank, world, process_group=None, sparse=None):
@@ -127,6 +128,7 @@ class _Model(object):
             self._dp.step(arrs)                            # this rank's rows -> backward -> exchange -> Adam (loss / auc: global)
         else:
             eng.train_step(*arrs)
+        self._param_version += 1
         if fetch:
             loss, auc = eng.loss_auc()
             return auc, loss
@@ -177,6 +179,7 @@ class _Model(object):
         eng = self._train
         if eng is None or getattr(eng, "_feed_ring", None) is None:
             raise RuntimeError("train_fed_many(): feed() a batch first")
+        self._param_version += 1
         return eng.train_fed(max_steps=max_steps)
 
     def loss_auc(self):
@@ -190,6 +193,7 @@ class _Model(object):
         eng = self._train
         if eng is None or getattr(eng, "_feed_ring", None) is None:
             raise RuntimeError("train_fed(): feed() a batch first")
+        self._param_version += 1
         eng.train_fed(max_steps=1)
         if fetch:
             loss, auc = eng.loss_auc()
@@ -222,13 +226,50 @@ class _Model(object):
                                      want_attn=want_attention)
         return self._eval[key]
 
+    def build_item_index(self, precision=None):
+        """An ItemIndex (castrec_amd.index) of the current item table for recommend(index=), similar_items(index=) and
+        ItemIndex.search / save.  precision: "bf16x3" or "bf16"; by default what the engine's top-K computes in ("bf16" at
+        attn_precision "bf16").  The index is a snapshot: it records the parameter version, and recommend refuses it once a
+        training step or a load has changed the parameters."""
+        from .index import ItemIndex
+        if precision is None:
+            precision = "bf16" if self._owner.attn_precision == "bf16" else "bf16x3"
+        return ItemIndex.build(self._owner.p("item_emb"), precision, version=self._param_version)
+
+    def _check_index(self, index):
+        if index is None:
+            return
+        if (index.V, index.D) != (self.itemnum + 1, self._owner.D):
+            raise ValueError("index of a [%d, %d] table, the model's item table is [%d, %d]"
+                             % (index.V, index.D, self.itemnum + 1, self._owner.D))
+        if index.version is not None and index.version != self._param_version:
+            raise RuntimeError("stale index: built at parameter version %d, the model is at %d (build_item_index() again)"
+                               % (index.version, self._param_version))
+
+    def similar_items(self, ids, k=10, index=None):
+        """The k items whose table rows have the largest dot product with each given item's own row (the model's geometry: the scores
+        of recommend with the item's vector as the query), the item itself left out.  Returns numpy (ids [n, k], scores [n, k]).
+        index: an ItemIndex of the table to search instead of one built for this call."""
+        from .index import ItemIndex
+        ids = np.asarray(ids, np.int64).ravel()
+        if ids.size == 0 or ids.min() < 1 or ids.max() > self.itemnum:
+            raise ValueError("ids must be item ids in 1 .. %d" % self.itemnum)
+        self._check_index(index)
+        table = self._owner.p("item_emb")
+        if index is None:
+            index = ItemIndex.build(table, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3")
+        q = table[torch.from_numpy(ids).to(table.device)]
+        return index.search(q, int(k), exclude=[[int(i)] for i in ids])
+
     def recommend(self, u, seq, k=10, timeseq=None, hours_seq=None, days_seq=None, exclude="history", return_scores=True,
-                  targets=None):
+                  targets=None, index=None):
         """The k best items of the whole catalogue for each row of a batch (the last position's scores against every item row,
         sasrec.py:93-97 extended from a candidate list to the table; castrec.h cr_score_topk).  exclude: "history" (the nonzero ids
         of each row of seq), None, or one iterable of ids per row.  Returns numpy (ids [B, k], scores [B, k]) -- ids only when
         return_scores is False -- and, with targets ([B] ids), a third array: each target's 0-based rank among the eligible items
-        (-1 for an excluded target).  Rows with fewer than k eligible items end in id 0, score -inf."""
+        (-1 for an excluded target).  Rows with fewer than k eligible items end in id 0, score -inf.  index: an ItemIndex of the item
+        table (build_item_index): same results, the table's rows are not converted again."""
+        self._check_index(index)
         seq = np.asarray(seq)
         if seq.ndim == 1:
             seq = seq[None]
@@ -252,7 +293,7 @@ class _Model(object):
             off = np.zeros(B + 1, np.int64)
             off[1:] = np.cumsum([len(r) for r in rows])
             ids = np.concatenate(rows).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
-        top, sc, rk = eng.topk(int(k), off, ids, targets)
+        top, sc, rk = eng.topk(int(k), off, ids, targets, index=index)
         out = (top.cpu().numpy(),) + ((sc.cpu().numpy(),) if return_scores else ())
         if targets is not None:
             out = out + (rk.cpu().numpy(),)
@@ -288,6 +329,7 @@ class _Model(object):
                 self._apply_opt(d["M"], d["V"], nxt)
             else:
                 self._pending_opt = (d["M"], d["V"], nxt)
+        self._param_version += 1
 
     def load_tf_checkpoint(self, prefix):
         """Loads a checkpoint written by the reference (tf.train.Saver bundle `<prefix>.index` +
@@ -317,12 +359,14 @@ class _Model(object):
                 self._apply_opt(M, V, steps + 1)
             else:
                 self._pending_opt = (M, V, steps + 1)
+        self._param_version += 1
 
     def get_params(self):
         return self._owner.get_params()
 
     def load_params(self, d):
         self._owner.load_params(d)
+        self._param_version += 1
 
 
 class SASRec(_Model):

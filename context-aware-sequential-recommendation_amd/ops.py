@@ -133,20 +133,51 @@ def topk_workspace_bytes(B, V, D, K):
     return n
 
 
-def score_topk(query, ld, table, B, K, precision, excl_off, excl_ids, targets, workspace, top_ids, top_scores, rank=None):
+def score_topk(query, ld, table, B, K, precision, excl_off, excl_ids, targets, workspace, top_ids, top_scores, rank=None,
+               index=None, index_precision=None):
     """cr_score_topk: query rows query + b * ld (a float32 CUDA tensor's storage), table [V, D]; excl_off a host int64 numpy array
-    [B + 1] or None, excl_ids an int32 CUDA tensor; workspace a uint8 CUDA tensor of at least topk_workspace_bytes bytes."""
+    [B + 1] or None, excl_ids an int32 CUDA tensor; workspace a uint8 CUDA tensor of at least topk_workspace_bytes bytes.
+    index: a uint8 CUDA tensor from topk_index_build (index_precision: what it was built with) -- the scores then come from it and
+    `table` may be the (V, D) pair instead of the tensor."""
     import numpy as np
     off = None
     if excl_off is not None:
         off = np.ascontiguousarray(excl_off, np.int64)
         if off.shape != (B + 1,):
             raise ValueError("excl_off must have B + 1 = %d entries, got %s" % (B + 1, off.shape))
-    d = L.TopkDesc(_p(_f32(query, "query")), ld, _p(_f32(table, "table")), table.shape[0], table.shape[1], B, K, precision,
+    if index is not None and not torch.is_tensor(table):
+        (V, D), table = table, None
+    else:
+        V, D = table.shape
+    d = L.TopkDesc(_p(_f32(query, "query")), ld, _p(_f32(table, "table")), V, D, B, K, precision,
                    None if off is None else off.ctypes.data, _p(_i32(excl_ids, "excl_ids")), _p(_i32(targets, "targets")),
                    _p(_i32(top_ids, "top_ids")), _p(_f32(top_scores, "top_scores")), _p(_i32(rank, "rank")),
                    _p(workspace), workspace.numel() * workspace.element_size())
+    if index is not None:
+        if index.dtype != torch.uint8 or not index.is_cuda or not index.is_contiguous():
+            raise TypeError("index must be a contiguous uint8 CUDA tensor")
+        d.index, d.index_bytes, d.index_precision = index.data_ptr(), index.numel(), int(precision if index_precision is None else index_precision)
     L.call("cr_score_topk", C.byref(d), _stream())
+
+
+def topk_index_bytes(V, D, precision=L.PREC_BF16X3):
+    n = L.lib.cr_topk_index_bytes(V, D, precision)
+    if n == 0:
+        raise ValueError("cr_topk_index_bytes: unsupported V=%d D=%d precision=%d (V >= 1, 8 <= D <= 256)" % (V, D, precision))
+    return n
+
+
+def topk_index_build(table, precision=L.PREC_BF16X3, out=None):
+    """cr_topk_index_build: the item index of table [V, D] (a contiguous float32 CUDA tensor) as a uint8 CUDA tensor."""
+    _f32(table, "table")
+    if table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("table must be a contiguous [V, D] tensor")
+    V, D = table.shape
+    n = topk_index_bytes(V, D, precision)
+    if out is None:
+        out = torch.empty(n, dtype=torch.uint8, device=table.device)
+    L.call("cr_topk_index_build", _p(table), V, D, precision, out.data_ptr(), out.numel(), _stream())
+    return out
 
 
 def softmax_ce_workspace_bytes(M, V, D):

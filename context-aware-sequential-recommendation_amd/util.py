@@ -243,10 +243,11 @@ def _eval_users(usernum):
     return range(1, usernum + 1)
 
 
-def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256):
+def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256, use_index=False):
     """Full-ranking form of _evaluate: the same users (those its next call samples) and inputs, the target ranked against EVERY item outside the user's `rated`
     set (the set the sampled evaluator draws its 100 negatives outside of) instead of against 100 of them.  Draws nothing from
-    np.random.  rank = #{eligible i : s_i > s_t} + #{eligible i != t : s_i == s_t, i < t} (castrec.h cr_score_topk)."""
+    np.random.  rank = #{eligible i : s_i > s_t} + #{eligible i != t : s_i == s_t, i < t} (castrec.h cr_score_topk).
+    use_index: one ItemIndex of the item table, built here, serves every batch (same ranks, bit for bit)."""
     train, valid, test, usernum, itemnum = dataset[0], dataset[1], dataset[2], dataset[3], dataset[4]
     min_td, max_td = get_delta_range(train)
     rows = []
@@ -255,13 +256,14 @@ def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256):
         if r is not None:
             rows.append((u,) + r)
     NDCG = HT = 0.0
+    kw = {"index": model.build_item_index()} if use_index else {}
     for i in range(0, len(rows), eval_batch):
         chunk = rows[i:i + eval_batch]
         us = [c[0] for c in chunk]
         seq, ts, hrs, dys = (np.stack([c[j] for c in chunk]) for j in range(1, 5))
         tgt = np.array([c[5][0] for c in chunk], np.int32)
         excl = [sorted(c[5][1] - {c[5][0]}) for c in chunk]     # the target itself always competes (as item_idx[0] does)
-        _, _, rank = model.recommend(us, seq, k=k, timeseq=ts, hours_seq=hrs, days_seq=dys, exclude=excl, targets=tgt)
+        _, _, rank = model.recommend(us, seq, k=k, timeseq=ts, hours_seq=hrs, days_seq=dys, exclude=excl, targets=tgt, **kw)
         for rk in rank:
             if 0 <= rk < k:
                 NDCG += 1 / np.log2(rk + 2)
@@ -270,11 +272,11 @@ def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256):
     return NDCG / n, HT / n
 
 
-def evaluate_full(model, dataset, args, sess=None, k=10):
+def evaluate_full(model, dataset, args, sess=None, k=10, use_index=False):
     """(NDCG@k, HR@k) of the test split over the full catalogue (see _evaluate_full)."""
-    return _evaluate_full(model, dataset, args, "test", k)
+    return _evaluate_full(model, dataset, args, "test", k, use_index=use_index)
 
 
-def evaluate_valid_full(model, dataset, args, sess=None, k=10):
+def evaluate_valid_full(model, dataset, args, sess=None, k=10, use_index=False):
     """(NDCG@k, HR@k) of the validation split over the full catalogue."""
-    return _evaluate_full(model, dataset, args, "valid", k)
+    return _evaluate_full(model, dataset, args, "valid", k, use_index=use_index)

@@ -464,9 +464,31 @@ struct cr_topk_desc {
     int32_t* rank;                    /* device [B]; required with targets */
     void* workspace;
     size_t workspace_bytes;
+    const void* index;                /* optional: an item index of the table (below); NULL: the table is read */
+    size_t index_bytes;               /* == cr_topk_index_bytes(V, D, index_precision) */
+    int index_precision;              /* the precision the index was built with */
 };
 size_t cr_score_topk_workspace(int B, int V, int D, int K);    /* 0 for a shape outside the supported range */
 int cr_score_topk(const cr_topk_desc* d, void* stream);
+
+/* ---- item index: the table pre-split into the sweep's operand fragments (csrc/cr_topk.hip) ----------------------------
+ * cr_score_topk masks every item row and splits it into bf16 hi / lo fragments in every workgroup of every call.  An index holds
+ * those fragments, made once (by the same code, so the bits are the sweep's) and stored in the order the sweep's lanes read them.
+ * Layout: NK = 1, 2, 4 or 8 k-steps (D / 32 rounded up to one of them), n_tiles = ceil(V / 16), planes = 2 for a split index
+ * (CR_PREC_BF16X3; CR_PREC_F32 means the same) or 1 for a plain one (CR_PREC_BF16).  The blob is an array of 16-byte groups of
+ * eight bf16; group (plane h, tile t, k-step ks, lane l) is at byte (((h n_tiles + t) NK + ks) 64 + l) 16 and its element j is
+ * column c = 32 ks + 8 (l >> 4) + j of row r = 16 t + (l & 15): plane 0 hi = bf16(x) (round to nearest even), plane 1
+ * lo = bf16(x - hi); +0 where r >= V or c >= D.  Row 0 is stored like any row (the sweep never makes it eligible).
+ * planes n_tiles NK 1024 bytes in all: the size of the fp32 table at D a multiple of 32 (split), half of it (plain).
+ *   - cr_topk_index_bytes: that size; 0 for V < 1, D outside 8 .. 256 or an unknown precision.  No device call.
+ *   - cr_topk_index_build: one asynchronous launch that writes the whole blob (padding included) from table [V, D]; index: device
+ *     memory, 16-byte aligned, of index_bytes >= cr_topk_index_bytes(V, D, precision).  Two builds give the same bytes.
+ *   - cr_topk_desc.index != NULL: every score (the sweep's item rows, the target rows, the excluded rows of the rank) comes from
+ *     the index; `table` is not read and may be NULL; the results are the bits of the call on the table the index was built
+ *     from.  A split index serves every precision (CR_PREC_BF16 reads plane 0 only); a plain index serves CR_PREC_BF16 only.
+ *     index_bytes must equal cr_topk_index_bytes(V, D, index_precision).  Checked before any device call, as everything else. */
+size_t cr_topk_index_bytes(int V, int D, int precision);
+int cr_topk_index_build(const float* table, int V, int D, int precision, void* index, size_t index_bytes, void* stream);
 
 /* ---- full-catalogue softmax cross-entropy (csrc/cr_ce.hip) ----------------------------------------------------------
  * The training objective over the whole item table, an alternative to cr_head_fwd_bwd's one-negative BCE.  Rows m = 0 .. M-1,
