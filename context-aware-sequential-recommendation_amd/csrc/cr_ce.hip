@@ -1,50 +1,50 @@
-// Softmax cross-entropy without ever writing the [M, candidates] scores, and its un-normalised gradients wrt h and E (castrec.h):
-//  * cr_softmax_ce, the full catalogue: per batch row m the loss logsumexp_v s_mv - s_{m,pos_m} over the items v = 1 .. V-1 with
-//    s_mv = h_m . E_v;
-//  * cr_sampled_ce, shared uniform negatives: log(exp z_{m,pos} + sum_{j: s_j != pos_m} exp z_{m,s_j}) - z_{m,pos} over the target and
-//    N sample ids shared by the call, against a compact table of the samples' rows, so the cost is O(M N D), independent of V.
-//  * cr_gbce, gSASRec's generalised binary cross-entropy over the same shared negatives: beta softplus(-z_{m,pos}) + sum_{j: s_j !=
-//    pos_m} softplus(z_{m,s_j}).  A pointwise objective has no normaliser, so one row sweep gives the loss and dh (gbce_row below) and
-//    the item sweep is de without a per-row statistic; ids, dedup, stats, scatter and tgt are the sampled op's.
-// The two softmax ops run the same four sweep passes, templated on the candidate kind -- the argument struct: CeArgs, the catalogue, whose candidates
-// are the items 1 .. V-1 of E with the target among them; SceArgs, the sampled, whose candidates are the N gathered rows Es with the
-// target beside them (a sample equal to a row's target is masked; the target's own terms come separately); ScePopArgs, the sampled
-// under a popularity proposal, whose every candidate score carries the log-Q correction -logq[id] (castrec.h) as a base-2 bias that
-// travels beside the ids:
+// The candidate-sweep losses: none writes the [M, candidates] scores; each gives the loss sums and the un-normalised gradients wrt h
+// and E (castrec.h).  A score is s_mv = h_m . E_v; pos_m is row m's target (0: the row is padding).
 //
-//  * lse    (a workgroup per 64 rows, 256 threads).  Each wave keeps its 16 rows as B fragments in registers; the workgroup streams the
-//           candidates through an LDS image of 32 rows (bf16 hi / lo, cr_bf16.hpp img_off<2>), filled from registers loaded a block
-//           ahead.  A wave scores its rows against the block (tk_tile: the product sequence of cr_topk.hip, so a score has the same bits
-//           here as there) and folds the scores into a running base-2 max / sum per lane (exp2 with log2 e folded into the score); the
-//           four lane groups of a row merge in a fixed butterfly.  Out: lse2 = log2 sum exp2 per row, the row tile's loss / AUC / target
-//           sums.  Catalogue: the target and neg scores are picked up as the sweep passes them.  Sampled: they come from diagonal tiles
-//           of the gathered rows E[pos] / E[neg] against the wave's own rows (tk_tile again; cr_score_topk's ranks use the same trick),
-//           the target enters the running max / sum of lane group 0 before the first block, and gpos = p_pos - 1 is written per row.
-//  * stats  (one wave).  The row tiles' sums in a fixed order: state[0..2] +=, then the snapshot [8..11] (see castrec.h, state block).
-//  * dh     (same grid as lse).  The same sweep recomputes each score, p = exp2(s log2 e - lse2) (catalogue: minus the one-hot of pos;
-//           sampled: 0 at a hit), and multiplies the [16 rows x 32 candidates] G block by the candidate block: A = G straight from the
-//           two score tiles' accumulators (k slot 8 lg + j <-> candidate (j < 4 ? 0 : 16) + 4 lg + (j & 3)), B = the same LDS image
-//           read transposed (tr_frag with that k order).  Sampled: the epilogue adds gpos_m E[pos_m] in fp32.
-//  * de     (a workgroup per 64 candidates x a part of the rows).  Each wave keeps its 16 candidates as B fragments; the batch rows of
-//           the part stream through the LDS image.  The score tile is computed with the roles swapped (ce_tile_t: rows as A, candidates
-//           as B, the three products in tk_tile's order), so a lane holds rows against its candidate -- the A operand of dE = G^T H;
-//           B = the row image read transposed.  Each part writes its slice of the workspace; a catalogue of one part += into table_grad.
-// Around the sweeps, per op:
-//  * de_sum  (catalogue, parts > 1) adds the parts into table_grad in part order.
-//  * ids     (sampled; grid-stride over N x D).  Copy or draw the N ids (castrec.h states the draw), write them and samples_out, and
-//            gather the N rows of E into the compact fp32 table Es [N, D] of the workspace.  Popularity proposal (ids_pop): the id of
-//            a sample is found once, by the workgroup that holds its first element -- a copy, or the binary search of the cdf -- and
-//            handed to the gathering threads through LDS; the same thread writes the sample's bias -logq[id] log2 e.
-//  * dedup   (sampled, a thread per sample; only with table_grad).  For sample j: whether it is its id's first occurrence, and the next
-//            j' > j with the same id (a linked list in j order).  Each thread compares its id against all N through LDS chunks: O(N^2)
-//            compares, a few microseconds at N = 4096.
-//  * scatter (sampled, a workgroup per sample).  The first occurrence of each id walks its list in j order, adds the parts in part
-//            order and += the sum into table_grad[id]: one writer per distinct id.
-//  * tgt     (sampled; grid-stride over M x D).  dE_{pos_m} += gpos_m h_m with float atomics.
-//  * gbce_row (gBCE; the grid of lse).  The sweep of dh with g = sigma(score) (0 at a hit) from one exp2 per score, the softplus of the
-//            same exponential summed per lane in sweep order, and lse's prologue / epilogue: the target's score from the diagonal
-//            tile, gpos = beta (sigma_pos - 1), the row's loss, the row tile's sums, dh += gpos E[pos] in fp32.
-// Every partition is fixed by the shape; the sampled tgt is the only pass with float atomics (the one non-deterministic output).
+// The skeleton, written once:
+//  * stream  (ce_stream).  A workgroup of 256 threads streams rows of an fp32 matrix through an LDS image of 32 rows (bf16 hi / lo,
+//            cr_bf16.hpp img_off<2>), filled from registers loaded a block ahead, with up to two words per row beside it (ids, biases,
+//            pos, lse2), staged the same way.  Each wave holds 16 rows of the other operand as B fragments and scores them against
+//            the block in two tiles (tk_tile: the product sequence of cr_topk.hip, so a score has the same bits here as there); the
+//            caller gives what happens to a score tile and what happens once per block while the image is still there.
+//  * row kernels (a workgroup per 64 batch rows; ce_row: the wave's rows, ce_row_scores: neg and the diagonal scores, ce_tile_stats:
+//            the row tile's loss / AUC / target sums, ce_store_dh).  The candidates (ce_cands) stream past the wave's batch rows.
+//  * de      (k_ce_de, a workgroup per 64 candidates x a part of the rows).  Each wave keeps 16 candidates; the batch rows of the part
+//            stream past with pos (and lse2) beside them.  The score tile has the roles swapped (ce_tile_t: the three products in
+//            tk_tile's order), so a lane holds rows against its candidate -- the A operand of dE = G^T H (g_times_img: A = G straight
+//            from the two score tiles' accumulators, k slot 8 lg + j <-> image row (j < 4 ? 0 : 16) + 4 lg + (j & 3); B = the image
+//            read transposed, tr_frag with that k order).  Each part writes its slice of the workspace; a catalogue of one part +=
+//            into table_grad.
+//  * stats   (k_ce_stats, one wave).  The row tiles' sums in a fixed order: state[0..2] +=, then the snapshot [8..11] (castrec.h).
+// The ops are kinds of candidates -- the argument struct -- and what they do per score:
+//  * cr_softmax_ce, CeArgs: the items 1 .. V-1 of E with the target among them.  Loss logsumexp_v s_mv - s_{m,pos_m}.
+//      lse     per lane a running base-2 max / sum (exp2 with log2 e folded into the score; 64 blocks per inner partial), the four
+//              lane groups of a row merged in a fixed butterfly; the target and neg scores are picked up as the sweep passes them.
+//              Out: lse2 = log2 sum exp2 per row, the row tile's sums.
+//      dh      the same sweep recomputes each score, g = exp2(s log2 e - lse2) - [v = pos], dh = G x the block (g_times_img).
+//      de      g as in dh; de_sum (parts > 1) adds the parts into table_grad in part order.
+//  * cr_sampled_ce, SceArgs: N sample ids shared by the call, as the gathered rows Es [N, D], the target beside them: log(exp z_pos +
+//    sum_{j: s_j != pos_m} exp z_{m,s_j}) - z_pos, O(M N D) independent of V.  The deltas:
+//      ids     (grid-stride over N x D) copies or draws the ids (castrec.h states the draw), writes them and samples_out, gathers Es.
+//      dedup   (a thread per sample; only with table_grad) whether sample j is its id's first occurrence, and the next j' > j with
+//              the same id: each thread compares against all N ids through LDS chunks, a few microseconds at N = 4096.
+//      lse     a sample equal to the row's target is masked; the target and neg scores come from diagonal tiles of E[pos] / E[neg]
+//              against the wave's own rows (tk_tile again; cr_score_topk's ranks use the same trick); the target enters the running
+//              max / sum of lane group 0 before the first block; gpos = p_pos - 1 is written per row.
+//      dh      g = 0 at a hit; the store adds gpos_m E[pos_m] in fp32.
+//      de      every part writes its slice; scatter (a workgroup per sample): the first occurrence of each id walks its list in j
+//              order, adds the parts in part order and += the sum into table_grad[id], one writer per distinct id; tgt (grid-stride
+//              over M x D): dE_{pos_m} += gpos_m h_m with float atomics.
+//  * ... under a popularity proposal, ScePopArgs: every candidate score carries the log-Q correction -logq[id] (castrec.h) as a base-2
+//    bias, the second word beside a sample's id.  ids_pop: the id of a sample is found once, by the workgroup that holds its first
+//    element -- a copy, or the binary search of the cdf -- and handed to the gathering threads through LDS; the same thread writes
+//    the bias -logq[id] log2 e.
+//  * cr_gbce, GbceArgs: gSASRec's generalised binary cross-entropy over the sampled op's candidates, beta softplus(-z_pos) +
+//    sum_{j: s_j != pos_m} softplus(z_{m,s_j}).  A pointwise objective has no normaliser, so one row kernel (k_gbce_row) stands for
+//    lse and dh: g = sigma(score) (0 at a hit) from one exp2 per score, the softplus of the same exponential summed per lane in sweep
+//    order; gpos = beta (sigma_pos - 1).  de: g = sigma, no lse2 beside pos.  ids (its own draw site), dedup, stats, scatter, tgt: the
+//    sampled op's.
+// Every partition is fixed by the shape; tgt is the only pass with float atomics (the one non-deterministic output).
 // One MFMA shape in this file (build.py ISA_CHECKED): v_mfma_f32_16x16x32_bf16.
 #include <algorithm>
 
@@ -54,36 +54,38 @@ namespace {
 
 constexpr float CE_LOG2E = 1.4426950408889634f;
 constexpr float CE_LN2 = 0.6931471805599453f;
-constexpr int CE_BLK = 32;                  // rows of the streamed LDS block (candidates in lse / dh, batch rows in de)
+constexpr int CE_BLK = 32;                  // rows of the streamed LDS block (candidates in the row kernels, batch rows in de)
 constexpr int CE_PART_ELEMS = 32768;        // catalogue: parts x V of the de pass's partial sums at most (the workspace reserves
 constexpr int CE_MAX_PARTS = 16;            //   min(16 V, this) rows)
 constexpr int SCE_PART_ROWS = 65536;        // sampled: parts x N of the de pass's partial sums at most
 constexpr int SCE_MAX_PARTS = 64;
 constexpr int SCE_CHUNK = 2048;             // ids per LDS chunk of the dedup pass
 
-struct CeArgs {
-    static constexpr bool SAMPLED = false, GBCE = false, POP = false;
+// what every kind has
+struct CeBase {
     const float* h; int64_t ldh;
     const float* E;
     const int32_t* pos; const int32_t* neg;
     int M, D, V;
-    float* lse2;                            // [M] log2 sum_v exp2(s_mv log2 e)
+    float* lse2;                            // [M] log2 of the candidate sum (base-2 exponent of the scores); gBCE: none
     float* stats;                           // [n_rt, 4] loss / auc / target sums per row tile
     float* dh; int64_t ldd;
     float* tg;
-    float* part;                            // [parts, V, D] (parts > 1)
+    float* part;                            // [parts, V or N, D] (catalogue: parts > 1)
     int rpp, parts;                         // batch rows per part of the de pass
-    float* lse_out;
+    float* lse_out;                         // [M] or NULL (gBCE: the per-row loss)
     float* state;
     int n_rt;
 };
 
-struct SceArgs {
+struct CeArgs : CeBase {
+    static constexpr bool SAMPLED = false, GBCE = false, POP = false;
+};
+
+struct SceArgs : CeBase {
     static constexpr bool SAMPLED = true, GBCE = false, POP = false;
-    const float* h; int64_t ldh;
-    const float* E;
-    const int32_t* pos; const int32_t* neg;
-    int M, D, V, N;
+    static constexpr uint32_t SITE = CR_SCE_SITE;
+    int N;
     const int32_t* samples;                 // caller's ids, or NULL: drawn from (seed, *step)
     uint32_t seed; const uint32_t* step;
     int32_t* sid;                           // [N] the ids used
@@ -91,21 +93,13 @@ struct SceArgs {
     int32_t* nxt;                           // [N] next j' > j with the same id (N: none)
     int32_t* head;                          // [N] 1 where j is its id's first occurrence
     float* Es;                              // [N, D] gathered rows
-    float* lse2;                            // [M] log2 of the candidate sum (base-2 exponent of the scores)
-    float* gpos;                            // [M] p_pos - 1 for target rows, 0 elsewhere
-    float* stats;                           // [n_rt, 4] loss / auc / target sums per row tile
-    float* dh; int64_t ldd;
-    float* tg;
-    float* part;                            // [parts, N, D]
-    int rpp, parts;                         // batch rows per part of the de pass
-    float* lse_out;
-    float* state;
-    int n_rt;
+    float* gpos;                            // [M] the target term's coefficient (p_pos - 1) for target rows, 0 elsewhere
 };
 
-// gBCE: the sampled op's candidates and buffers (lse2 unused; lse_out takes the per-row loss), g = sigma instead of the softmax's p
+// gBCE: the sampled op's candidates and buffers, g = sigma instead of the softmax's p
 struct GbceArgs : SceArgs {
     static constexpr bool GBCE = true;
+    static constexpr uint32_t SITE = CR_GBCE_SITE;
     float beta;                             // weight of the positive term, (0, 1]
 };
 
@@ -115,6 +109,11 @@ struct ScePopArgs : SceArgs {
     const uint32_t* cdf;                    // [V] the proposal's cumulative masses in units of 2^-32 (device draw), or NULL
     const float* logq;                      // [V] log Q(v); [0] = 0
     float* sb;                              // [N] the samples' base-2 biases -logq[s_j] log2 e
+};
+
+struct CeStatsArgs {
+    float* stats; float* state;
+    int n_rt;
 };
 
 // ---- the streamed block ---------------------------------------------------------------------------------------------------
@@ -186,17 +185,14 @@ __device__ __forceinline__ f32x4 ce_tile_t(const bf8 (&rh)[NK], const bf8 (&rl)[
     return c;
 }
 
-// two score tiles' registers (k slots 8 lg + j: tile j >> 2, register j & 3) as one operand of a k = 32 product
-template <bool SPLIT>
-__device__ __forceinline__ void g_frag(const float (&g)[2][4], bf8& h, bf8& l) {
+// acc[db] += G x (the image read transposed), for the column blocks below D.  G: two score tiles' registers as the A operand of a
+// k = 32 product (k slot 8 lg + j: tile j >> 2, register j & 3); the image's rows in that k order, columns 16 db .. + 15.
+template <int NK, bool SPLIT>
+__device__ __forceinline__ void g_times_img(f32x4 (&acc)[2 * NK], const float (&g)[2][4], const CeImg<(NK + 1) / 2>& img, int D) {
     const float x[8] = {g[0][0], g[0][1], g[0][2], g[0][3], g[1][0], g[1][1], g[1][2], g[1][3]};
-    split8<SPLIT>(x, h, l);
-    if (!SPLIT) l = h;
-}
-
-// acc[db] += G x (the image read transposed: k = image row in g_frag's order, columns 16 db .. + 15), for the column blocks below D
-template <int NK, int NCB, bool SPLIT>
-__device__ __forceinline__ void g_times_img(f32x4 (&acc)[2 * NK], const bf8& gh, const bf8& gl, const CeImg<NCB>& img, int D) {
+    bf8 gh, gl;
+    split8<SPLIT>(x, gh, gl);
+    if (!SPLIT) gl = gh;
 #pragma unroll
     for (int db = 0; db < 2 * NK; ++db) {
         if (16 * db < D) {                                          // uniform: every lane reads (ds_read_b64_tr_b16 wants EXEC full)
@@ -342,136 +338,109 @@ __device__ __forceinline__ float sce_gathered_score(const SceArgs& a, int id, bo
     return sce_diag<NK, SPLIT>(th, tl, bh, bl);
 }
 
-// popularity: what a thread stages for the block of samples j0 .. j0 + 31 -- threads 0 .. 31 the ids, threads 32 .. 63 the biases'
-// bits (one register for both, as the ids alone take)
-__device__ __forceinline__ int sce_pop_stage(const ScePopArgs& a, int j0) {
-    const int j = j0 + (threadIdx.x & (CE_BLK - 1));
-    if (threadIdx.x >= 2 * CE_BLK || j >= a.N) return 0;
-    return threadIdx.x < CE_BLK ? a.sid[j] : __float_as_int(a.sb[j]);
+// ---- the stream ----------------------------------------------------------------------------------------------------------------
+// Rows r0 .. end - 1 of src (`last`: the matrix's last row, blk_issue), with NSIDE words beside row j: w0[j], then the bits of w1[j].
+struct CeStream {
+    const float* src; int64_t ld;
+    int r0, end, last;
+    const int32_t* w0; const float* w1;
+};
+
+// the candidates of a kind: the items 1 .. V-1 of E; the N gathered rows Es with their ids (popularity: and biases) beside them
+template <class A>
+constexpr int CE_NSIDE = A::SAMPLED ? (A::POP ? 2 : 1) : 0;
+template <class A>
+__device__ __forceinline__ CeStream ce_cands(const A& a) {
+    if constexpr (A::POP) return {a.Es, a.D, 0, a.N, a.N - 1, a.sid, a.sb};
+    else if constexpr (A::SAMPLED) return {a.Es, a.D, 0, a.N, a.N - 1, a.sid, nullptr};
+    else return {a.E, a.D, 1, a.V, a.V - 1, nullptr, nullptr};
 }
 
-// ---- the sweep passes (A: CeArgs, SceArgs or ScePopArgs) ------------------------------------------------------------------
-template <class A, int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_ce_lse(A a) {
-    constexpr bool S = A::SAMPLED, P = A::POP;
+// what a thread stages for the block of rows j0 .. j0 + 31: threads 0 .. 31 the first words, threads 32 .. 63 the second (one
+// register either way)
+template <int NSIDE>
+__device__ __forceinline__ int ce_side_stage(const CeStream& s, int j0) {
+    const int j = j0 + (threadIdx.x & (CE_BLK - 1));
+    if (threadIdx.x >= NSIDE * CE_BLK || j >= s.end) return 0;
+    if (NSIDE == 2 && threadIdx.x >= CE_BLK) return __float_as_int(s.w1[j]);
+    return s.w0[j];
+}
+
+// The sweep every pass shares.  Per block: the image and side[32 k + i] = word k of row j0 + i, then tile(j0, tt, c) for the score
+// tiles tt = 0, 1 of image rows 16 tt .. + 15 against the wave's fragments (bh, bl) -- tk_tile: register r of lane (li, lg) = image
+// row 16 tt + 4 lg + r against the wave's row li; SWAP: ce_tile_t -- then block(rd) with the image still resident.
+template <int NK, bool SPLIT, int NSIDE, bool SWAP, class Tile, class Block>
+__device__ __forceinline__ void ce_stream(const CeStream& s, int D, CeImg<(NK + 1) / 2>& img, int* side, const bf8 (&bh)[NK],
+                                          const bf8 (&bl)[NK], Tile&& tile, Block&& block) {
     constexpr int NCB = (NK + 1) / 2;
-    __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
-    __shared__ int s_id[P ? 2 * CE_BLK : CE_BLK];                   // (sampled; popularity: the biases' bits behind the ids)
-    __shared__ float red[3][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const int q = blockIdx.x * 64 + wave * 16 + li;
-    const bool qok = q < a.M;
-    bf8 bh[NK], bl[NK];
-    {
-        float v[NK][8];
-        tk_row_issue<NK>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D);
-        tk_row_finish<NK, SPLIT>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D, bh, bl);
-    }
-    const int pq = qok ? a.pos[q] : 0, nq = (qok && a.neg) ? a.neg[q] : 0;
-    float sp = 0.0f, sn = 0.0f;
-    if constexpr (S) {
-        sp = sce_gathered_score<NK, SPLIT>(a, pq, qok, bh, bl);
-        if (a.neg) {                                                // (uniform: the tile runs with every lane on)
-            const float x = sce_gathered_score<NK, SPLIT>(a, nq, qok, bh, bl);
-            sn = nq != 0 ? x : 0.0f;                                // neg 0: a zero score, as the catalogue's row 0
-        }
-    }
-    // sampled: the target is lane group 0's first candidate (popularity: corrected as every candidate; a padded row reads logq[0] = 0)
-    float tp = sp * CE_LOG2E;
-    if constexpr (P) tp = __builtin_fmaf(sp, CE_LOG2E, -a.logq[pq] * CE_LOG2E);
-    float mx = (S && lg == 0) ? tp : -INFINITY, s_in = (S && lg == 0) ? 1.0f : 0.0f, s_out = 0.0f;
-    const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
-    int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
-    if constexpr (S) { src = a.Es; c0 = 0; end = a.N; }
-    else { src = a.E; c0 = 1; end = a.V; }
-    const int rounds = (end - c0 + CE_BLK - 1) / CE_BLK;
+    const int rounds = (s.end - s.r0 + CE_BLK - 1) / CE_BLK;
     float v[NCB][8];
-    int nid = 0;                                                    // (sampled: the ids of the next block, staged through LDS)
-    blk_issue<NCB>(v, src, a.D, c0, end, end - 1, a.D);
-    if constexpr (P) nid = sce_pop_stage(a, 0);
-    else if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
+    blk_issue<NCB>(v, s.src, s.ld, s.r0, s.end, s.last, D);
+    int nw = ce_side_stage<NSIDE>(s, s.r0);
     for (int rd = 0; rd < rounds; ++rd) {
-        const int j0 = c0 + rd * CE_BLK;
-        blk_store<NCB, SPLIT>(v, img, src, a.D, j0, end, end - 1, a.D);
-        if constexpr (P) { if (threadIdx.x < 2 * CE_BLK) s_id[threadIdx.x] = nid; }
-        else if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
+        const int j0 = s.r0 + rd * CE_BLK;
+        blk_store<NCB, SPLIT>(v, img, s.src, s.ld, j0, s.end, s.last, D);
+        if (NSIDE > 0 && threadIdx.x < NSIDE * CE_BLK) side[threadIdx.x] = nw;
         __syncthreads();
         if (rd + 1 < rounds) {
-            blk_issue<NCB>(v, src, a.D, j0 + CE_BLK, end, end - 1, a.D);
-            if constexpr (P) {
-                nid = sce_pop_stage(a, j0 + CE_BLK);
-            } else if constexpr (S) {
-                const int j = j0 + CE_BLK + threadIdx.x;
-                nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
-            }
+            blk_issue<NCB>(v, s.src, s.ld, j0 + CE_BLK, s.end, s.last, D);
+            nw = ce_side_stage<NSIDE>(s, j0 + CE_BLK);
         }
-        float t[2][4];
-        float bm = -INFINITY;
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
             bf8 ah[NK], al[NK];
             img_rows<NK, NCB, SPLIT>(img, 16 * tt, ah, al);
-            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int jl = 16 * tt + 4 * lg + r;
-                bool ok;
-                if constexpr (S) {
-                    ok = j0 + jl < end && s_id[jl] != pq;           // a sample equal to the target is masked
-                } else {
-                    const int id = j0 + 16 * tt + 4 * lg + r;
-                    ok = id < end;
-                    sp = (ok && id == pq) ? c[r] : sp;
-                    sn = (ok && id == nq) ? c[r] : sn;
-                }
-                if constexpr (P) t[tt][r] = ok ? __builtin_fmaf(c[r], CE_LOG2E, __int_as_float(s_id[CE_BLK + jl])) : -INFINITY;
-                else t[tt][r] = ok ? c[r] * CE_LOG2E : -INFINITY;
-                bm = fmaxf(bm, t[tt][r]);
-            }
+            tile(j0, tt, SWAP ? ce_tile_t<NK, SPLIT>(ah, al, bh, bl) : tk_tile<NK, SPLIT>(ah, al, bh, bl));
         }
-        if (bm > mx) {                                              // (mx = -inf: the sums are 0 and stay 0)
-            const float f = ce_exp2(mx - bm);
-            s_in *= f;
-            s_out *= f;
-            mx = bm;
-        }
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) s_in += t[tt][r] > -INFINITY ? ce_exp2(t[tt][r] - mx) : 0.0f;
-        if ((rd & 63) == 63) {                                      // two-level sum: 64 rounds per inner partial
-            s_out += s_in;
-            s_in = 0.0f;
-        }
+        block(rd);
         __syncthreads();
     }
-    float s = s_out + s_in;
-    // the row's four lane groups: a fixed butterfly, symmetric in the two partners (every lane ends with the same bits)
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) {
-        const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(s, o, 64);
-        const float m2 = fmaxf(mx, mo);
-        s = (mx > -INFINITY ? s * ce_exp2(mx - m2) : 0.0f) + (mo > -INFINITY ? so * ce_exp2(mo - m2) : 0.0f);
-        mx = m2;
-        if constexpr (!S) {
-            sp += __shfl_xor(sp, o, 64);                            // one lane of the four holds the score, the others 0
-            sn += __shfl_xor(sn, o, 64);
+}
+
+// ---- the row kernels' shared pieces ---------------------------------------------------------------------------------------------
+// What lane (li, lg) of a wave holds of batch row q = 64 blockIdx.x + 16 wave + li, beside the row itself as a B fragment (bh, bl)
+struct CeRow {
+    int q, pq, nq;                          // the row, its target, its neg (0: none)
+    bool qok, ist;                          // the row exists; ... and has a target
+    float sp, sn;                           // the scores of pos and neg (catalogue: as the sweep passes them)
+};
+
+template <class A, int NK, bool SPLIT>
+__device__ __forceinline__ void ce_row(const A& a, CeRow& w, bf8 (&bh)[NK], bf8 (&bl)[NK]) {
+    w.q = blockIdx.x * 64 + (threadIdx.x >> 6) * 16 + (threadIdx.x & 15);
+    w.qok = w.q < a.M;
+    float v[NK][8];
+    tk_row_issue<NK>(v, a.h, a.ldh, w.q, w.qok, w.q == a.M - 1, a.D);
+    tk_row_finish<NK, SPLIT>(v, a.h, a.ldh, w.q, w.qok, w.q == a.M - 1, a.D, bh, bl);
+    w.pq = w.qok ? a.pos[w.q] : 0;
+    w.ist = w.qok && w.pq != 0;
+    w.nq = 0;
+    w.sp = w.sn = 0.0f;
+}
+
+// (after ce_row) neg, and for the sampled kinds the scores of E[pos] and E[neg]: diagonal tiles against the wave's own rows
+template <class A, int NK, bool SPLIT>
+__device__ __forceinline__ void ce_row_scores(const A& a, CeRow& w, const bf8 (&bh)[NK], const bf8 (&bl)[NK]) {
+    w.nq = (w.qok && a.neg) ? a.neg[w.q] : 0;
+    if constexpr (A::SAMPLED) {
+        w.sp = sce_gathered_score<NK, SPLIT>(a, w.pq, w.qok, bh, bl);
+        if (a.neg) {                                                // (uniform: the tile runs with every lane on)
+            const float x = sce_gathered_score<NK, SPLIT>(a, w.nq, w.qok, bh, bl);
+            w.sn = w.nq != 0 ? x : 0.0f;                            // neg 0: a zero score, as the catalogue's row 0
         }
     }
-    const float l2 = mx + __log2f(s);
-    const bool ist = qok && pq != 0;
+}
+
+// The row tile's loss / AUC / target sums to stats: l, the loss of the lane's row, counts once per target row (lane group 0)
+template <class A>
+__device__ __forceinline__ void ce_tile_stats(const A& a, const CeRow& w, float l, float (&red)[3][4]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float lr = 0.0f, ar = 0.0f, nr = 0.0f;
-    if (qok && lg == 0) {
-        a.lse2[q] = l2;
-        // sampled: relative to the target's own base-2 score, so a row whose every sample is a hit gets l = 0 and p_pos - 1 = 0 exactly
-        if constexpr (S) a.gpos[q] = ist ? ce_exp2(tp - l2) - 1.0f : 0.0f;
-        if (a.lse_out) a.lse_out[q] = l2 * CE_LN2;
-        if (ist) {
-            lr = S ? (l2 - tp) * CE_LN2 : l2 * CE_LN2 - sp;
-            const float dlt = sp - sn;                              // neg 0 (or none): row 0 reads as zeros
-            ar = a.neg ? ((dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? 0.0f : 0.5f)) : 0.0f;
-            nr = 1.0f;
-        }
+    if (w.ist && lane < 16) {
+        lr = l;
+        const float dlt = w.sp - w.sn;                              // neg 0 (or none): row 0 reads as zeros
+        ar = a.neg ? ((dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? 0.0f : 0.5f)) : 0.0f;
+        nr = 1.0f;
     }
     lr = wave_sum(lr);
     ar = wave_sum(ar);
@@ -481,10 +450,112 @@ __global__ __launch_bounds__(256) void k_ce_lse(A a) {
     if (threadIdx.x < 3) a.stats[blockIdx.x * 4 + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
 }
 
+// dh from acc[db] register r: row 16 wave + 4 lg + r of the tile, column 16 db + li.  Sampled kinds: plus the target term
+// gpos(r, row) E[pos] in fp32 (gpos is asked for every r with all lanes on, before the row is known to exist).
+template <class A, int NK, class Gpos>
+__device__ __forceinline__ void ce_store_dh(const A& a, const f32x4 (&acc)[2 * NK], Gpos&& gpos) {
+    const int wave = threadIdx.x >> 6, li = threadIdx.x & 15, lg = (threadIdx.x & 63) >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
+        const float gp = gpos(r, row);
+        if (row >= a.M) continue;
+        const int pr = A::SAMPLED ? a.pos[row] : 0;
+        const float* er = a.E + (int64_t)pr * a.D;
+#pragma unroll
+        for (int db = 0; db < 2 * NK; ++db) {
+            const int col = 16 * db + li;
+            if (col >= a.D) continue;
+            if constexpr (A::SAMPLED) a.dh[(int64_t)row * a.ldd + col] = pr != 0 ? __builtin_fmaf(gp, er[col], acc[db][r]) : 0.0f;
+            else a.dh[(int64_t)row * a.ldd + col] = acc[db][r];
+        }
+    }
+}
+
+// ---- the passes (A: CeArgs, SceArgs, ScePopArgs or GbceArgs) -------------------------------------------------------------------
+template <class A, int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_ce_lse(A a) {
+    constexpr bool S = A::SAMPLED, P = A::POP;
+    constexpr int NSIDE = CE_NSIDE<A>;
+    __shared__ __attribute__((aligned(16))) CeImg<(NK + 1) / 2> img;
+    __shared__ int s_id[NSIDE ? NSIDE * CE_BLK : 1];                // (sampled: the block's ids; popularity: the biases' bits behind)
+    __shared__ float red[3][4];
+    const int lg = (threadIdx.x & 63) >> 4;
+    CeRow w;
+    bf8 bh[NK], bl[NK];
+    ce_row<A, NK, SPLIT>(a, w, bh, bl);
+    ce_row_scores<A, NK, SPLIT>(a, w, bh, bl);
+    // sampled: the target is lane group 0's first candidate (popularity: corrected as every candidate; a padded row reads logq[0] = 0)
+    float tp = w.sp * CE_LOG2E;
+    if constexpr (P) tp = __builtin_fmaf(w.sp, CE_LOG2E, -a.logq[w.pq] * CE_LOG2E);
+    float mx = (S && lg == 0) ? tp : -INFINITY, s_in = (S && lg == 0) ? 1.0f : 0.0f, s_out = 0.0f;
+    const CeStream cd = ce_cands(a);
+    float t[2][4];
+    float bm = -INFINITY;
+    ce_stream<NK, SPLIT, NSIDE, false>(
+        cd, a.D, img, s_id, bh, bl,
+        [&](int j0, int tt, const f32x4& c) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int jl = 16 * tt + 4 * lg + r;
+                bool ok;
+                if constexpr (S) {
+                    ok = (j0 + jl < cd.end) & (s_id[jl] != w.pq);   // a sample equal to the target is masked (&, here and in
+                                                                    //   dh and gBCE: no branch round the LDS read of the id)
+                } else {
+                    const int id = j0 + jl;
+                    ok = id < cd.end;
+                    w.sp = (ok && id == w.pq) ? c[r] : w.sp;
+                    w.sn = (ok && id == w.nq) ? c[r] : w.sn;
+                }
+                if constexpr (P) t[tt][r] = ok ? __builtin_fmaf(c[r], CE_LOG2E, __int_as_float(s_id[CE_BLK + jl])) : -INFINITY;
+                else t[tt][r] = ok ? c[r] * CE_LOG2E : -INFINITY;
+                bm = fmaxf(bm, t[tt][r]);
+            }
+        },
+        [&](int rd) {
+            if (bm > mx) {                                          // (mx = -inf: the sums are 0 and stay 0)
+                const float f = ce_exp2(mx - bm);
+                s_in *= f;
+                s_out *= f;
+                mx = bm;
+            }
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s_in += t[tt][r] > -INFINITY ? ce_exp2(t[tt][r] - mx) : 0.0f;
+            if ((rd & 63) == 63) {                                  // two-level sum: 64 rounds per inner partial
+                s_out += s_in;
+                s_in = 0.0f;
+            }
+            bm = -INFINITY;
+        });
+    float s = s_out + s_in;
+    // the row's four lane groups: a fixed butterfly, symmetric in the two partners (every lane ends with the same bits)
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+        const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(s, o, 64);
+        const float m2 = fmaxf(mx, mo);
+        s = (mx > -INFINITY ? s * ce_exp2(mx - m2) : 0.0f) + (mo > -INFINITY ? so * ce_exp2(mo - m2) : 0.0f);
+        mx = m2;
+        if constexpr (!S) {
+            w.sp += __shfl_xor(w.sp, o, 64);                        // one lane of the four holds the score, the others 0
+            w.sn += __shfl_xor(w.sn, o, 64);
+        }
+    }
+    const float l2 = mx + __log2f(s);
+    if (w.qok && lg == 0) {
+        a.lse2[w.q] = l2;
+        // sampled: relative to the target's own base-2 score, so a row whose every sample is a hit gets l = 0 and p_pos - 1 = 0 exactly
+        if constexpr (S) a.gpos[w.q] = w.ist ? ce_exp2(tp - l2) - 1.0f : 0.0f;
+        if (a.lse_out) a.lse_out[w.q] = l2 * CE_LN2;
+    }
+    ce_tile_stats(a, w, S ? (l2 - tp) * CE_LN2 : l2 * CE_LN2 - w.sp, red);
+}
+
 // state[0..2] += the row tiles' sums (fixed order), then the snapshot [8..11] the head kernels take (castrec.h, state block).  One
 // workgroup adds and snapshots, so it is the last piece of work by construction; the ticket [12] is left re-armed (0).
-template <class A>
-__global__ __launch_bounds__(64) void k_ce_stats(A a) {
+__global__ __launch_bounds__(64) void k_ce_stats(CeStatsArgs a) {
     const int lane = threadIdx.x;
     float s[3] = {0.0f, 0.0f, 0.0f};
     for (int i = lane; i < a.n_rt; i += 64)
@@ -504,227 +575,101 @@ __global__ __launch_bounds__(64) void k_ce_stats(A a) {
     }
 }
 
+// (NK = 1: held to five waves per SIMD -- the branch-free g below would otherwise cost the sampled kinds' bf16x3 kernels their fifth)
 template <class A, int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_ce_dh(A a) {
+__global__ __launch_bounds__(256, NK == 1 ? 5 : 1) void k_ce_dh(A a) {
     constexpr bool S = A::SAMPLED, P = A::POP;
-    constexpr int NCB = (NK + 1) / 2;
-    __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
-    __shared__ int s_id[P ? 2 * CE_BLK : CE_BLK];                   // (sampled; popularity: the biases' bits behind the ids)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const int q = blockIdx.x * 64 + wave * 16 + li;
-    const bool qok = q < a.M;
+    constexpr int NSIDE = CE_NSIDE<A>;
+    __shared__ __attribute__((aligned(16))) CeImg<(NK + 1) / 2> img;
+    __shared__ int s_id[NSIDE ? NSIDE * CE_BLK : 1];                // (sampled: the block's ids; popularity: the biases' bits behind)
+    const int lg = (threadIdx.x & 63) >> 4;
+    CeRow w;
     bf8 bh[NK], bl[NK];
-    {
-        float v[NK][8];
-        tk_row_issue<NK>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D);
-        tk_row_finish<NK, SPLIT>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D, bh, bl);
-    }
-    const int pq = qok ? a.pos[q] : 0;
-    const bool ist = qok && pq != 0;
-    const float l2 = qok ? a.lse2[q] : 0.0f;
+    ce_row<A, NK, SPLIT>(a, w, bh, bl);
+    const float l2 = w.qok ? a.lse2[w.q] : 0.0f;
     f32x4 acc[2 * NK];
 #pragma unroll
     for (int i = 0; i < 2 * NK; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
-    int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
-    if constexpr (S) { src = a.Es; c0 = 0; end = a.N; }
-    else { src = a.E; c0 = 1; end = a.V; }
-    const int rounds = (end - c0 + CE_BLK - 1) / CE_BLK;
-    float v[NCB][8];
-    int nid = 0;                                                    // (sampled: the ids of the next block, staged through LDS)
-    blk_issue<NCB>(v, src, a.D, c0, end, end - 1, a.D);
-    if constexpr (P) nid = sce_pop_stage(a, 0);
-    else if constexpr (S) if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
-    for (int rd = 0; rd < rounds; ++rd) {
-        const int j0 = c0 + rd * CE_BLK;
-        blk_store<NCB, SPLIT>(v, img, src, a.D, j0, end, end - 1, a.D);
-        if constexpr (P) { if (threadIdx.x < 2 * CE_BLK) s_id[threadIdx.x] = nid; }
-        else if constexpr (S) if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
-        __syncthreads();
-        if (rd + 1 < rounds) {
-            blk_issue<NCB>(v, src, a.D, j0 + CE_BLK, end, end - 1, a.D);
-            if constexpr (P) {
-                nid = sce_pop_stage(a, j0 + CE_BLK);
-            } else if constexpr (S) {
-                const int j = j0 + CE_BLK + threadIdx.x;
-                nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
-            }
-        }
-        float g[2][4];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            bf8 ah[NK], al[NK];
-            img_rows<NK, NCB, SPLIT>(img, 16 * tt, ah, al);
-            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+    const CeStream cd = ce_cands(a);
+    float g[2][4];
+    ce_stream<NK, SPLIT, NSIDE, false>(
+        cd, a.D, img, s_id, bh, bl,
+        [&](int j0, int tt, const f32x4& c) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                if constexpr (P) {
-                    const int jl = 16 * tt + 4 * lg + r;
-                    g[tt][r] = (ist && j0 + jl < end && s_id[jl] != pq) ? ce_pb(c[r], __int_as_float(s_id[CE_BLK + jl]), l2) : 0.0f;
-                } else if constexpr (S) {
-                    const int jl = 16 * tt + 4 * lg + r;
-                    g[tt][r] = (ist && j0 + jl < end && s_id[jl] != pq) ? ce_p(c[r], l2) : 0.0f;     // a hit is masked
-                } else {
-                    const int id = j0 + 16 * tt + 4 * lg + r;
-                    g[tt][r] = (ist && id < end) ? ce_g(c[r], l2, id == pq) : 0.0f;
-                }
+                const int jl = 16 * tt + 4 * lg + r, id = j0 + jl;  // (catalogue: the item's id)
+                bool live = w.ist && id < cd.end;
+                if constexpr (S) live = live & (s_id[jl] != w.pq);  // a hit is masked
+                float p;                                            // (computed for every score: selects, no branches)
+                if constexpr (P) p = ce_pb(c[r], __int_as_float(s_id[CE_BLK + jl]), l2);
+                else if constexpr (S) p = ce_p(c[r], l2);
+                else p = ce_g(c[r], l2, id == w.pq);
+                g[tt][r] = live ? p : 0.0f;
             }
-        }
-        bf8 gh, gl;
-        g_frag<SPLIT>(g, gh, gl);
-        g_times_img<NK, NCB, SPLIT>(acc, gh, gl, img, a.D);
-        __syncthreads();
-    }
-    // acc[db] register r: row 16 wave + 4 lg + r of the tile, column 16 db + li
-    if constexpr (S) {
-        // plus the target term (p_pos - 1) E_pos
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
-            if (row >= a.M) continue;
-            const int pr = a.pos[row];
-            const float gp = a.gpos[row];
-            const float* er = a.E + (int64_t)pr * a.D;
-#pragma unroll
-            for (int db = 0; db < 2 * NK; ++db) {
-                const int col = 16 * db + li;
-                if (col < a.D) a.dh[(int64_t)row * a.ldd + col] = pr != 0 ? __builtin_fmaf(gp, er[col], acc[db][r]) : 0.0f;
-            }
-        }
-    } else {
-#pragma unroll
-        for (int db = 0; db < 2 * NK; ++db) {
-            const int col = 16 * db + li;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
-                if (row < a.M && col < a.D) a.dh[(int64_t)row * a.ldd + col] = acc[db][r];
-            }
-        }
-    }
+        },
+        [&](int) { g_times_img<NK, SPLIT>(acc, g, img, a.D); });
+    ce_store_dh<A, NK>(a, acc, [&](int, int row) {
+        if constexpr (S) return row < a.M ? a.gpos[row] : 0.0f;
+        else return 0.0f;
+    });
 }
 
-// gBCE: loss and dh from one sweep of the candidates (the sweep of k_ce_dh<SceArgs>, the prologue and epilogue of k_ce_lse<SceArgs>)
+// gBCE: loss and dh from one sweep of the candidates
 template <int NK, bool SPLIT>
 __global__ __launch_bounds__(256) void k_gbce_row(GbceArgs a) {
-    constexpr int NCB = (NK + 1) / 2;
-    __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
+    __shared__ __attribute__((aligned(16))) CeImg<(NK + 1) / 2> img;
     __shared__ int s_id[CE_BLK];
     __shared__ float red[3][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const int q = blockIdx.x * 64 + wave * 16 + li;
-    const bool qok = q < a.M;
+    const int lg = (threadIdx.x & 63) >> 4;
+    CeRow w;
     bf8 bh[NK], bl[NK];
-    {
-        float v[NK][8];
-        tk_row_issue<NK>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D);
-        tk_row_finish<NK, SPLIT>(v, a.h, a.ldh, q, qok, q == a.M - 1, a.D, bh, bl);
-    }
-    const int pq = qok ? a.pos[q] : 0, nq = (qok && a.neg) ? a.neg[q] : 0;
-    const bool ist = qok && pq != 0;
-    const float sp = sce_gathered_score<NK, SPLIT>(a, pq, qok, bh, bl);
-    float sn = 0.0f;
-    if (a.neg) {                                                    // (uniform: the tile runs with every lane on)
-        const float x = sce_gathered_score<NK, SPLIT>(a, nq, qok, bh, bl);
-        sn = nq != 0 ? x : 0.0f;                                    // neg 0: a zero score, as the catalogue's row 0
-    }
+    ce_row<GbceArgs, NK, SPLIT>(a, w, bh, bl);
+    ce_row_scores<GbceArgs, NK, SPLIT>(a, w, bh, bl);
     f32x4 acc[2 * NK];
 #pragma unroll
     for (int i = 0; i < 2 * NK; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
     float ls = 0.0f;                                                // softplus of this lane's candidates, in sweep order
-    const int end = a.N;
-    const int rounds = (end + CE_BLK - 1) / CE_BLK;
-    float v[NCB][8];
-    int nid = 0;                                                    // the ids of the next block, staged through LDS
-    blk_issue<NCB>(v, a.Es, a.D, 0, end, end - 1, a.D);
-    if (threadIdx.x < CE_BLK && (int)threadIdx.x < a.N) nid = a.sid[threadIdx.x];
-    for (int rd = 0; rd < rounds; ++rd) {
-        const int j0 = rd * CE_BLK;
-        blk_store<NCB, SPLIT>(v, img, a.Es, a.D, j0, end, end - 1, a.D);
-        if (threadIdx.x < CE_BLK) s_id[threadIdx.x] = nid;
-        __syncthreads();
-        if (rd + 1 < rounds) {
-            blk_issue<NCB>(v, a.Es, a.D, j0 + CE_BLK, end, end - 1, a.D);
-            const int j = j0 + CE_BLK + threadIdx.x;
-            nid = (threadIdx.x < CE_BLK && j < a.N) ? a.sid[j] : 0;
-        }
-        float g[2][4];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            bf8 ah[NK], al[NK];
-            img_rows<NK, NCB, SPLIT>(img, 16 * tt, ah, al);
-            const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+    const CeStream cd = ce_cands(a);
+    float g[2][4];
+    ce_stream<NK, SPLIT, 1, false>(
+        cd, a.D, img, s_id, bh, bl,
+        [&](int j0, int tt, const f32x4& c) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int jl = 16 * tt + 4 * lg + r;
-                const bool live = ist && j0 + jl < end && s_id[jl] != pq;       // a hit is masked
+                const bool live = (w.ist && j0 + jl < cd.end) & (s_id[jl] != w.pq);        // a hit is masked
                 const float e = gb_e(c[r]);
                 g[tt][r] = live ? gb_sigma(c[r], e) : 0.0f;
                 ls += live ? gb_softplus(c[r], e) : 0.0f;
             }
-        }
-        if (a.dh) {
-            bf8 gh, gl;
-            g_frag<SPLIT>(g, gh, gl);
-            g_times_img<NK, NCB, SPLIT>(acc, gh, gl, img, a.D);
-        }
-        __syncthreads();
-    }
+        },
+        [&](int) { if (a.dh) g_times_img<NK, SPLIT>(acc, g, img, a.D); });
     // the row's four lane groups: a butterfly symmetric in the two partners (every lane ends with the same bits)
     ls += __shfl_xor(ls, 16, 64);
     ls += __shfl_xor(ls, 32, 64);
     // the target: beta softplus(-z_pos), coefficient beta (sigma(z_pos) - 1) = -beta sigma(-z_pos)
-    const float et = gb_e(sp);
-    const float gp = ist ? -a.beta * gb_sigma(-sp, et) : 0.0f;
-    const float l = ist ? __builtin_fmaf(a.beta, gb_softplus(-sp, et), ls) : 0.0f;
-    float lr = 0.0f, ar = 0.0f, nr = 0.0f;
-    if (qok && lg == 0) {
-        a.gpos[q] = gp;
-        if (a.lse_out) a.lse_out[q] = l;
-        if (ist) {
-            lr = l;
-            const float dlt = sp - sn;                              // neg 0 (or none): row 0 reads as zeros
-            ar = a.neg ? ((dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? 0.0f : 0.5f)) : 0.0f;
-            nr = 1.0f;
-        }
+    const float et = gb_e(w.sp);
+    const float gp = w.ist ? -a.beta * gb_sigma(-w.sp, et) : 0.0f;
+    const float l = w.ist ? __builtin_fmaf(a.beta, gb_softplus(-w.sp, et), ls) : 0.0f;
+    if (w.qok && lg == 0) {
+        a.gpos[w.q] = gp;
+        if (a.lse_out) a.lse_out[w.q] = l;
     }
-    lr = wave_sum(lr);
-    ar = wave_sum(ar);
-    nr = wave_sum(nr);
-    if (lane == 0) { red[0][wave] = lr; red[1][wave] = ar; red[2][wave] = nr; }
-    __syncthreads();
-    if (threadIdx.x < 3) a.stats[blockIdx.x * 4 + threadIdx.x] = ((red[threadIdx.x][0] + red[threadIdx.x][1]) + red[threadIdx.x][2]) + red[threadIdx.x][3];
+    ce_tile_stats(a, w, l, red);
     if (!a.dh) return;
-    // acc[db] register r: row 16 wave + 4 lg + r of the tile (its gpos sits in lane 4 lg + r), column 16 db + li; plus gpos E_pos
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const float gpr = __shfl(gp, 4 * lg + r, 64);
-        const int row = blockIdx.x * 64 + wave * 16 + 4 * lg + r;
-        if (row >= a.M) continue;
-        const int pr = a.pos[row];
-        const float* er = a.E + (int64_t)pr * a.D;
-#pragma unroll
-        for (int db = 0; db < 2 * NK; ++db) {
-            const int col = 16 * db + li;
-            if (col < a.D) a.dh[(int64_t)row * a.ldd + col] = pr != 0 ? __builtin_fmaf(gpr, er[col], acc[db][r]) : 0.0f;
-        }
-    }
+    ce_store_dh<GbceArgs, NK>(a, acc, [&](int r, int) { return __shfl(gp, 4 * lg + r, 64); });     // (row 4 lg + r's gpos: lane 4 lg + r)
 }
 
 template <class A, int NK, bool SPLIT>
 __global__ __launch_bounds__(256) void k_ce_de(A a) {
-    constexpr bool S = A::SAMPLED, G = A::GBCE, P = A::POP;         // (gBCE: no per-row statistic, so no s_l2)
-    constexpr int NCB = (NK + 1) / 2;
-    __shared__ __attribute__((aligned(16))) CeImg<NCB> img;
-    __shared__ float s_l2[G ? 1 : CE_BLK];
-    __shared__ int s_pos[CE_BLK];
+    constexpr bool S = A::SAMPLED, G = A::GBCE, P = A::POP;
+    constexpr int NSIDE = G ? 1 : 2;                                // (gBCE: no per-row statistic, so no lse2 beside pos)
+    __shared__ __attribute__((aligned(16))) CeImg<(NK + 1) / 2> img;
+    __shared__ int s_row[NSIDE * CE_BLK];                           // the block's pos; the bits of its lse2 behind
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
-    const float* src;                                               // the candidates: rows c0 .. end - 1 of src (catalogue: the
-    int c0, end;                                                    // items 1 .. V-1 of E; sampled: the N gathered rows Es)
-    if constexpr (S) { src = a.Es; c0 = 0; end = a.N; }
-    else { src = a.E; c0 = 1; end = a.V; }
-    const int j = c0 + blockIdx.x * 64 + wave * 16 + li;
-    const bool jok = j < end;
+    const CeStream cd = ce_cands(a);
+    const int j = cd.r0 + blockIdx.x * 64 + wave * 16 + li;
+    const bool jok = j < cd.end;
     int id = j;                                                     // the candidate's item id
     if constexpr (S) id = jok ? a.sid[j] : -1;
     float bj = 0.0f;                                                // (popularity: the candidate's base-2 bias)
@@ -732,71 +677,38 @@ __global__ __launch_bounds__(256) void k_ce_de(A a) {
     bf8 bh[NK], bl[NK];
     {
         float v[NK][8];
-        tk_row_issue<NK>(v, src, a.D, j, jok, j == end - 1, a.D);
-        tk_row_finish<NK, SPLIT>(v, src, a.D, j, jok, j == end - 1, a.D, bh, bl);
+        tk_row_issue<NK>(v, cd.src, a.D, j, jok, j == cd.last, a.D);
+        tk_row_finish<NK, SPLIT>(v, cd.src, a.D, j, jok, j == cd.last, a.D, bh, bl);
     }
     const int rb = blockIdx.y * a.rpp, re = min(a.M, rb + a.rpp);
     f32x4 acc[2 * NK];
 #pragma unroll
     for (int i = 0; i < 2 * NK; ++i) acc[i] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    const int rounds = (re - rb + CE_BLK - 1) / CE_BLK;
-    float v[NCB][8];
-    int npos = 0;
-    float nl2 = 0.0f;
-    blk_issue<NCB>(v, a.h, a.ldh, rb, re, a.M - 1, a.D);
-    if (threadIdx.x < CE_BLK && rb + (int)threadIdx.x < re) {
-        npos = a.pos[rb + threadIdx.x];
-        if constexpr (!G) nl2 = a.lse2[rb + threadIdx.x];
-    }
-    for (int rd = 0; rd < rounds; ++rd) {
-        const int r0 = rb + rd * CE_BLK;
-        blk_store<NCB, SPLIT>(v, img, a.h, a.ldh, r0, re, a.M - 1, a.D);
-        if (threadIdx.x < CE_BLK) {
-            s_pos[threadIdx.x] = npos;
-            if constexpr (!G) s_l2[threadIdx.x] = nl2;
-        }
-        __syncthreads();
-        if (rd + 1 < rounds) {
-            blk_issue<NCB>(v, a.h, a.ldh, r0 + CE_BLK, re, a.M - 1, a.D);
-            const int r = r0 + CE_BLK + threadIdx.x;
-            npos = 0;
-            nl2 = 0.0f;
-            if (threadIdx.x < CE_BLK && r < re) {
-                npos = a.pos[r];
-                if constexpr (!G) nl2 = a.lse2[r];
-            }
-        }
-        float g[2][4];
-#pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-            bf8 ah[NK], al[NK];
-            img_rows<NK, NCB, SPLIT>(img, 16 * tt, ah, al);
-            const f32x4 c = ce_tile_t<NK, SPLIT>(ah, al, bh, bl);
+    float g[2][4];
+    ce_stream<NK, SPLIT, NSIDE, true>(
+        CeStream{a.h, a.ldh, rb, re, a.M - 1, a.pos, a.lse2}, a.D, img, s_row, bh, bl,
+        [&](int, int tt, const f32x4& c) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int lr = 16 * tt + 4 * lg + r;
-                const int pr = s_pos[lr];
-                if constexpr (P) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_pb(c[r], bj, s_l2[lr]) : 0.0f;
+                const int pr = s_row[lr];
+                if constexpr (P) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_pb(c[r], bj, __int_as_float(s_row[CE_BLK + lr])) : 0.0f;
                 else if constexpr (G) g[tt][r] = (jok && pr != 0 && pr != id) ? gb_sigma(c[r], gb_e(c[r])) : 0.0f;
-                else if constexpr (S) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_p(c[r], s_l2[lr]) : 0.0f;
-                else g[tt][r] = (jok && pr != 0) ? ce_g(c[r], s_l2[lr], pr == id) : 0.0f;
+                else if constexpr (S) g[tt][r] = (jok && pr != 0 && pr != id) ? ce_p(c[r], __int_as_float(s_row[CE_BLK + lr])) : 0.0f;
+                else g[tt][r] = (jok && pr != 0) ? ce_g(c[r], __int_as_float(s_row[CE_BLK + lr]), pr == id) : 0.0f;
             }
-        }
-        bf8 gh, gl;
-        g_frag<SPLIT>(g, gh, gl);
-        g_times_img<NK, NCB, SPLIT>(acc, gh, gl, img, a.D);
-        __syncthreads();
-    }
+        },
+        [&](int) { g_times_img<NK, SPLIT>(acc, g, img, a.D); });
     // acc[db] register r: candidate 16 wave + 4 lg + r of the workgroup's 64, column 16 db + li
 #pragma unroll
     for (int db = 0; db < 2 * NK; ++db) {
         const int col = 16 * db + li;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const int jr = c0 + blockIdx.x * 64 + wave * 16 + 4 * lg + r;
-            if (jr < end && col < a.D) {
+            const int jr = cd.r0 + blockIdx.x * 64 + wave * 16 + 4 * lg + r;
+            if (jr < cd.end && col < a.D) {
                 if (!S && a.parts == 1) a.tg[(int64_t)jr * a.D + col] += acc[db][r];
-                else a.part[((int64_t)blockIdx.y * end + jr) * a.D + col] = acc[db][r];
+                else a.part[((int64_t)blockIdx.y * cd.end + jr) * a.D + col] = acc[db][r];
             }
         }
     }
@@ -847,8 +759,8 @@ struct CeGeom {
     int NK, n_rt, n_ct, parts, rpp;         // n_ct: the de pass's workgroups of 64 candidates
 };
 
-// Candidates c0 .. end - 1 (cands()).  The de pass: about 512 workgroups of (64 candidates x a part of the rows) where the candidates
-// are few; its partial sums are at most max_parts slices of `end` rows, parts x end <= part_rows.
+// Candidates c0 .. end - 1 (ce_cands).  The de pass: about 512 workgroups of (64 candidates x a part of the rows) where the
+// candidates are few; its partial sums are at most max_parts slices of `end` rows, parts x end <= part_rows.
 bool ce_geometry(int M, int c0, int end, int D, int max_parts, int part_rows, CeGeom& g) {
     if (M < 1 || end <= c0 || D < 8 || D > 256) return false;
     g.NK = tk_nk(D);
@@ -871,60 +783,91 @@ size_t ce_workspace(int M, int V, int D, CeGeom& g) {
 
 size_t sce_part_rows(int N) { return std::min<size_t>((size_t)SCE_MAX_PARTS * N, std::max<size_t>(N, SCE_PART_ROWS)); }
 
-// sampled workspace: [sid | nxt | head: N ints each | Es N x D | lse2 M | gpos M | row-tile sums n_rt x 4 | de parts min(64 N, 65536)
-// x D | the samples' biases N (popularity proposal)] (the parts section is sized by N alone, so the total never decreases as M or N
-// grows).  0: an unsupported shape.
-size_t sce_workspace(int M, int N, int D, CeGeom& g) {
+// sampled workspace: [sid | nxt | head: N ints each | Es N x D | lse2 M (softmax) | gpos M | row-tile sums n_rt x 4 | de parts
+// min(64 N, 65536) x D | the samples' biases N (softmax: the popularity proposal's)] (the parts section is sized by N alone, so the
+// total never decreases as M or N grows).  softmax: cr_sampled_ce; gBCE has neither lse2 nor biases.  0: an unsupported shape.
+size_t sce_workspace(int M, int N, int D, bool softmax, CeGeom& g) {
     if (N > CR_SCE_MAX_SAMPLES || !ce_geometry(M, 0, N, D, SCE_MAX_PARTS, SCE_PART_ROWS, g)) return 0;
-    return 3 * cr_align256(4 * (size_t)N) + cr_align256(4 * (size_t)N * D) + 2 * cr_align256(4 * (size_t)M) +
-           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D) + cr_align256(4 * (size_t)N);
+    return 3 * cr_align256(4 * (size_t)N) + cr_align256(4 * (size_t)N * D) + (softmax ? 2 : 1) * cr_align256(4 * (size_t)M) +
+           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D) + (softmax ? cr_align256(4 * (size_t)N) : 0);
 }
 
-// gBCE workspace: the sampled one without lse2
-size_t gbce_workspace(int M, int N, int D, CeGeom& g) {
-    if (N > CR_SCE_MAX_SAMPLES || !ce_geometry(M, 0, N, D, SCE_MAX_PARTS, SCE_PART_ROWS, g)) return 0;
-    return 3 * cr_align256(4 * (size_t)N) + cr_align256(4 * (size_t)N * D) + cr_align256(4 * (size_t)M) +
-           cr_align256(16 * (size_t)g.n_rt) + cr_align256(4 * sce_part_rows(N) * D);
+// What the three entry points check alike, in two steps: the descriptor's fields before an op's own checks, the workspace after them
+// (the order of the checks is the order every op has had).  `items`: what the op does with the table's rows; n: the sampled kinds' N.
+template <class Desc>
+int ce_check_desc(const char* op, const char* items, const Desc* d, const int* n = nullptr) {
+    CR_REQUIRE(d, "%s: NULL descriptor", op);
+    CR_REQUIRE(d->seq_emb && d->table && d->pos && d->state, "%s: NULL seq_emb, table, pos or state", op);
+    CR_REQUIRE(d->D >= 8 && d->D <= 256, "%s: D=%d outside 8 .. 256", op, d->D);
+    CR_REQUIRE(d->V >= 2, "%s: V=%d < 2 (row 0 is padding: no item to %s)", op, d->V, items);
+    CR_REQUIRE(d->M >= 1, "%s: M=%d <= 0", op, d->M);
+    CR_REQUIRE(!n || (*n >= 1 && *n <= CR_SCE_MAX_SAMPLES), "%s: N=%d outside 1 .. %d", op, n ? *n : 0, CR_SCE_MAX_SAMPLES);
+    CR_REQUIRE(d->ld >= d->D, "%s: ld=%d < D=%d", op, d->ld, d->D);
+    CR_REQUIRE(!d->d_seq_emb || d->ldd >= d->D, "%s: ldd=%d < D=%d", op, d->ldd, d->D);
+    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
+               "%s: unknown precision %d", op, d->precision);
+    return CR_OK;
+}
+template <class Desc>
+int ce_check_workspace(const char* op, const Desc* d, size_t need) {
+    CR_REQUIRE(need, "%s: unsupported shape", op);
+    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "%s: workspace of %zu bytes, %s_workspace says %zu", op,
+               d->workspace ? d->workspace_bytes : (size_t)0, op, need);
+    return CR_OK;
+}
+
+// the fields every kind has, from a descriptor; out: the optional per-row output
+template <class Desc>
+void ce_fill(CeBase& a, const Desc* d, float* out, const CeGeom& g) {
+    a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
+    a.M = d->M; a.D = d->D; a.V = d->V;
+    a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
+    a.rpp = g.rpp; a.parts = g.parts;
+    a.lse_out = out; a.state = d->state; a.n_rt = g.n_rt;
+}
+
+// ... and the sampled kinds' own, carved from the workspace in sce_workspace's order.  Returns the biases' place.
+template <class Desc>
+float* sce_fill(SceArgs& a, const Desc* d, float* out, bool softmax, const CeGeom& g) {
+    ce_fill(a, d, out, g);
+    a.N = d->N;
+    a.samples = d->samples; a.seed = d->seed; a.step = d->step; a.samples_out = d->samples_out;
+    unsigned char* w = static_cast<unsigned char*>(d->workspace);
+    auto take = [&](size_t bytes) { void* p = w; w += cr_align256(bytes); return p; };
+    a.sid = static_cast<int32_t*>(take(4 * (size_t)d->N));
+    a.nxt = static_cast<int32_t*>(take(4 * (size_t)d->N));
+    a.head = static_cast<int32_t*>(take(4 * (size_t)d->N));
+    a.Es = static_cast<float*>(take(4 * (size_t)d->N * d->D));
+    a.lse2 = softmax ? static_cast<float*>(take(4 * (size_t)d->M)) : nullptr;
+    a.gpos = static_cast<float*>(take(4 * (size_t)d->M));
+    a.stats = static_cast<float*>(take(16 * (size_t)g.n_rt));
+    a.part = static_cast<float*>(take(4 * sce_part_rows(d->N) * d->D));
+    return reinterpret_cast<float*>(w);
 }
 
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>(2048, (n + 255) / 256)); }
 
+// The launches of one op.  Sampled: eight (ids, dedup, lse, stats, dh, de, scatter, tgt); gBCE: seven (one row kernel for lse and dh).
 template <class A, int NK, bool SPLIT>
 void ce_launch(const A& a, const CeGeom& g, hipStream_t st) {
     constexpr bool S = A::SAMPLED;
     if constexpr (S) {
         if constexpr (A::POP) hipLaunchKernelGGL(k_sce_ids_pop, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_sce_ids<CR_SCE_SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_sce_ids<A::SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, a);
         if (a.tg) hipLaunchKernelGGL(k_sce_dedup, dim3((a.N + 255) / 256), dim3(256), 0, st, a);
     }
-    hipLaunchKernelGGL((k_ce_lse<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ce_stats<A>, dim3(1), dim3(64), 0, st, a);
-    if (a.dh) hipLaunchKernelGGL((k_ce_dh<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
+    if constexpr (A::GBCE) hipLaunchKernelGGL((k_gbce_row<NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_ce_lse<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(k_ce_stats, dim3(1), dim3(64), 0, st, CeStatsArgs{a.stats, a.state, a.n_rt});
+    if constexpr (!A::GBCE) if (a.dh) hipLaunchKernelGGL((k_ce_dh<A, NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
     if (a.tg) {
         hipLaunchKernelGGL((k_ce_de<A, NK, SPLIT>), dim3(g.n_ct, g.parts), dim3(256), 0, st, a);
         if constexpr (S) {
             hipLaunchKernelGGL(k_sce_scatter, dim3(a.N), dim3(std::min(256, (a.D + 63) / 64 * 64)), 0, st, a);
             hipLaunchKernelGGL(k_sce_tgt, dim3(grid_for((int64_t)a.M * a.D)), dim3(256), 0, st, a);
         } else if (g.parts > 1) {
-            const int64_t n = (int64_t)(a.V - 1) * a.D;
-            const int grid = (int)std::min<int64_t>(2048, (n + 255) / 256);
-            hipLaunchKernelGGL(k_ce_de_sum, dim3(grid), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_ce_de_sum, dim3(grid_for((int64_t)(a.V - 1) * a.D)), dim3(256), 0, st, a);
         }
-    }
-}
-
-// gBCE: seven launches (no lse / dh pair: one row sweep)
-template <int NK, bool SPLIT>
-void gbce_launch(const GbceArgs& a, const CeGeom& g, hipStream_t st) {
-    const SceArgs& s = a;
-    hipLaunchKernelGGL(k_sce_ids<CR_GBCE_SITE>, dim3(grid_for((int64_t)a.N * a.D)), dim3(256), 0, st, s);
-    if (a.tg) hipLaunchKernelGGL(k_sce_dedup, dim3((a.N + 255) / 256), dim3(256), 0, st, s);
-    hipLaunchKernelGGL((k_gbce_row<NK, SPLIT>), dim3(g.n_rt), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(k_ce_stats<SceArgs>, dim3(1), dim3(64), 0, st, s);
-    if (a.tg) {
-        hipLaunchKernelGGL((k_ce_de<GbceArgs, NK, SPLIT>), dim3(g.n_ct, g.parts), dim3(256), 0, st, a);
-        hipLaunchKernelGGL(k_sce_scatter, dim3(a.N), dim3(std::min(256, (a.D + 63) / 64 * 64)), 0, st, s);
-        hipLaunchKernelGGL(k_sce_tgt, dim3(grid_for((int64_t)a.M * a.D)), dim3(256), 0, st, s);
     }
 }
 
@@ -942,128 +885,56 @@ extern "C" size_t cr_softmax_ce_workspace(int M, int V, int D) {
 }
 
 extern "C" int cr_softmax_ce(const cr_softmax_ce_desc* d, void* stream) {
-    CR_REQUIRE(d, "cr_softmax_ce: NULL descriptor");
-    CR_REQUIRE(d->seq_emb && d->table && d->pos && d->state, "cr_softmax_ce: NULL seq_emb, table, pos or state");
-    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_softmax_ce: D=%d outside 8 .. 256", d->D);
-    CR_REQUIRE(d->V >= 2, "cr_softmax_ce: V=%d < 2 (row 0 is padding: no item to score)", d->V);
-    CR_REQUIRE(d->M >= 1, "cr_softmax_ce: M=%d <= 0", d->M);
-    CR_REQUIRE(d->ld >= d->D, "cr_softmax_ce: ld=%d < D=%d", d->ld, d->D);
-    CR_REQUIRE(!d->d_seq_emb || d->ldd >= d->D, "cr_softmax_ce: ldd=%d < D=%d", d->ldd, d->D);
-    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
-               "cr_softmax_ce: unknown precision %d", d->precision);
+    if (const int rc = ce_check_desc("cr_softmax_ce", "score", d)) return rc;
     CeGeom g;
-    const size_t need = ce_workspace(d->M, d->V, d->D, g);
-    CR_REQUIRE(need, "cr_softmax_ce: unsupported shape");
-    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_softmax_ce: workspace of %zu bytes, cr_softmax_ce_workspace says %zu",
-               d->workspace ? d->workspace_bytes : (size_t)0, need);
+    if (const int rc = ce_check_workspace("cr_softmax_ce", d, ce_workspace(d->M, d->V, d->D, g))) return rc;
 
     unsigned char* w = static_cast<unsigned char*>(d->workspace);
     CeArgs a;
-    a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
-    a.M = d->M; a.D = d->D; a.V = d->V;
+    ce_fill(a, d, d->lse_out, g);
     a.lse2 = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
     a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
     a.part = reinterpret_cast<float*>(w);
-    a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
-    a.rpp = g.rpp; a.parts = g.parts;
-    a.lse_out = d->lse_out; a.state = d->state; a.n_rt = g.n_rt;
     ce_run(a, g, d->precision, cr_stream(stream));
     return cr_check_launch("cr_softmax_ce");
 }
 
 extern "C" size_t cr_sampled_ce_workspace(int M, int N, int D) {
     CeGeom g;
-    return sce_workspace(M, N, D, g);
+    return sce_workspace(M, N, D, true, g);
 }
 
 extern "C" int cr_sampled_ce(const cr_sampled_ce_desc* d, void* stream) {
-    CR_REQUIRE(d, "cr_sampled_ce: NULL descriptor");
-    CR_REQUIRE(d->seq_emb && d->table && d->pos && d->state, "cr_sampled_ce: NULL seq_emb, table, pos or state");
-    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_sampled_ce: D=%d outside 8 .. 256", d->D);
-    CR_REQUIRE(d->V >= 2, "cr_sampled_ce: V=%d < 2 (row 0 is padding: no item to sample)", d->V);
-    CR_REQUIRE(d->M >= 1, "cr_sampled_ce: M=%d <= 0", d->M);
-    CR_REQUIRE(d->N >= 1 && d->N <= CR_SCE_MAX_SAMPLES, "cr_sampled_ce: N=%d outside 1 .. %d", d->N, CR_SCE_MAX_SAMPLES);
-    CR_REQUIRE(d->ld >= d->D, "cr_sampled_ce: ld=%d < D=%d", d->ld, d->D);
-    CR_REQUIRE(!d->d_seq_emb || d->ldd >= d->D, "cr_sampled_ce: ldd=%d < D=%d", d->ldd, d->D);
-    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
-               "cr_sampled_ce: unknown precision %d", d->precision);
+    if (const int rc = ce_check_desc("cr_sampled_ce", "sample", d, d ? &d->N : nullptr)) return rc;
     CR_REQUIRE(d->samples || d->step, "cr_sampled_ce: NULL step with NULL samples (the device draw reads the step word)");
     CR_REQUIRE(!d->cdf || d->logq, "cr_sampled_ce: cdf without logq (a proposal is both: the draw and its log-Q correction)");
     CR_REQUIRE(d->samples || !d->logq || d->cdf, "cr_sampled_ce: logq with NULL samples needs the cdf (the device draw searches it)");
     CeGeom g;
-    const size_t need = sce_workspace(d->M, d->N, d->D, g);
-    CR_REQUIRE(need, "cr_sampled_ce: unsupported shape");
-    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_sampled_ce: workspace of %zu bytes, cr_sampled_ce_workspace says %zu",
-               d->workspace ? d->workspace_bytes : (size_t)0, need);
+    if (const int rc = ce_check_workspace("cr_sampled_ce", d, sce_workspace(d->M, d->N, d->D, true, g))) return rc;
 
-    unsigned char* w = static_cast<unsigned char*>(d->workspace);
-    SceArgs a;
-    a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
-    a.M = d->M; a.D = d->D; a.V = d->V; a.N = d->N;
-    a.samples = d->samples; a.seed = d->seed; a.step = d->step; a.samples_out = d->samples_out;
-    a.sid = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
-    a.nxt = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
-    a.head = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
-    a.Es = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->N * d->D);
-    a.lse2 = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
-    a.gpos = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
-    a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
-    a.part = reinterpret_cast<float*>(w); w += cr_align256(4 * sce_part_rows(d->N) * d->D);
-    a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
-    a.rpp = g.rpp; a.parts = g.parts;
-    a.lse_out = d->lse_out; a.state = d->state; a.n_rt = g.n_rt;
-    if (d->logq) {                                                  // popularity proposal: the corrected candidates
-        ScePopArgs p;
-        static_cast<SceArgs&>(p) = a;
-        p.cdf = d->cdf; p.logq = d->logq;
-        p.sb = reinterpret_cast<float*>(w);
-        ce_run(p, g, d->precision, cr_stream(stream));
-    } else {
-        ce_run(a, g, d->precision, cr_stream(stream));
-    }
+    ScePopArgs p;                                                   // (uniform: launched as its SceArgs base, which carries none of sb, cdf, logq)
+    p.sb = sce_fill(p, d, d->lse_out, true, g);
+    p.cdf = d->cdf; p.logq = d->logq;
+    if (d->logq) ce_run(p, g, d->precision, cr_stream(stream));     // popularity proposal: the corrected candidates
+    else ce_run(static_cast<const SceArgs&>(p), g, d->precision, cr_stream(stream));
     return cr_check_launch("cr_sampled_ce");
 }
 
 extern "C" size_t cr_gbce_workspace(int M, int N, int D) {
     CeGeom g;
-    return gbce_workspace(M, N, D, g);
+    return sce_workspace(M, N, D, false, g);
 }
 
 extern "C" int cr_gbce(const cr_gbce_desc* d, void* stream) {
-    CR_REQUIRE(d, "cr_gbce: NULL descriptor");
-    CR_REQUIRE(d->seq_emb && d->table && d->pos && d->state, "cr_gbce: NULL seq_emb, table, pos or state");
-    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_gbce: D=%d outside 8 .. 256", d->D);
-    CR_REQUIRE(d->V >= 2, "cr_gbce: V=%d < 2 (row 0 is padding: no item to sample)", d->V);
-    CR_REQUIRE(d->M >= 1, "cr_gbce: M=%d <= 0", d->M);
-    CR_REQUIRE(d->N >= 1 && d->N <= CR_SCE_MAX_SAMPLES, "cr_gbce: N=%d outside 1 .. %d", d->N, CR_SCE_MAX_SAMPLES);
-    CR_REQUIRE(d->ld >= d->D, "cr_gbce: ld=%d < D=%d", d->ld, d->D);
-    CR_REQUIRE(!d->d_seq_emb || d->ldd >= d->D, "cr_gbce: ldd=%d < D=%d", d->ldd, d->D);
-    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
-               "cr_gbce: unknown precision %d", d->precision);
+    if (const int rc = ce_check_desc("cr_gbce", "sample", d, d ? &d->N : nullptr)) return rc;
     CR_REQUIRE(d->beta > 0.0f && d->beta <= 1.0f, "cr_gbce: beta=%g outside (0, 1]", (double)d->beta);     // (NaN fails both)
     CR_REQUIRE(d->samples || d->step, "cr_gbce: NULL step with NULL samples (the device draw reads the step word)");
     CeGeom g;
-    const size_t need = gbce_workspace(d->M, d->N, d->D, g);
-    CR_REQUIRE(need, "cr_gbce: unsupported shape");
-    CR_REQUIRE(d->workspace && d->workspace_bytes >= need, "cr_gbce: workspace of %zu bytes, cr_gbce_workspace says %zu",
-               d->workspace ? d->workspace_bytes : (size_t)0, need);
+    if (const int rc = ce_check_workspace("cr_gbce", d, sce_workspace(d->M, d->N, d->D, false, g))) return rc;
 
-    unsigned char* w = static_cast<unsigned char*>(d->workspace);
     GbceArgs a;
-    a.h = d->seq_emb; a.ldh = d->ld; a.E = d->table; a.pos = d->pos; a.neg = d->neg;
-    a.M = d->M; a.D = d->D; a.V = d->V; a.N = d->N; a.beta = d->beta;
-    a.samples = d->samples; a.seed = d->seed; a.step = d->step; a.samples_out = d->samples_out;
-    a.sid = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
-    a.nxt = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
-    a.head = reinterpret_cast<int32_t*>(w); w += cr_align256(4 * (size_t)d->N);
-    a.Es = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->N * d->D);
-    a.lse2 = nullptr;
-    a.gpos = reinterpret_cast<float*>(w); w += cr_align256(4 * (size_t)d->M);
-    a.stats = reinterpret_cast<float*>(w); w += cr_align256(16 * (size_t)g.n_rt);
-    a.part = reinterpret_cast<float*>(w);
-    a.dh = d->d_seq_emb; a.ldd = d->ldd; a.tg = d->table_grad;
-    a.rpp = g.rpp; a.parts = g.parts;
-    a.lse_out = d->loss_out; a.state = d->state; a.n_rt = g.n_rt;
-    tk_dispatch(g.NK, d->precision != CR_PREC_BF16, [&](auto nk, auto split) { gbce_launch<nk, split>(a, g, cr_stream(stream)); });
+    sce_fill(a, d, d->loss_out, false, g);
+    a.beta = d->beta;
+    ce_run(a, g, d->precision, cr_stream(stream));
     return cr_check_launch("cr_gbce");
 }

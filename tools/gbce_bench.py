@@ -6,8 +6,9 @@ shape with loss "bce", "ce", "sampled_ce" and "gbce" (N = 256).
 
     python tools/gbce_bench.py [--shapes a,b,c] [--reps 7] [--out DIR/gbce_bench.json] [--no-torch] [--no-step]
 
---dump DIR writes what cr_softmax_ce, cr_sampled_ce (uniform proposal) and cr_gbce compute at one fixed case per precision (state, lse_out, d_seq_emb, samples
-and the table_grad rows that are no row's target: the outputs that have the same bits on every call) as .npy files, and exits;
+--dump DIR writes what cr_softmax_ce, cr_sampled_ce (uniform and popularity proposal, device draw) and cr_gbce compute at the cases of
+DUMP_CASES per precision, and at one of them with each optional pointer NULL (state, lse_out, d_seq_emb, samples and the table_grad
+rows that are no row's target: the outputs that have the same bits on every call) as .npy files, and exits;
 --lib PATH runs that through another build of libcastrec.so (loaded beside this one: lib.py binds every symbol of this header on
 import, so an older build cannot stand in through CASTREC_LIB); --compare DIR_A DIR_B says whether two dumps hold the same bits.
 """
@@ -27,7 +28,7 @@ import castrec_amd  # noqa: E402,F401
 from castrec_amd import lib as L  # noqa: E402
 from castrec_amd import ops as O  # noqa: E402
 from ce_bench import _time, train_step_ms  # noqa: E402
-from sce_bench import BF16_PEAK, SHAPES, _dpad  # noqa: E402
+from sce_bench import BF16_PEAK, SHAPES, _dpad, zipf_proposal  # noqa: E402
 
 
 def torch_gbce(h, table, pos, s, beta):
@@ -112,10 +113,20 @@ def run(key, reps, with_torch, beta=0.5):
     return res
 
 
-# ---- the existing losses, bit for bit ------------------------------------------------------------------------------------------
+# ---- the candidate-sweep losses, bit for bit -------------------------------------------------------------------------------------
+# (M, V, D, N): the smallest shapes that reach each path of csrc/cr_ce.hip
+DUMP_CASES = (("nk1", 77, 17, 8, 7),              # one k-step, a ragged row tile, fewer candidates than one block
+              ("base", 1300, 3417, 50, 256),      # two k-steps, catalogue parts > 1, more than 64 blocks in the catalogue sweep
+              ("nk4", 200, 3417, 100, 300),       # four k-steps, N no multiple of the block
+              ("nk8", 130, 1031, 200, 70),        # eight k-steps
+              ("long", 100, 3417, 50, 2100))      # sampled kinds only: more than 64 blocks, more than one dedup chunk
+DUMP_OPS = ("cr_softmax_ce", "cr_sampled_ce", "cr_sampled_ce_pop", "cr_gbce")      # _pop: popularity proposal, device draw
+DUMP_VARIANTS = ("all", "no_neg", "no_dh", "no_tg")                                # the optional pointers NULL: at "base" only
+
+
 def dump(out_dir, lib_path):
-    """cr_softmax_ce, cr_sampled_ce and cr_gbce at one fixed case per precision through `lib_path` (None: this build; a build from
-    before cr_gbce: without it)."""
+    """Every op of csrc/cr_ce.hip at DUMP_CASES x both precisions, and at "base" with neg, d_seq_emb or table_grad NULL, through
+    `lib_path` (None: this build; a build from before an op: without it)."""
     lib = L.lib
     if lib_path:
         lib = C.CDLL(os.path.abspath(lib_path))
@@ -126,46 +137,59 @@ def dump(out_dir, lib_path):
             getattr(lib, n + "_workspace").restype, getattr(lib, n + "_workspace").argtypes = C.c_size_t, [C.c_int] * 3
         lib.cr_last_error.restype = C.c_char_p
     os.makedirs(out_dir, exist_ok=True)
-    M, V, D, N = 1300, 3417, 50, 256
-    rs = np.random.RandomState(7)
-    h = torch.from_numpy(rs.standard_normal((M, D)).astype(np.float32) * (1.5 / D ** 0.5)).cuda()
-    table = torch.from_numpy(rs.standard_normal((V, D)).astype(np.float32) * 1.5).cuda()
-    pos_h = rs.randint(1, V, M).astype(np.int32)
-    pos_h[rs.rand(M) < 0.3] = 0
-    pos = torch.from_numpy(pos_h).cuda()
-    neg = torch.from_numpy((rs.randint(1, V, M) * (pos_h != 0)).astype(np.int32)).cuda()
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
-    keep = np.ones(V, bool)
-    keep[pos_h] = False                                   # the sampled op's target rows take float atomics
-    for prec, pname in ((L.PREC_BF16X3, "bf16x3"), (L.PREC_BF16, "bf16")):
-        for op in [o for o in ("cr_softmax_ce", "cr_sampled_ce", "cr_gbce") if hasattr(lib, o)]:
-            st = torch.zeros(L.CR_STATE_FLOATS, device="cuda")
-            st[4:5].view(torch.int32)[0] = 3
-            dh = torch.zeros(M, D, device="cuda")
-            tg = torch.zeros(V, D, device="cuda")
-            lse = torch.zeros(M, device="cuda")
-            so = torch.zeros(N, dtype=torch.int32, device="cuda")
-            p = lambda t: t.data_ptr()
-            if op == "cr_softmax_ce":
-                ws = torch.empty(lib.cr_softmax_ce_workspace(M, V, D), dtype=torch.uint8, device="cuda")
-                d = L.SoftmaxCeDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, prec, p(st), p(dh), D, p(tg), p(lse), p(ws), ws.numel())
-            elif op == "cr_gbce":
-                ws = torch.empty(lib.cr_gbce_workspace(M, N, D), dtype=torch.uint8, device="cuda")
-                d = L.GbceDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, N, prec, 0.4, None, 42, p(st) + 16, p(so), p(st), p(dh), D,
-                               p(tg), p(lse), p(ws), ws.numel())
-            else:
-                ws = torch.empty(lib.cr_sampled_ce_workspace(M, N, D), dtype=torch.uint8, device="cuda")
-                d = L.SampledCeDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, N, prec, None, 42, p(st) + 16, p(so), p(st), p(dh), D,
-                                    p(tg), p(lse), p(ws), ws.numel())
-            rc = getattr(lib, op)(C.byref(d), stream)
-            if rc != 0:
-                raise RuntimeError("%s failed: %s" % (op, lib.cr_last_error().decode()))
-            torch.cuda.synchronize()
-            outs = dict(state=st, lse_out=lse, d_seq_emb=dh, table_grad=tg.cpu()[torch.from_numpy(keep)] if op != "cr_softmax_ce" else tg,
-                        samples=so)
-            for k, v in outs.items():
-                np.save(os.path.join(out_dir, "%s_%s_%s.npy" % (op, pname, k)), v.cpu().numpy())
-    print("dumped", out_dir, "through", lib_path or L.LIB_PATH)
+    p = lambda t: t.data_ptr() if t is not None else None
+    n_files = 0
+    for case, M, V, D, N in DUMP_CASES:
+        rs = np.random.RandomState(7)
+        h = torch.from_numpy(rs.standard_normal((M, D)).astype(np.float32) * (1.5 / D ** 0.5)).cuda()
+        table = torch.from_numpy(rs.standard_normal((V, D)).astype(np.float32) * 1.5).cuda()
+        pos_h = rs.randint(1, V, M).astype(np.int32)
+        pos_h[rs.rand(M) < 0.3] = 0
+        pos = torch.from_numpy(pos_h).cuda()
+        neg_all = torch.from_numpy((rs.randint(1, V, M) * (pos_h != 0)).astype(np.int32)).cuda()
+        cdf, logq = zipf_proposal(V)
+        keep = np.ones(V, bool)
+        keep[pos_h] = False                               # the sampled ops' target rows take float atomics
+        for variant in (DUMP_VARIANTS if case == "base" else DUMP_VARIANTS[:1]):
+            for prec, pname in ((L.PREC_BF16X3, "bf16x3"), (L.PREC_BF16, "bf16")):
+                for op in DUMP_OPS:
+                    fn = op[:-4] if op.endswith("_pop") else op
+                    if not hasattr(lib, fn) or (case == "long" and op == "cr_softmax_ce"):
+                        continue
+                    st = torch.zeros(L.CR_STATE_FLOATS, device="cuda")
+                    st[4:5].view(torch.int32)[0] = 3
+                    neg = None if variant == "no_neg" else neg_all
+                    dh = None if variant == "no_dh" else torch.zeros(M, D, device="cuda")
+                    tg = None if variant == "no_tg" else torch.zeros(V, D, device="cuda")
+                    lse = torch.zeros(M, device="cuda")
+                    so = torch.zeros(N, dtype=torch.int32, device="cuda")
+                    if op == "cr_softmax_ce":
+                        ws = torch.empty(lib.cr_softmax_ce_workspace(M, V, D), dtype=torch.uint8, device="cuda")
+                        d = L.SoftmaxCeDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, prec, p(st), p(dh), D, p(tg), p(lse), p(ws),
+                                            ws.numel())
+                    elif op == "cr_gbce":
+                        ws = torch.empty(lib.cr_gbce_workspace(M, N, D), dtype=torch.uint8, device="cuda")
+                        d = L.GbceDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, N, prec, 0.4, None, 42, p(st) + 16, p(so), p(st), p(dh),
+                                       D, p(tg), p(lse), p(ws), ws.numel())
+                    else:
+                        ws = torch.empty(lib.cr_sampled_ce_workspace(M, N, D), dtype=torch.uint8, device="cuda")
+                        pop = op.endswith("_pop")
+                        d = L.SampledCeDesc(p(h), D, p(table), p(pos), p(neg), M, D, V, N, prec, None, 42, p(st) + 16, p(so), p(st), p(dh),
+                                            D, p(tg), p(lse), p(ws), ws.numel(), p(cdf) if pop else None, p(logq) if pop else None)
+                    rc = getattr(lib, fn)(C.byref(d), stream)
+                    if rc != 0:
+                        raise RuntimeError("%s failed: %s" % (op, lib.cr_last_error().decode()))
+                    torch.cuda.synchronize()
+                    outs = dict(state=st, lse_out=lse, samples=so)
+                    if dh is not None:
+                        outs["d_seq_emb"] = dh
+                    if tg is not None:
+                        outs["table_grad"] = tg if op == "cr_softmax_ce" else tg.cpu()[torch.from_numpy(keep)]
+                    for k, v in outs.items():
+                        np.save(os.path.join(out_dir, "%s_%s_%s_%s_%s.npy" % (case, variant, op, pname, k)), v.cpu().numpy())
+                        n_files += 1
+    print("dumped %d arrays to" % n_files, out_dir, "through", lib_path or L.LIB_PATH)
 
 
 def compare(a, b):
