@@ -350,7 +350,9 @@ extern "C" int cr_adam_step(const cr_adam_desc* d, void* stream) {
         const long long slot4 = ((d->ids_copy_elems ? d->ids_copy_elems : d->ids_slot_elems) + 3) / 4;
         nb_ring = (int)((slot4 + NT - 1) / NT > 256 ? 256 : (slot4 + NT - 1) / NT);
     }
-    static const char* nt_env = getenv("CASTREC_ADAM_STREAM");
+    // read on EVERY call (not cached in a static: a test or a tool that sets it after the process's first step would be ignored);
+    // a captured graph keeps the instantiation chosen at capture time -- the variable is not looked at again on replay
+    const char* nt_env = getenv("CASTREC_ADAM_STREAM");
     const bool stream_sweep = nt_env ? atoi(nt_env) != 0 : n_swept * 4 >= (256ll << 20);
     cr_tgrad_desc g;
     memset(&g, 0, sizeof(g));

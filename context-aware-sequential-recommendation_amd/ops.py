@@ -248,12 +248,31 @@ def gbce(seq_emb, ld, table, pos, state, workspace, M, N, beta=1.0, precision=L.
 
 
 def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, state, beta1=0.9, beta2=0.98, eps=1e-8,
-              stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None):
+              stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None, l2=0.0, n_l2=0,
+              slab_counts=None, ids_ring=None, ids_ring_slots=0, ids_slot_elems=0, ids_dst=None, ids_copy_elems=0, tg=None):
+    """cr_adam_step (castrec.h cr_adam_desc).  l2 / n_l2: the embedding regulariser on the first n_l2 parameters; slab_counts: int32
+    [ceil(n_dense / 256)]; ids_ring .. ids_copy_elems: the id ring whose next slot this launch moves to ids_dst; tg: an L.TgradDesc
+    (the table section's gradient from the occurrence index; table_grad may then be None)."""
     d = L.AdamDesc(_p(p), _p(m), _p(v), _p(table_grad), _p(dense_slabs), n_table, n_dense, n_slabs, lr, beta1, beta2,
                    eps, _p(state), _p(stats) if stats is not None else None,
-                   _p(step_snapshot) if step_snapshot is not None else None, 0.0, 0,
-                   _p(lazy_ids), 0 if lazy_ids is None else lazy_ids.numel(), lazy_rows, lazy_D, _p(lazy_flags), None)
+                   _p(step_snapshot) if step_snapshot is not None else None, float(l2), int(n_l2),
+                   _p(lazy_ids), 0 if lazy_ids is None else lazy_ids.numel(), lazy_rows, lazy_D, _p(lazy_flags),
+                   _p(_i32(slab_counts, "slab_counts")), _p(_i32(ids_ring, "ids_ring")), int(ids_ring_slots), int(ids_slot_elems),
+                   _p(_i32(ids_dst, "ids_dst")), int(ids_copy_elems))
+    if tg is not None:
+        d.tg = C.pointer(tg)
     L.call("cr_adam_step", C.byref(d), _stream())
+
+
+def reduce_slabs(dense_slabs, n_slabs, n_dense, out, state=None, stats_out=None, slab_counts=None):
+    """cr_reduce_slabs: out[i] = sum of the first slab_counts[i // 256] (default n_slabs) slabs of column i; state[0..2] -> stats_out."""
+    L.call("cr_reduce_slabs", _p(_f32(dense_slabs, "dense_slabs")), n_slabs, n_dense, _p(_f32(out, "out")), _p(state), _p(stats_out),
+           _p(_i32(slab_counts, "slab_counts")), _stream())
+
+
+def l2_penalty(p, n, scale, state):
+    """cr_l2_penalty: state[7] = scale * sum(p[:n] ** 2)."""
+    L.call("cr_l2_penalty", _p(_f32(p, "p")), int(n), float(scale), _p(_f32(state, "state")), _stream())
 
 
 class Graph:
