@@ -52,266 +52,254 @@ __device__ __forceinline__ float slab_sum256(const float* slabs, int n_slabs, in
     return g;
 }
 
-// blocks [0, nb_dense): 256 dense parameters each (slab reduction + update); then nb_lazy blocks (lazy item-table rows,
-// one wave per listed id); the rest: table entries, grid-stride
-// STREAM (a swept table section of the Infinity Cache's size or more: nothing of it is read again before 7 x its size has passed):
-// the sweep's accesses are streaming loads / stores, and four groups instead of two are in flight per thread.  The 10 M-item table
-// of config C5 (71.7 GB per step): 14.2 -> 13.6 ms.  (Four groups cost 76 bytes of scratch at this kernel's 128 registers -- the four
-// arrays' 64-bit addresses; a contiguous region per workgroup, which needs one 32-bit offset only, ran the sweep 20 % SLOWER: 256
-// separate streams per array instead of one moving window.)
-// LPR > 0 (with VEC): the table section's gradient comes from the batch's occurrence index `g` (cr_tgrad.hpp): nb_units blocks sum
-// the listed rows and update them in place, the sweep blocks give every row WITHOUT a unit the zero-gradient update -- no table_grad
-// array is read or zeroed (two of the sweep's eight streams: config C5's dense step moves 53.8 instead of 71.7 GB).
+// The workgroups of one launch, in block order: nb_dense blocks of 256 dense parameters (slab sums + update), nb_lazy blocks of lazy
+// item-table rows, nb_units unit workgroups of the occurrence index, nb_table sweep blocks, nb_ring blocks of the id-ring copy.
+// (The order is measured.  The unit workgroups FIRST: 29.7 against 25.8 us at the time -- the dense blocks' slab sums are the other
+//  long chain and want the early start; the short sections, id ring and sweep, first: 21.8 against 20.6 us.  The unit grid holds a
+//  batch's plan in ONE pass -- 384 workgroups: 260-280 are in use at the headline shape; at 256 a few workgroups ran two passes: 20.6
+//  against 19.8 us.)
+struct adam_grid { int nb_dense, nb_lazy, nb_units, nb_table, nb_ring; };
+#define ADAM_NT (64 * ADAM_WAVES)
+
+// The step's constants, formed once per thread, and 1 / n_target.  They cost two dependent loads (n, t) and two powf: every role forms
+// them BEHIND its first loads, which do not depend on them -- one memory round trip of this short kernel's critical path
+// (tools/adam_probe.py).  l2 is a REFERENCE into the kernel's argument d, which must outlive the struct (it is not assignable): copied,
+// a 16-byte group does its four l2 terms between the other arithmetic and k_adam<true, 0, 1> needs 96 instead of 76 bytes of scratch.
+struct adam_consts { float b1, c1, b2, c2, eps; const float& l2; long long n_l2; float lr_t, inv_n; };
+__device__ __forceinline__ adam_consts adam_scalars(const cr_adam_desc& d, float n, uint32_t t) {
+    const float b1t = powf(d.beta1, (float)t), b2t = powf(d.beta2, (float)t);
+    return {d.beta1, 1.0f - d.beta1, d.beta2, 1.0f - d.beta2, d.eps, d.l2, d.n_l2, d.lr * sqrtf(1.0f - b2t) / (1.0f - b1t), n > 0.0f ? 1.0f / n : 0.0f};
+}
+
+// THE update, of element i with gradient g: the CALLER has multiplied it by k.inv_n (nothing in here does), or passes a literal 0.0f
+// where there is none.  Every role calls it, so every role rounds alike: the compiler contracts these shapes to fma(b1, m, c1 * g) and
+// fma(b2, v, (c2 * g) * g), and the bitwise reproducibility of the one-GPU step rests on all roles agreeing.
+__device__ __forceinline__ void adam_update(const adam_consts& k, long long i, float g, float& p, float& m, float& v) {
+    if (i < k.n_l2) g = fmaf(k.l2, p, g);                // d/dp of l2 * sum(p^2) / 2 on the lookup tables (modules.py:153)
+    m = k.b1 * m + k.c1 * g;
+    v = k.b2 * v + k.c2 * g * g;
+    p = p - k.lr_t * m / (sqrtf(v) + k.eps);
+}
+// ... of one element in memory
+__device__ __forceinline__ void adam_element(const cr_adam_desc& d, const adam_consts& k, long long i, float g) {
+    float p = d.p[i], m = d.m[i], v = d.v[i];
+    adam_update(k, i, g, p, m, v);
+    d.m[i] = m; d.v[i] = v; d.p[i] = p;
+}
+// ... of one element whose gradient is table_grad[i], which is zeroed for the next step
+__device__ __forceinline__ void adam_element_tg(const cr_adam_desc& d, const adam_consts& k, long long i) {
+    const float g = d.table_grad[i];
+    d.table_grad[i] = 0.0f;
+    adam_element(d, k, i, g * k.inv_n);
+}
+
+// 16 bytes of a swept section: streaming (STREAM: nothing of the section is read again before 7 x its size has passed) or plain
+template <bool STREAM>
+__device__ __forceinline__ f4a ld4(const float* q) {
+    return STREAM ? __builtin_nontemporal_load(reinterpret_cast<const f4a*>(q)) : *reinterpret_cast<const f4a*>(q);
+}
+template <bool STREAM>
+__device__ __forceinline__ void st4(float* q, const f4a x) {
+    if (STREAM) __builtin_nontemporal_store(x, reinterpret_cast<f4a*>(q));
+    else *reinterpret_cast<f4a*>(q) = x;
+}
+// ... updated component by component and stored; g: the four gradients, or one float for all four
+__device__ __forceinline__ float adam_comp(const f4a g, int e) { return g[e]; }
+__device__ __forceinline__ float adam_comp(float g, int) { return g; }
+template <bool STREAM, typename G>
+__device__ __forceinline__ void adam_update4(const cr_adam_desc& d, const adam_consts& k, long long i, const G g, f4a p, f4a m, f4a v) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        float pe = p[e], me = m[e], ve = v[e];
+        adam_update(k, i + e, adam_comp(g, e), pe, me, ve);
+        p[e] = pe; m[e] = me; v[e] = ve;
+    }
+    st4<STREAM>(d.m + i, m); st4<STREAM>(d.v + i, v); st4<STREAM>(d.p + i, p);
+}
+// ... with the gradient group g of table_grad, which is zeroed for the next step
+template <bool STREAM>
+__device__ __forceinline__ void adam_update4_tg(const cr_adam_desc& d, const adam_consts& k, long long i, f4a g, const f4a p, const f4a m, const f4a v) {
+    st4<STREAM>(d.table_grad + i, (f4a){0.f, 0.f, 0.f, 0.f});
+    g *= k.inv_n;
+    adam_update4<STREAM>(d, k, i, g, p, m, v);
+}
+
+// ---- the roles of a workgroup (b: its number within the role) -----------------------------------------------------------------
+// the next step's ids out of the resident ring (nothing else in this launch reads the static id buffers; the occurrence index of
+// the RUNNING step is read from its ring slot, which these blocks do not write)
+__device__ __forceinline__ void adam_ring_copy(const cr_adam_desc& d, int b, int nb_ring, uint32_t t) {
+    const long long n_copy = d.ids_copy_elems ? d.ids_copy_elems : d.ids_slot_elems;
+    const int32_t* src1 = d.ids_ring + (long long)((t + 1u) % (uint32_t)d.ids_ring_slots) * d.ids_slot_elems;
+    const long long first = (long long)b * ADAM_NT + threadIdx.x, stride = (long long)nb_ring * ADAM_NT;
+    if ((d.ids_slot_elems & 3) == 0 && (n_copy & 3) == 0 && (((uintptr_t)d.ids_ring | (uintptr_t)d.ids_dst) & 15) == 0) {
+        const int4* src = reinterpret_cast<const int4*>(src1);
+        int4* dst = reinterpret_cast<int4*>(d.ids_dst);
+        for (long long i = first; i < (n_copy >> 2); i += stride) dst[i] = src[i];
+    } else {                                             // (a slot that is no multiple of 16 bytes: B * T odd)
+        for (long long i = first; i < n_copy; i += stride) d.ids_dst[i] = src1[i];
+    }
+}
+
+// 256 dense parameters: slab sums, then the update
+__device__ __forceinline__ void adam_dense_block(const cr_adam_desc& d, int b, float n, uint32_t t, float (*part)[ADAM_COLS]) {
+    const int j0 = b * ADAM_COLS;
+    const int ns = d.slab_counts ? min(d.slab_counts[b], d.n_slabs) : d.n_slabs;
+    // the parameter and its moments are requested BEFORE the slab sum (they do not depend on it): one memory round trip less on
+    // the critical path of this short kernel
+    const bool mine = threadIdx.x < ADAM_COLS && j0 + (int)threadIdx.x < d.n_dense;
+    const long long i0 = d.n_table + j0;                 // (uniform: the three arrays are addressed as a scalar base + a 32-bit lane offset)
+    const unsigned c = mine ? threadIdx.x : 0u;
+    float p = mine ? (d.p + i0)[c] : 0.0f, m = mine ? (d.m + i0)[c] : 0.0f, v = mine ? (d.v + i0)[c] : 0.0f;
+    const float g = slab_sum256(d.dense_slabs, ns, d.n_dense, j0, part);
+    const adam_consts k = adam_scalars(d, n, t);
+    if (mine) {
+        adam_update(k, i0 + c, g * k.inv_n, p, m, v);
+        (d.m + i0)[c] = m; (d.v + i0)[c] = v; (d.p + i0)[c] = p;
+    }
+}
+
+// lazy rows: wave w of the nb_lazy blocks walks ids w, w + W, ...; the first wave to swap the step number into a row's flag owns the
+// row (every other occurrence of the id finds it there and moves on)
+__device__ __forceinline__ void adam_lazy_rows(const cr_adam_desc& d, int b, int nb_lazy, float n, uint32_t t) {
+    const int lane = threadIdx.x & 63, W = nb_lazy * ADAM_WAVES;
+    const adam_consts k = adam_scalars(d, n, t);
+    for (int j = b * ADAM_WAVES + (threadIdx.x >> 6); j < d.n_lazy_ids; j += W) {
+        const int id = d.lazy_ids[j];
+        if (id <= 0 || id >= d.lazy_rows) continue;      // row 0: the zero-pad row never has a gradient
+        int mine = 0;
+        if (lane == 0) mine = atomicExch(&d.lazy_flags[id], t) != t;
+        mine = __shfl(mine, 0, 64);
+        if (!mine) continue;
+        for (int c = lane; c < d.lazy_D; c += 64) adam_element_tg(d, k, (long long)id * d.lazy_D + c);
+    }
+}
+
+// the rows the batch looked up (occurrence index, cr_tgrad.hpp): gradient = ordered sum over the row's occurrences, update in place.
+// (p / m / v requested in front of the batch's loads: 20 bytes of scratch per lane at 16 occurrences in flight, and no faster -- 20.1
+// against 20.3 us.)
+template <int LPR, int VEC>
+__device__ __forceinline__ void adam_unit_blocks(const cr_adam_desc& d, const cr_tgrad_desc& g, int b, int nb_units, float n, uint32_t t, float* part_s) {
+    const int32_t* ix = tg_index(g, t);
+    const adam_consts k = adam_scalars(d, n, t);
+    tg_unit_blocks<LPR, VEC, tg_ent(VEC)>(g, ix, b, nb_units, part_s, reinterpret_cast<int*>(part_s + ADAM_WAVES * ADAM_COLS),
+        [&](int row, int col0, const float (&acc)[VEC]) {
+            const long long i = (long long)row * g.D + col0;
+            float p[VEC], m[VEC], v[VEC];
+            tg_load<VEC>(p, d.p + i); tg_load<VEC>(m, d.m + i); tg_load<VEC>(v, d.v + i);
+#pragma unroll
+            for (int u = 0; u < VEC; ++u) adam_update(k, i + u, acc[u] * k.inv_n, p[u], m[u], v[u]);
+            tg_store<VEC>(d.m + i, m); tg_store<VEC>(d.v + i, v); tg_store<VEC>(d.p + i, p);
+        });
+}
+
+// the rows WITHOUT a unit: the zero-gradient update of TensorFlow's dense Adam (m, v decay, p moves on its momentum) -- no table_grad
+// array is read or zeroed (two of the plain sweep's eight streams: config C5's dense step moves 53.8 instead of 71.7 GB)
+template <bool STREAM>
+__device__ __forceinline__ void adam_bitmap_sweep(const cr_adam_desc& d, const cr_tgrad_desc& g, int b, int nb_table, float n, uint32_t t) {
+    const int32_t* ix = tg_index(g, t);
+    const uint32_t* bits = reinterpret_cast<const uint32_t*>(ix + ix[6]);
+    const long long stride = (long long)nb_table * ADAM_NT;
+    const adam_consts k = adam_scalars(d, n, t);
+    if ((g.D & 3) == 0) {
+        const long long n4 = d.n_table >> 2;
+        const unsigned D4 = (unsigned)g.D >> 2;
+        const int sh = (D4 & (D4 - 1u)) == 0u ? __builtin_ctz(D4) : -1;      // (128 / 256 columns: a shift instead of a 64-bit division per group)
+        constexpr int U = 4;
+        // p / m / v of a group are requested WITHOUT waiting for the bitmap word that says whether the row is listed (a dependent
+        // round trip in front of every batch of loads: the first version swept config C5's table no faster than the sweep that also
+        // read and zeroed a gradient array); a listed row's values are read and dropped (2 % of the rows at C5), only its STORES
+        // are skipped -- the unit workgroups write those elements
+        for (long long q = (long long)b * ADAM_NT + threadIdx.x; q < n4; q += U * stride) {
+            bool in[U];
+            uint32_t bw[U], row[U];
+            f4a p[U], m[U], v[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long long qq = q + u * stride;
+                in[u] = qq < n4;
+                const long long qc = in[u] ? qq : q;
+                row[u] = sh >= 0 ? (uint32_t)(qc >> sh) : (uint32_t)((unsigned long long)qc / D4);
+                bw[u] = bits[row[u] >> 5];
+                p[u] = ld4<STREAM>(d.p + 4 * qc); m[u] = ld4<STREAM>(d.m + 4 * qc); v[u] = ld4<STREAM>(d.v + 4 * qc);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (in[u] && !((bw[u] >> (row[u] & 31)) & 1u)) adam_update4<STREAM>(d, k, 4 * (q + u * stride), 0.0f, p[u], m[u], v[u]);
+        }
+    } else {
+        for (long long i = (long long)b * ADAM_NT + threadIdx.x; i < d.n_table; i += stride) {
+            const uint32_t row = (uint32_t)((unsigned long long)i / (unsigned)g.D);
+            if (!((bits[row >> 5] >> (row & 31)) & 1u)) adam_element(d, k, i, 0.0f);
+        }
+    }
+}
+
+// the table section with a gradient array: 16 bytes per lane per array (4-byte accesses moved 3.2 TB/s on a 188 MB table; see
+// DESIGN.md), two groups of four in flight per thread; the scalar head / tail (a start or an end that is not a multiple of 4) goes to
+// the first sweep block.
+// STREAM (a swept section of the Infinity Cache's size or more): streaming loads / stores, and four groups instead of two in flight
+// per thread.  The 10 M-item table of config C5 (71.7 GB per step): 14.2 -> 13.6 ms.  (Four groups cost 76 bytes of scratch at this
+// kernel's 128 registers -- the four arrays' 64-bit addresses; a contiguous region per workgroup, which needs one 32-bit offset only,
+// ran the sweep 20 % SLOWER: 256 separate streams per array instead of one moving window.)
+template <bool STREAM>
+__device__ __forceinline__ void adam_plain_sweep(const cr_adam_desc& d, int b, int nb_table, bool lazy, float n, uint32_t t) {
+    const long long first = lazy ? (long long)d.lazy_rows * d.lazy_D : 0;      // the lazy part of the table section is not swept
+    const long long a0 = min((first + 3) & ~3ll, d.n_table);
+    const long long n4 = (d.n_table - a0) >> 2;
+    const long long stride = (long long)nb_table * ADAM_NT;
+    long long q = (long long)b * ADAM_NT + threadIdx.x;
+    // the thread's first group (its only one on a table of a few hundred thousand entries): requested, THEN the scalars
+    const bool have = q < n4;
+    const long long i1 = a0 + 4 * (have ? q : 0);
+    f4a g1 = (f4a){0.f, 0.f, 0.f, 0.f}, p1 = g1, m1 = g1, v1 = g1;
+    if (have) { g1 = ld4<STREAM>(d.table_grad + i1); p1 = ld4<STREAM>(d.p + i1); m1 = ld4<STREAM>(d.m + i1); v1 = ld4<STREAM>(d.v + i1); }
+    const adam_consts k = adam_scalars(d, n, t);
+    if (have) {
+        adam_update4_tg<STREAM>(d, k, i1, g1, p1, m1, v1);
+        q += stride;
+    }
+    constexpr int U = STREAM ? 4 : 2;                     // groups of the four arrays requested before the first update
+    for (; q + (U - 1) * stride < n4; q += U * stride) {
+        f4a g[U], p[U], m[U], v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long long i = a0 + 4 * (q + u * stride);
+            g[u] = ld4<STREAM>(d.table_grad + i); p[u] = ld4<STREAM>(d.p + i); m[u] = ld4<STREAM>(d.m + i); v[u] = ld4<STREAM>(d.v + i);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) adam_update4_tg<STREAM>(d, k, a0 + 4 * (q + u * stride), g[u], p[u], m[u], v[u]);
+    }
+    for (; q < n4; q += stride) {
+        const long long i = a0 + 4 * q;
+        const f4a g = ld4<STREAM>(d.table_grad + i), p = ld4<STREAM>(d.p + i), m = ld4<STREAM>(d.m + i), v = ld4<STREAM>(d.v + i);
+        adam_update4_tg<STREAM>(d, k, i, g, p, m, v);
+    }
+    if (b == 0) {
+        for (long long i = first + threadIdx.x; i < a0; i += ADAM_NT) adam_element_tg(d, k, i);
+        for (long long i = a0 + 4 * n4 + threadIdx.x; i < d.n_table; i += ADAM_NT) adam_element_tg(d, k, i);
+    }
+}
+
+// One launch, every role (adam_grid).  STREAM: the sweep's accesses.  LPR > 0 (with VEC): the table section's gradient comes from the
+// batch's occurrence index `g` (cr_tgrad.hpp) -- unit workgroups and the bitmap sweep; LPR == 0: from table_grad -- lazy rows and the
+// plain sweep (the host refuses an index together with lazy rows).
 template <bool STREAM, int LPR, int VEC>
-__global__ __launch_bounds__(64 * ADAM_WAVES) void k_adam(cr_adam_desc d, cr_tgrad_desc g, int nb_dense, int nb_lazy, int nb_units, int nb_ring) {
+__global__ __launch_bounds__(ADAM_NT) void k_adam(cr_adam_desc d, cr_tgrad_desc g, adam_grid gr) {
     __shared__ float part_s[ADAM_WAVES * ADAM_COLS + 4];                         // (+ one word: "this slice arrived last", cr_tgrad.hpp)
-    float (*part)[ADAM_COLS] = reinterpret_cast<float (*)[ADAM_COLS]>(part_s);
     constexpr bool TG = LPR > 0;
     cr_kernarg_touch<sizeof(cr_adam_desc) + (TG ? sizeof(cr_tgrad_desc) : 0)>();
     const uint32_t t = d.step_snapshot ? *d.step_snapshot : *reinterpret_cast<const uint32_t*>(d.state + 4);
-    // (Two other dispatch orders were measured and lost: the unit workgroups FIRST -- 29.7 against 25.8 us at the time: the dense blocks'
-    //  slab sums are the other long chain and want the early start -- and the short sections, id ring and sweep, first -- 21.8 against
-    //  20.6 us.  The unit grid holds a batch's plan in ONE pass -- 384 workgroups: 260-280 are in use at the headline shape; at 256 a few
-    //  workgroups ran two passes: 20.6 against 19.8 us.)
     const int bid = (int)blockIdx.x;
-    if (bid >= (int)gridDim.x - nb_ring) {
-        // the last nb_ring blocks: the next step's ids out of the resident ring (nothing else in this launch reads the static id
-        // buffers; the occurrence index of the RUNNING step is read from its ring slot, which these blocks do not write)
-        constexpr int NT = 64 * ADAM_WAVES;
-        const long long n_copy = d.ids_copy_elems ? d.ids_copy_elems : d.ids_slot_elems;
-        const int32_t* src1 = d.ids_ring + (long long)((t + 1u) % (uint32_t)d.ids_ring_slots) * d.ids_slot_elems;
-        const long long first = (long long)(bid - ((int)gridDim.x - nb_ring)) * NT + threadIdx.x, stride = (long long)nb_ring * NT;
-        if ((d.ids_slot_elems & 3) == 0 && (n_copy & 3) == 0 && (((uintptr_t)d.ids_ring | (uintptr_t)d.ids_dst) & 15) == 0) {
-            const int4* src = reinterpret_cast<const int4*>(src1);
-            int4* dst = reinterpret_cast<int4*>(d.ids_dst);
-            for (long long i = first; i < (n_copy >> 2); i += stride) dst[i] = src[i];
-        } else {                                         // (a slot that is no multiple of 16 bytes: B * T odd)
-            for (long long i = first; i < n_copy; i += stride) d.ids_dst[i] = src1[i];
-        }
-        return;
-    }
+    const int b_lazy = gr.nb_dense, b_units = b_lazy + gr.nb_lazy, b_sweep = b_units + gr.nb_units, b_ring = b_sweep + gr.nb_table;
+    if (bid >= b_ring) return adam_ring_copy(d, bid - b_ring, gr.nb_ring, t);
     const float* st = d.stats ? d.stats : d.state;
     const float n = st[2];
-    // the step's scalars (two dependent loads, two powf) are formed where a section first needs them: BEHIND its first loads, which
-    // do not depend on them -- one memory round trip of this short kernel's critical path (tools/adam_probe.py)
-    float inv_n = 0.0f, lr_t = 0.0f;
-    auto scalars = [&]() {
-        inv_n = n > 0.0f ? 1.0f / n : 0.0f;
-        const float b1t = powf(d.beta1, (float)t), b2t = powf(d.beta2, (float)t);
-        lr_t = d.lr * sqrtf(1.0f - b2t) / (1.0f - b1t);
-    };
-    auto update = [&](long long i, float g) {
-        g *= inv_n;
-        if (i < d.n_l2) g = fmaf(d.l2, d.p[i], g);       // d/dp of l2 * sum(p^2) / 2 on the lookup tables (modules.py:153)
-        const float m = d.beta1 * d.m[i] + (1.0f - d.beta1) * g;
-        const float v = d.beta2 * d.v[i] + (1.0f - d.beta2) * g * g;
-        d.m[i] = m;
-        d.v[i] = v;
-        d.p[i] -= lr_t * m / (sqrtf(v) + d.eps);
-    };
-    if (bid < nb_dense) {
-        const int j0 = bid * ADAM_COLS;
-        const int ns = d.slab_counts ? min(d.slab_counts[bid], d.n_slabs) : d.n_slabs;
-        // the parameter and its moments are requested BEFORE the slab sum (they do not depend on it): one memory round trip less on
-        // the critical path of this short kernel
-        const bool mine = threadIdx.x < ADAM_COLS && j0 + (int)threadIdx.x < d.n_dense;
-        const long long i = d.n_table + j0 + (mine ? (int)threadIdx.x : 0);
-        const float p0 = mine ? d.p[i] : 0.0f, m0 = mine ? d.m[i] : 0.0f, v0 = mine ? d.v[i] : 0.0f;
-        float g = slab_sum256(d.dense_slabs, ns, d.n_dense, j0, part);
-        scalars();
-        if (mine) {
-            g *= inv_n;
-            if (i < d.n_l2) g = fmaf(d.l2, p0, g);
-            const float m = d.beta1 * m0 + (1.0f - d.beta1) * g;
-            const float v = d.beta2 * v0 + (1.0f - d.beta2) * g * g;
-            d.m[i] = m;
-            d.v[i] = v;
-            d.p[i] = p0 - lr_t * m / (sqrtf(v) + d.eps);
-        }
-    } else if (bid < nb_dense + nb_lazy) {
-        // lazy rows: wave w of the lazy blocks walks ids w, w + W, ...; the first wave to swap the step number into a row's
-        // flag owns the row (every other occurrence of the id finds it there and moves on)
-        const int lane = threadIdx.x & 63;
-        const int W = nb_lazy * ADAM_WAVES;
-        scalars();
-        for (int k = (bid - nb_dense) * ADAM_WAVES + (threadIdx.x >> 6); k < d.n_lazy_ids; k += W) {
-            const int id = d.lazy_ids[k];
-            if (id <= 0 || id >= d.lazy_rows) continue;                       // row 0: the zero-pad row never has a gradient
-            int mine = 0;
-            if (lane == 0) mine = atomicExch(&d.lazy_flags[id], t) != t;
-            mine = __shfl(mine, 0, 64);
-            if (!mine) continue;
-            for (int c = lane; c < d.lazy_D; c += 64) {
-                const long long i = (long long)id * d.lazy_D + c;
-                const float g = d.table_grad[i];
-                d.table_grad[i] = 0.0f;
-                update(i, g);
-            }
-        }
-    } else if (TG && bid < nb_dense + nb_lazy + nb_units) {
-        // the rows the batch looked up: gradient = ordered sum over the row's occurrences, update in place.  (p / m / v requested in
-        // front of the batch's loads: 20 bytes of scratch per lane at 16 occurrences in flight, and no faster -- 20.1 against 20.3 us.)
-        const int32_t* ix = tg_index(g, t);
-        constexpr int W = TG ? VEC : 1;
-        scalars();
-        tg_unit_blocks<TG ? LPR : 16, W, (TG && VEC == 4) ? 8 : 16>(g, ix, bid - nb_dense - nb_lazy, nb_units, part_s,
-            reinterpret_cast<int*>(part_s + ADAM_WAVES * ADAM_COLS),
-            [&](int row, int col0, const float (&acc)[W]) {
-                const long long i = (long long)row * g.D + col0;
-                float p0[W], m0[W], v0[W];
-                tg_load<W>(p0, d.p + i); tg_load<W>(m0, d.m + i); tg_load<W>(v0, d.v + i);
-#pragma unroll
-                for (int u = 0; u < W; ++u) {
-                    float gu = acc[u] * inv_n;
-                    if (i + u < d.n_l2) gu = fmaf(d.l2, p0[u], gu);
-                    m0[u] = d.beta1 * m0[u] + (1.0f - d.beta1) * gu;
-                    v0[u] = d.beta2 * v0[u] + (1.0f - d.beta2) * gu * gu;
-                    p0[u] -= lr_t * m0[u] / (sqrtf(v0[u]) + d.eps);
-                }
-                tg_store<W>(d.m + i, m0); tg_store<W>(d.v + i, v0); tg_store<W>(d.p + i, p0);
-            });
-    } else if (TG) {
-        // the rows WITHOUT a unit: the zero-gradient update of TensorFlow's dense Adam (m, v decay, p moves on its momentum)
-        const int32_t* ix = tg_index(g, t);
-        const uint32_t* bits = reinterpret_cast<const uint32_t*>(ix + ix[6]);
-        const int nb_table = gridDim.x - nb_dense - nb_lazy - nb_units - nb_ring;
-        const int tb = bid - nb_dense - nb_lazy - nb_units;
-        constexpr int NT = 64 * ADAM_WAVES;
-        const long long stride = (long long)nb_table * NT;
-        auto touched = [&](uint32_t row) { return ((bits[row >> 5] >> (row & 31)) & 1u) != 0u; };
-        scalars();
-        if ((g.D & 3) == 0) {
-            const float b1 = d.beta1, b2 = d.beta2, c1 = 1.0f - d.beta1, c2 = 1.0f - d.beta2;
-            auto ld4 = [](const float* q) { return STREAM ? __builtin_nontemporal_load(reinterpret_cast<const f4a*>(q)) : *reinterpret_cast<const f4a*>(q); };
-            auto st4 = [](float* q, const f4a x) {
-                if (STREAM) __builtin_nontemporal_store(x, reinterpret_cast<f4a*>(q));
-                else *reinterpret_cast<f4a*>(q) = x;
-            };
-            const long long n4 = d.n_table >> 2;
-            const unsigned D4 = (unsigned)g.D >> 2;
-            const int sh = (D4 & (D4 - 1u)) == 0u ? __builtin_ctz(D4) : -1;      // (128 / 256 columns: a shift instead of a 64-bit division per group)
-            constexpr int U = 4;
-            // p / m / v of a group are requested WITHOUT waiting for the bitmap word that says whether the row is listed (a dependent
-            // round trip in front of every batch of loads: the first version swept config C5's table no faster than the sweep that also
-            // read and zeroed a gradient array); a listed row's values are read and dropped (2 % of the rows at C5), only its STORES
-            // are skipped -- the unit workgroups write those elements
-            for (long long q = (long long)tb * NT + threadIdx.x; q < n4; q += U * stride) {
-                bool in[U];
-                uint32_t bw[U];
-                uint32_t row[U];
-                f4a p[U], m[U], v[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const long long qq = q + u * stride;
-                    in[u] = qq < n4;
-                    const long long qc = in[u] ? qq : q;
-                    row[u] = sh >= 0 ? (uint32_t)(qc >> sh) : (uint32_t)((unsigned long long)qc / D4);
-                    bw[u] = bits[row[u] >> 5];
-                    p[u] = ld4(d.p + 4 * qc); m[u] = ld4(d.m + 4 * qc); v[u] = ld4(d.v + 4 * qc);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    if (!in[u] || ((bw[u] >> (row[u] & 31)) & 1u)) continue;
-                    const long long i = 4 * (q + u * stride);
-                    f4a po;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float gu = 0.0f;
-                        if (i + e < d.n_l2) gu = fmaf(d.l2, p[u][e], gu);
-                        m[u][e] = b1 * m[u][e] + c1 * gu;
-                        v[u][e] = b2 * v[u][e] + c2 * gu * gu;
-                        po[e] = p[u][e] - lr_t * m[u][e] / (sqrtf(v[u][e]) + d.eps);
-                    }
-                    st4(d.m + i, m[u]); st4(d.v + i, v[u]); st4(d.p + i, po);
-                }
-            }
-        } else {
-            for (long long i = (long long)tb * NT + threadIdx.x; i < d.n_table; i += stride)
-                if (!touched((uint32_t)((unsigned long long)i / (unsigned)g.D))) update(i, 0.0f);
-        }
-    } else {
-        // table section: 16 bytes per lane per array (4-byte accesses moved 3.2 TB/s on a 188 MB table), two
-        // groups of four in flight per thread; the scalar head / tail (a start or an end that is not a multiple of 4) goes to
-        // the first table block
-        const int nb_table = gridDim.x - nb_dense - nb_lazy - nb_ring;
-        const int tb = bid - nb_dense - nb_lazy;
-        const long long first = nb_lazy > 0 ? (long long)d.lazy_rows * d.lazy_D : 0;   // the lazy part of the table section is not swept
-        constexpr int NT = 64 * ADAM_WAVES;
-        const long long a0 = min((first + 3) & ~3ll, d.n_table);
-        const long long n4 = (d.n_table - a0) >> 2;
-        const float b1 = d.beta1, b2 = d.beta2, c1 = 1.0f - d.beta1, c2 = 1.0f - d.beta2;
-        auto ld4 = [](const float* q) { return STREAM ? __builtin_nontemporal_load(reinterpret_cast<const f4a*>(q)) : *reinterpret_cast<const f4a*>(q); };
-        auto st4 = [](float* q, const f4a v) {
-            if (STREAM) __builtin_nontemporal_store(v, reinterpret_cast<f4a*>(q));
-            else *reinterpret_cast<f4a*>(q) = v;
-        };
-        auto finish4 = [&](long long i, f4a g, const f4a p, f4a m, f4a v) {
-            st4(d.table_grad + i, (f4a){0.f, 0.f, 0.f, 0.f});
-            g *= inv_n;
-            f4a po;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                float gu = g[u];
-                if (i + u < d.n_l2) gu = fmaf(d.l2, p[u], gu);
-                m[u] = b1 * m[u] + c1 * gu;
-                v[u] = b2 * v[u] + c2 * gu * gu;
-                po[u] = p[u] - lr_t * m[u] / (sqrtf(v[u]) + d.eps);
-            }
-            st4(d.m + i, m);
-            st4(d.v + i, v);
-            st4(d.p + i, po);
-        };
-        auto update4 = [&](long long q) {
-            const long long i = a0 + 4 * q;
-            const f4a g = ld4(d.table_grad + i);
-            const f4a p = ld4(d.p + i);
-            const f4a m = ld4(d.m + i), v = ld4(d.v + i);
-            finish4(i, g, p, m, v);
-        };
-        const long long stride = (long long)nb_table * NT;
-        long long q = (long long)tb * NT + threadIdx.x;
-        {
-            // the thread's first group (its only one on a table of a few hundred thousand entries): requested, THEN the scalars
-            const bool have = q < n4;
-            const long long i = a0 + 4 * (have ? q : 0);
-            f4a g = (f4a){0.f, 0.f, 0.f, 0.f}, p = g, m = g, v = g;
-            if (have) {
-                g = ld4(d.table_grad + i);
-                p = ld4(d.p + i);
-                m = ld4(d.m + i);
-                v = ld4(d.v + i);
-            }
-            scalars();
-            if (have) {
-                finish4(i, g, p, m, v);
-                q += stride;
-            }
-        }
-        constexpr int U = STREAM ? 4 : 2;                 // groups of the four arrays requested before the first update
-        for (; q + (U - 1) * stride < n4; q += U * stride) {
-            f4a g[U], p[U], m[U], v[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const long long i = a0 + 4 * (q + u * stride);
-                g[u] = ld4(d.table_grad + i); p[u] = ld4(d.p + i); m[u] = ld4(d.m + i); v[u] = ld4(d.v + i);
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) finish4(a0 + 4 * (q + u * stride), g[u], p[u], m[u], v[u]);
-        }
-        for (; q < n4; q += stride) update4(q);
-        if (tb == 0) {
-            for (long long i = first + threadIdx.x; i < a0; i += NT) {
-                const float g = d.table_grad[i];
-                d.table_grad[i] = 0.0f;
-                update(i, g);
-            }
-            for (long long i = a0 + 4 * n4 + threadIdx.x; i < d.n_table; i += NT) {
-                const float g = d.table_grad[i];
-                d.table_grad[i] = 0.0f;
-                update(i, g);
-            }
-        }
-    }
+    if (bid < b_lazy) adam_dense_block(d, bid, n, t, reinterpret_cast<float (*)[ADAM_COLS]>(part_s));
+    else if (bid < b_units) adam_lazy_rows(d, bid - b_lazy, gr.nb_lazy, n, t);
+    else if constexpr (TG) {
+        if (bid < b_sweep) adam_unit_blocks<LPR, VEC>(d, g, bid - b_units, gr.nb_units, n, t, part_s);
+        else adam_bitmap_sweep<STREAM>(d, g, bid - b_sweep, gr.nb_table, n, t);
+    } else adam_plain_sweep<STREAM>(d, bid - b_sweep, gr.nb_table, gr.nb_lazy > 0, n, t);
     if (bid == 0 && threadIdx.x == 0) {
         d.state[5] = (n > 0.0f ? st[0] / n : 0.0f) + (d.n_l2 > 0 ? d.state[7] : 0.0f);   // loss (sasrec.py:105-110)
         d.state[6] = n > 0.0f ? st[1] / n : 0.0f;        // auc   (sasrec.py:113-115)
@@ -322,72 +310,76 @@ __global__ __launch_bounds__(64 * ADAM_WAVES) void k_adam(cr_adam_desc d, cr_tgr
     }
 }
 
+// Checks the lazy-row, id-ring and index arguments (in cr_adam_step's order of old: each count follows from what was just checked) and
+// lays out the launch's grid; *n_swept: the table elements its sweep blocks walk (decides between the plain and the streaming forms)
+static int adam_grid_of(const cr_adam_desc* d, adam_grid* gr, long long* n_swept) {
+    *gr = adam_grid{cr_ceil_div(d->n_dense, ADAM_COLS), 0, 0, 0, 0};
+    *n_swept = d->n_table;
+    if (d->lazy_ids) {
+        CR_REQUIRE(d->lazy_flags && d->n_lazy_ids > 0 && d->lazy_rows > 0 && d->lazy_D > 0 &&
+                   (long long)d->lazy_rows * d->lazy_D <= d->n_table, "cr_adam_step: bad lazy-row arguments");
+        gr->nb_lazy = cr_ceil_div(d->n_lazy_ids, ADAM_WAVES * 8);            // ~8 ids per wave
+        if (gr->nb_lazy > 4096) gr->nb_lazy = 4096;
+        *n_swept = d->n_table - (long long)d->lazy_rows * d->lazy_D;
+    }
+    const long long groups = *n_swept / 4 + 1;                               // 16-byte groups (+ one block's worth of head / tail)
+    gr->nb_table = (int)((groups + ADAM_NT - 1) / ADAM_NT > 1024 ? 1024 : (groups + ADAM_NT - 1) / ADAM_NT);
+    if (gr->nb_table < 1) gr->nb_table = 1;
+    if (d->ids_ring) {
+        CR_REQUIRE(d->lazy_ids == nullptr, "cr_adam_step: ids_ring and lazy_ids exclude each other (row-sparse Adam reads the step's ids)");
+        CR_REQUIRE(d->ids_dst && d->ids_ring_slots > 0 && d->ids_slot_elems > 0, "cr_adam_step: bad id-ring arguments");
+        CR_REQUIRE(d->ids_copy_elems >= 0 && d->ids_copy_elems <= d->ids_slot_elems, "cr_adam_step: ids_copy_elems exceeds the slot");
+        const long long slot4 = ((d->ids_copy_elems ? d->ids_copy_elems : d->ids_slot_elems) + 3) / 4;
+        gr->nb_ring = (int)((slot4 + ADAM_NT - 1) / ADAM_NT > 256 ? 256 : (slot4 + ADAM_NT - 1) / ADAM_NT);
+    }
+    if (d->tg) {
+        const cr_tgrad_desc* g = d->tg;
+        const char* why = tg_unsupported(g);
+        CR_REQUIRE(why == nullptr, "cr_adam_step: tg: %s", why ? why : "");
+        CR_REQUIRE(d->lazy_ids == nullptr, "cr_adam_step: tg and lazy_ids exclude each other");
+        CR_REQUIRE(d->n_table == ((int64_t)g->lay.V + g->lay.T_pos) * g->D, "cr_adam_step: tg: n_table must be (V + T_pos) * D");
+        CR_REQUIRE((g->ring != nullptr) == (d->ids_ring != nullptr) && (!g->ring || (g->ring == d->ids_ring && g->ring_slots == d->ids_ring_slots && g->slot_words == d->ids_slot_elems)),
+                   "cr_adam_step: tg: the index ring must be the id ring of this launch (or both absent)");
+        gr->nb_units = tg_unit_grid(g);
+    }
+    return 0;
+}
+
+template <bool STREAM, int LPR, int VEC>
+static void adam_launch(const cr_adam_desc* d, const cr_tgrad_desc& g, const adam_grid& gr, void* stream) {
+    hipLaunchKernelGGL((k_adam<STREAM, LPR, VEC>), dim3(gr.nb_dense + gr.nb_lazy + gr.nb_units + gr.nb_table + gr.nb_ring), dim3(ADAM_NT), 0, cr_stream(stream), *d, g, gr);
+}
+
 extern "C" int cr_adam_step(const cr_adam_desc* d, void* stream) {
     CR_REQUIRE(d && d->p && d->m && d->v && d->state, "cr_adam_step: NULL pointer");
     CR_REQUIRE(d->n_table >= 0 && d->n_dense >= 0 && d->n_table + d->n_dense > 0, "cr_adam_step: bad sizes");
     CR_REQUIRE(d->n_table == 0 || d->table_grad || d->tg, "cr_adam_step: table_grad is NULL");
     CR_REQUIRE(d->n_dense == 0 || (d->dense_slabs && d->n_slabs > 0), "cr_adam_step: dense_slabs missing");
     CR_REQUIRE(d->step_snapshot == nullptr || d->stats != nullptr, "cr_adam_step: step_snapshot needs stats (a copy of the sums that does not alias state[0..2])");
-    const int nb_dense = cr_ceil_div(d->n_dense, ADAM_COLS);
-    int nb_lazy = 0;
-    long long n_swept = d->n_table;
-    if (d->lazy_ids) {
-        CR_REQUIRE(d->lazy_flags && d->n_lazy_ids > 0 && d->lazy_rows > 0 && d->lazy_D > 0 &&
-                   (long long)d->lazy_rows * d->lazy_D <= d->n_table, "cr_adam_step: bad lazy-row arguments");
-        nb_lazy = cr_ceil_div(d->n_lazy_ids, ADAM_WAVES * 8);             // ~8 ids per wave
-        if (nb_lazy > 4096) nb_lazy = 4096;
-        n_swept = d->n_table - (long long)d->lazy_rows * d->lazy_D;
-    }
-    constexpr int NT = 64 * ADAM_WAVES;
-    const long long groups = n_swept / 4 + 1;                                 // 16-byte groups (+ one block's worth of head / tail)
-    int nb_table = (int)((groups + NT - 1) / NT > 1024 ? 1024 : (groups + NT - 1) / NT);
-    if (nb_table < 1) nb_table = 1;
-    int nb_ring = 0;
-    if (d->ids_ring) {
-        CR_REQUIRE(d->lazy_ids == nullptr, "cr_adam_step: ids_ring and lazy_ids exclude each other (row-sparse Adam reads the step's ids)");
-        CR_REQUIRE(d->ids_dst && d->ids_ring_slots > 0 && d->ids_slot_elems > 0, "cr_adam_step: bad id-ring arguments");
-        CR_REQUIRE(d->ids_copy_elems >= 0 && d->ids_copy_elems <= d->ids_slot_elems, "cr_adam_step: ids_copy_elems exceeds the slot");
-        const long long slot4 = ((d->ids_copy_elems ? d->ids_copy_elems : d->ids_slot_elems) + 3) / 4;
-        nb_ring = (int)((slot4 + NT - 1) / NT > 256 ? 256 : (slot4 + NT - 1) / NT);
-    }
+    adam_grid gr;
+    long long n_swept;
+    if (const int rc = adam_grid_of(d, &gr, &n_swept)) return rc;
     // read on EVERY call (not cached in a static: a test or a tool that sets it after the process's first step would be ignored);
     // a captured graph keeps the instantiation chosen at capture time -- the variable is not looked at again on replay
     const char* nt_env = getenv("CASTREC_ADAM_STREAM");
     const bool stream_sweep = nt_env ? atoi(nt_env) != 0 : n_swept * 4 >= (256ll << 20);
     cr_tgrad_desc g;
     memset(&g, 0, sizeof(g));
-    int nb_units = 0, lpr = 0, vec = 0;
-    if (d->tg) {
-        g = *d->tg;
-        const char* why = tg_unsupported(&g);
-        CR_REQUIRE(why == nullptr, "cr_adam_step: tg: %s", why ? why : "");
-        CR_REQUIRE(d->lazy_ids == nullptr, "cr_adam_step: tg and lazy_ids exclude each other");
-        CR_REQUIRE(d->n_table == ((int64_t)g.lay.V + g.lay.T_pos) * g.D, "cr_adam_step: tg: n_table must be (V + T_pos) * D");
-        CR_REQUIRE((g.ring != nullptr) == (d->ids_ring != nullptr) && (!g.ring || (g.ring == d->ids_ring && g.ring_slots == d->ids_ring_slots && g.slot_words == d->ids_slot_elems)),
-                   "cr_adam_step: tg: the index ring must be the id ring of this launch (or both absent)");
-        int ent = 0;
-        tg_shape(g.D, &lpr, &vec, &ent);
-        nb_units = tg_unit_grid(&g);
-    }
-    const dim3 grid(nb_dense + nb_lazy + nb_units + nb_table + nb_ring);
-#define ADAM_LAUNCH(S, L, V) hipLaunchKernelGGL((k_adam<S, L, V>), grid, dim3(NT), 0, cr_stream(stream), *d, g, nb_dense, nb_lazy, nb_units, nb_ring)
     if (!d->tg) {
-        if (stream_sweep) ADAM_LAUNCH(true, 0, 1);
-        else ADAM_LAUNCH(false, 0, 1);
-    } else if (vec == 4 && lpr == 64) {
-        if (stream_sweep) ADAM_LAUNCH(true, 64, 4);
-        else ADAM_LAUNCH(false, 64, 4);
-    } else if (vec == 4 && lpr == 32) {
-        if (stream_sweep) ADAM_LAUNCH(true, 32, 4);
-        else ADAM_LAUNCH(false, 32, 4);
-    } else if (vec == 4) ADAM_LAUNCH(false, 16, 4);
-    else if (vec == 2 && lpr == 64) ADAM_LAUNCH(false, 64, 2);
-    else if (vec == 2 && lpr == 32) ADAM_LAUNCH(false, 32, 2);
-    else if (vec == 2) ADAM_LAUNCH(false, 16, 2);
-    else if (lpr == 64) ADAM_LAUNCH(false, 64, 1);
-    else if (lpr == 32) ADAM_LAUNCH(false, 32, 1);
-    else ADAM_LAUNCH(false, 16, 1);
-#undef ADAM_LAUNCH
+        stream_sweep ? adam_launch<true, 0, 1>(d, g, gr, stream) : adam_launch<false, 0, 1>(d, g, gr, stream);
+    } else {
+        g = *d->tg;
+        int lpr = 0, vec = 0, ent = 0;
+        tg_shape(g.D, &lpr, &vec, &ent);
+        tg_dispatch(lpr, vec, [&](auto L, auto V, auto) {
+            constexpr int LPR = decltype(L)::value, VEC = decltype(V)::value;
+            // (a STREAM form exists for these two shapes only: ADVICE.md item 4)
+            if constexpr (VEC == 4 && LPR >= 32) {
+                if (stream_sweep) return adam_launch<true, LPR, VEC>(d, g, gr, stream);
+            }
+            adam_launch<false, LPR, VEC>(d, g, gr, stream);
+        });
+    }
     return cr_check_launch("cr_adam_step");
 }
 

@@ -1,8 +1,6 @@
 // cr_table_grad: the table section's gradient of a step WRITTEN from the batch's occurrence index (include/castrec.h, "occurrence
 // index"; device code: cr_tgrad.hpp) -- the data-parallel path, whose gradient bucket is all-reduced before Adam runs.  The
 // one-GPU step never materialises the table gradient: cr_adam_step sums each listed row and updates it in place (cr_adam.hip).
-#include <string.h>
-
 #include <stdlib.h>
 #include "cr_tgrad.hpp"
 
@@ -35,16 +33,8 @@ extern "C" int cr_table_grad(const cr_tgrad_desc* d, float* table_grad, void* st
     int lpr = 0, vec = 0, ent = 0;
     tg_shape(d->D, &lpr, &vec, &ent);
     const dim3 grid((unsigned)tg_unit_grid(d));
-#define TG_LAUNCH(L, V, E) hipLaunchKernelGGL((k_table_grad<L, V, E>), grid, dim3(TG_NT), 0, cr_stream(stream), *d, table_grad)
-    if (vec == 4 && lpr == 64) TG_LAUNCH(64, 4, 8);
-    else if (vec == 4 && lpr == 32) TG_LAUNCH(32, 4, 8);
-    else if (vec == 4) TG_LAUNCH(16, 4, 8);
-    else if (vec == 2 && lpr == 64) TG_LAUNCH(64, 2, 16);
-    else if (vec == 2 && lpr == 32) TG_LAUNCH(32, 2, 16);
-    else if (vec == 2) TG_LAUNCH(16, 2, 16);
-    else if (lpr == 64) TG_LAUNCH(64, 1, 16);
-    else if (lpr == 32) TG_LAUNCH(32, 1, 16);
-    else TG_LAUNCH(16, 1, 16);
-#undef TG_LAUNCH
+    tg_dispatch(lpr, vec, [&](auto L, auto V, auto E) {
+        hipLaunchKernelGGL((k_table_grad<decltype(L)::value, decltype(V)::value, decltype(E)::value>), grid, dim3(TG_NT), 0, cr_stream(stream), *d, table_grad);
+    });
     return cr_check_launch("cr_table_grad");
 }

@@ -16,6 +16,7 @@
 // Every load of a batch is unconditional (absent entries read row 0 with a zero coefficient, a pos / neg entry reads its row twice
 // instead of a second partial): no branch stands between two loads.
 #pragma once
+#include <type_traits>
 #include "cr_common.hpp"
 
 #define TG_NT 1024
@@ -107,7 +108,7 @@ __device__ __forceinline__ void tg_unit_blocks(const cr_tgrad_desc& g, const int
     for (int u = ub; u < n_blocks; u += nub) {
         if (u != ub) rec = *reinterpret_cast<const int4*>(recs + 4 * ((size_t)u * NG + grp));
         const uint32_t info = (uint32_t)rec.w;
-        const int q = info & 63, k = (info >> 6) & 127, sidx = (info >> 13) & 511, nsl = info >> 22;
+        const int q = info & 63, k = (info >> 6) & 127;
         float acc[VEC];
         tg_batch<LPR, VEC, ENT>(g, occ, rec.y, rec.z, col, acc);     // (an idle group: count 0, every coefficient 0)
 #pragma unroll
@@ -155,7 +156,6 @@ __device__ __forceinline__ void tg_unit_blocks(const cr_tgrad_desc& g, const int
                 }
                 if (colok) consume(rec.x, col0, t);
             }
-            (void)sidx; (void)nsl;
         } else if (head && colok) {
             consume(rec.x, col0, t);
         }
@@ -163,12 +163,29 @@ __device__ __forceinline__ void tg_unit_blocks(const cr_tgrad_desc& g, const int
     }
 }
 
+// occurrences per lane group at a vector width (16-byte loads: 8 in flight fill the registers that 16 narrower ones do)
+constexpr int tg_ent(int vec) { return vec == 4 ? 8 : 16; }
 // (lanes per row, floats per lane, occurrences per lane group) for a hidden size; false = not covered
 static inline bool tg_shape(int D, int* lpr, int* vec, int* ent) {
-    if (D >= 1 && D % 4 == 0 && D <= 256) { *vec = 4; *lpr = D <= 64 ? 16 : (D <= 128 ? 32 : 64); *ent = 8; return true; }
-    if (D >= 1 && D % 2 == 0 && D <= 128) { *vec = 2; *lpr = D <= 32 ? 16 : (D <= 64 ? 32 : 64); *ent = 16; return true; }
-    if (D >= 1 && D <= 64) { *vec = 1; *lpr = D <= 16 ? 16 : (D <= 32 ? 32 : 64); *ent = 16; return true; }
+    if (D >= 1 && D % 4 == 0 && D <= 256) { *vec = 4; *lpr = D <= 64 ? 16 : (D <= 128 ? 32 : 64); *ent = tg_ent(4); return true; }
+    if (D >= 1 && D % 2 == 0 && D <= 128) { *vec = 2; *lpr = D <= 32 ? 16 : (D <= 64 ? 32 : 64); *ent = tg_ent(2); return true; }
+    if (D >= 1 && D <= 64) { *vec = 1; *lpr = D <= 16 ? 16 : (D <= 32 ? 32 : 64); *ent = tg_ent(1); return true; }
     return false;
+}
+// f(LPR, VEC, ENT) with a shape of tg_shape as three compile-time constants (tg_c): the one place where a shape becomes an
+// instantiation, for cr_table_grad and cr_adam_step alike.  (lpr, vec) MUST come from tg_shape: anything else lands in <16, ., 1>.
+template <int N> using tg_c = std::integral_constant<int, N>;
+template <int VEC, typename F>
+static inline void tg_dispatch_lpr(int lpr, F&& f) {
+    if (lpr == 64) f(tg_c<64>(), tg_c<VEC>(), tg_c<tg_ent(VEC)>());
+    else if (lpr == 32) f(tg_c<32>(), tg_c<VEC>(), tg_c<tg_ent(VEC)>());
+    else f(tg_c<16>(), tg_c<VEC>(), tg_c<tg_ent(VEC)>());
+}
+template <typename F>
+static inline void tg_dispatch(int lpr, int vec, F&& f) {
+    if (vec == 4) tg_dispatch_lpr<4>(lpr, f);
+    else if (vec == 2) tg_dispatch_lpr<2>(lpr, f);
+    else tg_dispatch_lpr<1>(lpr, f);
 }
 static inline const char* tg_unsupported(const cr_tgrad_desc* g) {
     if (!g) return "NULL description";

@@ -704,7 +704,7 @@ typedef struct {
     const float* seq_emb; int ld_emb;
     const float* coef;                /* [2, M] */
     int D;
-    float* part_rows; uint32_t* tickets;   /* workspace of the sliced rows: [lay.cap_blocks, D] floats and [lay.cap_blocks] words, the
+    float* part_rows; uint32_t* tickets;   /* workspace of the sliced rows: [lay.cap_blocks, (D + 3) & ~3] floats and [lay.cap_blocks] words, the
                                               words ZERO before the first launch (every launch leaves them zero) */
 } cr_tgrad_desc;
 int cr_table_grad(const cr_tgrad_desc* d, float* table_grad, void* stream);

@@ -2,6 +2,7 @@
 plain restatement (no GPU), and -- on the GPU -- the gather it drives against the scatter it replaces (autodiff of modules.py:157
 through sasrec.py:27, of sasrec.py:89-90 and of the learned positional lookup sasrec.py:40-50)."""
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -124,6 +125,52 @@ def test_geometry_of_the_gather():
         assert L.lib.cr_tgrad_geometry(D, C.byref(ng), C.byref(ent)) == 1 and (ng.value, ent.value) == want, D
     for D in (0, 65, 67, 130, 260, 512):
         assert L.lib.cr_tgrad_geometry(D, C.byref(ng), C.byref(ent)) == 0, D
+
+
+_DISPATCH_PROBE = r"""
+#include <stdio.h>
+#include "cr_tgrad.hpp"
+int main() {
+    for (int D = 1; D <= 256; ++D) {
+        int lpr = 0, vec = 0, ent = 0, got[3] = {0, 0, 0};
+        if (tg_shape(D, &lpr, &vec, &ent))
+            tg_dispatch(lpr, vec, [&](auto L, auto V, auto E) { got[0] = decltype(L)::value; got[1] = decltype(V)::value; got[2] = decltype(E)::value; });
+        printf("%d %d %d %d %d %d %d\n", D, lpr, vec, ent, got[0], got[1], got[2]);
+    }
+    return 0;
+}
+"""
+
+
+def test_dispatch_shape_and_geometry_agree_for_every_hidden_size(tmp_path):
+    """tg_dispatch (cr_tgrad.hpp: the one place where a shape becomes an instantiation of k_table_grad and k_adam) hands out exactly
+    the constants tg_shape chose, for every D in 1..256; cr_tgrad_geometry covers the same hidden sizes with 1024 / LPR lane groups
+    and the same ENT; the shapes are the rule of the header restated here, nine in all.  Host code only: compiled without device pass."""
+    import subprocess
+    from castrec_amd import build as B
+    src = tmp_path / "dispatch_probe.cpp"
+    src.write_text(_DISPATCH_PROBE)
+    exe = tmp_path / "dispatch_probe"
+    r = subprocess.run([B._hipcc(), "-x", "hip", "--cuda-host-only", "-std=c++17", "-I", os.path.join(B.ROOT, "include"), "-I", B.CSRC,
+                        str(src), "-o", str(exe)], capture_output=True, text=True)      # (the compiler build() itself needs)
+    assert r.returncode == 0, r.stderr
+    rows = [[int(x) for x in l.split()] for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()]
+    assert [r[0] for r in rows] == list(range(1, 257))
+    by_width = lambda D, a, b: 16 if D <= a else 32 if D <= b else 64
+    ng, ent = C.c_int(), C.c_int()
+    seen = set()
+    for D, lpr, vec, e, L_, V_, E_ in rows:
+        want = (by_width(D, 64, 128), 4) if D % 4 == 0 else (by_width(D, 32, 64), 2) if D % 2 == 0 and D <= 128 else \
+            (by_width(D, 16, 32), 1) if D % 2 == 1 and D <= 64 else None
+        ok = L.lib.cr_tgrad_geometry(D, C.byref(ng), C.byref(ent))
+        if want is None:
+            assert (lpr, vec, e, L_, V_, E_) == (0, 0, 0, 0, 0, 0) and ok == 0, D
+            continue
+        assert (lpr, vec) == want and e == (8 if vec == 4 else 16), D
+        assert (L_, V_, E_) == (lpr, vec, e), D               # the dispatch: the same three constants
+        assert ok == 1 and (ng.value, ent.value) == (1024 // lpr, e), D
+        seen.add((lpr, vec))
+    assert seen == {(l, v) for l in (16, 32, 64) for v in (1, 2, 4)}
 
 
 # ---- GPU: the gather against the scatter -------------------------------------------------------------------
