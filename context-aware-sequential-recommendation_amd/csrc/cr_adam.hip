@@ -159,12 +159,14 @@ __device__ __forceinline__ void adam_dense_block(const cr_adam_desc& d, int b, f
 }
 
 // lazy rows: wave w of the nb_lazy blocks walks ids w, w + W, ...; the first wave to swap the step number into a row's flag owns the
-// row (every other occurrence of the id finds it there and moves on)
+// row (every other occurrence of the id finds it there and moves on).  The ids: lazy_ids followed by lazy_ids2 (where set) -- two
+// buffers walked as one list, no copy that joins them (the host has checked that the sum of the counts fits an int)
 __device__ __forceinline__ void adam_lazy_rows(const cr_adam_desc& d, int b, int nb_lazy, float n, uint32_t t) {
     const int lane = threadIdx.x & 63, W = nb_lazy * ADAM_WAVES;
+    const int n_ids = d.n_lazy_ids + (d.lazy_ids2 ? d.n_lazy_ids2 : 0);
     const adam_consts k = adam_scalars(d, n, t);
-    for (int j = b * ADAM_WAVES + (threadIdx.x >> 6); j < d.n_lazy_ids; j += W) {
-        const int id = d.lazy_ids[j];
+    for (int j = b * ADAM_WAVES + (threadIdx.x >> 6); j < n_ids; j += W) {
+        const int id = j < d.n_lazy_ids ? d.lazy_ids[j] : d.lazy_ids2[j - d.n_lazy_ids];
         if (id <= 0 || id >= d.lazy_rows) continue;      // row 0: the zero-pad row never has a gradient
         int mine = 0;
         if (lane == 0) mine = atomicExch(&d.lazy_flags[id], t) != t;
@@ -315,10 +317,17 @@ __global__ __launch_bounds__(ADAM_NT) void k_adam(cr_adam_desc d, cr_tgrad_desc 
 static int adam_grid_of(const cr_adam_desc* d, adam_grid* gr, long long* n_swept) {
     *gr = adam_grid{cr_ceil_div(d->n_dense, ADAM_COLS), 0, 0, 0, 0};
     *n_swept = d->n_table;
+    CR_REQUIRE(d->lazy_ids2 == nullptr || d->lazy_ids != nullptr, "cr_adam_step: lazy_ids2 needs lazy_ids (it is a second list of the same row-sparse update)");
     if (d->lazy_ids) {
         CR_REQUIRE(d->lazy_flags && d->n_lazy_ids > 0 && d->lazy_rows > 0 && d->lazy_D > 0 &&
                    (long long)d->lazy_rows * d->lazy_D <= d->n_table, "cr_adam_step: bad lazy-row arguments");
-        gr->nb_lazy = cr_ceil_div(d->n_lazy_ids, ADAM_WAVES * 8);            // ~8 ids per wave
+        int n_ids = d->n_lazy_ids;
+        if (d->lazy_ids2) {
+            CR_REQUIRE(d->n_lazy_ids2 >= 1, "cr_adam_step: lazy_ids2 is set but n_lazy_ids2 = %d (at least one id)", d->n_lazy_ids2);
+            CR_REQUIRE((long long)d->n_lazy_ids + d->n_lazy_ids2 <= 0x7fffffffll, "cr_adam_step: lazy_ids2: n_lazy_ids + n_lazy_ids2 does not fit an int");
+            n_ids += d->n_lazy_ids2;
+        }
+        gr->nb_lazy = cr_ceil_div(n_ids, ADAM_WAVES * 8);                    // ~8 ids per wave
         if (gr->nb_lazy > 4096) gr->nb_lazy = 4096;
         *n_swept = d->n_table - (long long)d->lazy_rows * d->lazy_D;
     }

@@ -66,7 +66,7 @@ class Hyper:
     def __init__(self, args=None, **kw):
         d = dict(maxlen=50, hidden_units=50, num_blocks=2, num_heads=1, dropout_rate=0.5, l2_emb=0.0, lr=1e-3,
                  max_bins=200, num_context_blocks=2, seed=42, loss="bce", ce_negatives=256, gbce_t=0.75, ce_proposal="uniform",
-                 ce_pop_power=1.0)
+                 ce_pop_power=1.0, row_sparse_adam=False)
         for k in d:
             if args is not None and hasattr(args, k):
                 d[k] = getattr(args, k)
@@ -195,7 +195,8 @@ class ParamLayout:
 class Engine:
     def __init__(self, model, usernum, itemnum, hp, batch_size, training=True, seed=None, n_slabs=None,
                  share=None, batch_global=None, row_offset=0, want_attn=False, device="cuda", fused=None,
-                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None, gbce_t=None, ce_proposal=None):
+                 attn_precision=None, lazy_adam=None, loss=None, ce_negatives=None, gbce_t=None, ce_proposal=None,
+                 row_sparse_adam=None):
         """loss: the training objective, "bce" (the default: hp.loss, else "bce") or "ce" -- full-catalogue softmax cross-entropy
         (cr_softmax_ce).  Under "ce" the prediction head is one cr_softmax_ce launch that stores d(seq_emb) and accumulates the item
         table's gradient into Gt; the occurrence index and the head fusions are off, so the embedding backward scatters with float
@@ -203,7 +204,7 @@ class Engine:
         (ValueError).  Eval engines ignore the option.
         "sampled_ce" takes the route of "ce" with one cr_sampled_ce launch: the softmax over each row's target and ce_negatives
         (default hp.ce_negatives, else 256) item ids drawn uniformly on the device for the whole batch from the engine's seed and step
-        word; eng.samples holds the last step's ids.  It refuses what "ce" refuses and ce_negatives outside 1..CR_SCE_MAX_SAMPLES.
+        word; eng.samples holds the last step's ids.  It refuses what "ce" refuses (row_sparse_adam apart, below) and ce_negatives outside 1..CR_SCE_MAX_SAMPLES.
         "gbce" takes the route of "sampled_ce" with one cr_gbce launch: binary cross-entropy over the target and ce_negatives shared
         uniform negatives, the positive term weighted by eng.gbce_beta = 1 - t (1 - alpha), alpha = min(1, ce_negatives / max(1,
         itemnum - 1)) the sampling rate over the items that are not the target and t = gbce_t (default hp.gbce_t, else 0.75; the
@@ -212,7 +213,13 @@ class Engine:
         derived for uniform sampling).  Under "popularity" the samples are drawn from the item weights of set_item_weights() -- a step
         before the first call raises RuntimeError -- and every candidate's logit, the target's included, is corrected by -log Q; the
         device arrays item_cdf / item_logq [itemnum + 1] are allocated here and rewritten in place, so a captured graph follows a new
-        set of weights.  Still one cr_sampled_ce launch: the launch list is "sampled_ce"'s.  Eval engines ignore the option."""
+        set of weights.  Still one cr_sampled_ce launch: the launch list is "sampled_ce"'s.  Eval engines ignore the option.
+        row_sparse_adam (default hp.row_sparse_adam, else False): Adam moves only the item rows that have a gradient in the step -- a
+        DEVIATION from the reference's dense update.  Taken by "bce" (rows seq | pos | neg: the engine of
+        lazy_adam=True), "sampled_ce" and "gbce" (rows seq | pos and the step's samples, read by the Adam launch from eng.samples where
+        the loss launch left them: neg has no gradient under these losses and is not listed); "ce" refuses it (every item row has a
+        gradient).  It sets eng.lazy_adam.  The older spelling lazy_adam=True / CASTREC_LAZY_ADAM=1 lists seq | pos | neg only and
+        stays refused for the three softmax-route losses."""
         if model not in MODELS:
             raise ValueError("model must be one of %s" % MODELS)
         if not torch.cuda.is_available():
@@ -232,6 +239,9 @@ class Engine:
         # row-sparse Adam on the item table (DEVIATION from the reference's dense update, for tables like C5's 10 M rows;
         # castrec.h cr_adam_desc.lazy_ids): off unless asked for
         self.lazy_adam = bool(int(os.environ.get("CASTREC_LAZY_ADAM", "0"))) if lazy_adam is None else bool(lazy_adam)
+        if row_sparse_adam is None:
+            row_sparse_adam = getattr(hp, "row_sparse_adam", False)
+        row_sparse_adam = bool(row_sparse_adam)
         if loss is None:
             loss = getattr(hp, "loss", None) or "bce"
         if loss not in ALL_LOSSES:
@@ -254,8 +264,11 @@ class Engine:
                              "sampling; bce and ce draw no shared negatives)" % self.loss)
         if self.loss in SOFTMAX_LOSSES:
             op = {"ce": "cr_softmax_ce", "sampled_ce": "cr_sampled_ce", "gbce": "cr_gbce"}[self.loss]
-            if self.lazy_adam:
+            if self.loss == "ce" and (self.lazy_adam or row_sparse_adam):
                 raise ValueError("loss='%s' does not take row-sparse Adam (lazy_adam): every item row has a gradient" % self.loss)
+            if self.lazy_adam:
+                raise ValueError("loss='%s' does not take lazy_adam / CASTREC_LAZY_ADAM (its id list is seq | pos | neg: the step's samples "
+                                 "have a gradient too); ask for row_sparse_adam=True, which lists them" % self.loss)
             if (batch_global is not None and batch_global != batch_size) or row_offset:
                 raise ValueError("loss='%s' does not take data parallelism (the item table's gradient is not in the exchanged bucket)"
                                  % self.loss)
@@ -270,6 +283,10 @@ class Engine:
             # the sampling rate over the pool of negatives (the itemnum - 1 items that are not the target), gSASRec eq. for beta
             alpha = min(1.0, self.ce_negatives / max(1, itemnum - 1))
             self.gbce_beta = 1.0 - self.gbce_t * (1.0 - alpha)
+        # the public spelling of the row-sparse update: from here on everything (dist.py, models.py, set_step) reads lazy_adam alone
+        self.row_sparse_adam = row_sparse_adam
+        if row_sparse_adam:
+            self.lazy_adam = True
         self.M = self.B * self.T
         self.usernum, self.itemnum = usernum, itemnum
         self.training = training
@@ -1234,13 +1251,20 @@ class Engine:
             snap, tsnap = self.state.data_ptr() + 4 * 8, self.state.data_ptr() + 4 * 11
             l2 = float(self.hp.l2_emb)
             n_l2 = lay.n_l2 if l2 != 0.0 else 0
-            lazy = (None, 0, 0, 0, None)
+            lazy, lazy2 = (None, 0, 0, 0, None), None
             if self.lazy_adam:
                 self.lazy_flags = torch.zeros(self.itemnum + 1, dtype=torch.int32, device=self.dev)
                 world = max(1, self.batch_global // self.B)
                 # this step's seq | pos | neg ids; under data parallelism the ids of ALL ranks (the sparse exchange hands
                 # them over, dist.DataParallel.exchange): every replica must update the same rows
                 self.lazy_ids = self.ids_all[:3].reshape(-1) if world == 1 else torch.zeros(world * 3 * self.M, dtype=torch.int32, device=self.dev)
+                if self.loss in SAMPLED_LOSSES:
+                    # the rows with a gradient: seq (embedding backward) | pos (the target term) and the step's samples, which the
+                    # Adam launch reads where the loss launch wrote them (cr_adam_desc.lazy_ids2) -- neg only feeds the AUC here, and
+                    # listing it would move rows the loss never touched on their momentum
+                    assert world == 1
+                    self.lazy_ids = self.ids_all[:2].reshape(-1)
+                    lazy2 = self.samples
                 lazy = (self.lazy_ids.data_ptr(), self.lazy_ids.numel(), self.itemnum + 1, self.D, self.lazy_flags.data_ptr())
             # slabs in use per 256-parameter block: n_wslabs where cr_gemm_wgrad is the only writer, n_slabs elsewhere
             counts = None
@@ -1272,10 +1296,14 @@ class Engine:
                                         se.data_ptr(), se.shape[1], self._head_coef(), self.D, self._tg_part.data_ptr(), self._tg_tickets.data_ptr())
                 ad.tg = C.pointer(self._tgd)
                 self._tgrad = ("cr_table_grad", L.lib.cr_table_grad, (C.byref(self._tgd), self.Gt.data_ptr()))
+            if lazy2 is not None:
+                ad.lazy_ids2, ad.n_lazy_ids2 = lazy2.data_ptr(), lazy2.numel()
             self._adam = ("cr_adam_step", L.lib.cr_adam_step, (C.byref(ad),))
             ad1 = L.AdamDesc(self.P.data_ptr(), self.Mom.data_ptr(), self.Vel.data_ptr(), self.Gt.data_ptr(),
                              self.Gflat.data_ptr() + 4 * lay.n_table, lay.n_table, lay.n_dense, 1, float(self.hp.lr), 0.9, 0.98,
                              1e-8, self.state.data_ptr(), self.Gflat.data_ptr() + 4 * lay.n_total, tsnap, l2, n_l2, *lazy, None)
+            if lazy2 is not None:
+                ad1.lazy_ids2, ad1.n_lazy_ids2 = lazy2.data_ptr(), lazy2.numel()
             self._adam_flat = ("cr_adam_step", L.lib.cr_adam_step, (C.byref(ad1),))
             self._reduce = ("cr_reduce_slabs", L.lib.cr_reduce_slabs,
                             (self.Gs.data_ptr(), self.n_slabs, lay.n_dense, self.Gflat.data_ptr() + 4 * lay.n_table,

@@ -140,7 +140,7 @@ class AdamDesc(C.Structure):
                 ("beta2", c_f), ("eps", c_f), ("state", c_p), ("stats", c_p), ("step_snapshot", c_p), ("l2", c_f), ("n_l2", C.c_int64),
                 ("lazy_ids", c_p), ("n_lazy_ids", c_i), ("lazy_rows", c_i), ("lazy_D", c_i), ("lazy_flags", c_p), ("slab_counts", c_p),
                 ("ids_ring", c_p), ("ids_ring_slots", c_i), ("ids_slot_elems", C.c_int64), ("ids_dst", c_p),
-                ("ids_copy_elems", C.c_int64), ("tg", C.POINTER(TgradDesc))]
+                ("ids_copy_elems", C.c_int64), ("tg", C.POINTER(TgradDesc)), ("lazy_ids2", c_p), ("n_lazy_ids2", c_i)]
 
 
 CR_TOPK_MAX = 128

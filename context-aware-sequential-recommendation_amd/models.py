@@ -158,7 +158,8 @@ class _Model(object):
         dp_cfg = getattr(self, "_dp_cfg", None)
         data_parallel = getattr(self, "_dp", None) is not None or (dp_cfg is not None and dp_cfg[1] > 1)
         # (row-sparse Adam: the engine's own setting once it exists, before that what it will read -- Engine.__init__)
-        lazy = self._train.lazy_adam if self._train is not None else bool(int(os.environ.get("CASTREC_LAZY_ADAM", "0")))
+        lazy = self._train.lazy_adam if self._train is not None else (bool(int(os.environ.get("CASTREC_LAZY_ADAM", "0")))
+                                                                       or bool(getattr(getattr(self, "hp", None), "row_sparse_adam", False)))
         if not self._graph or data_parallel or self._batch_global is not None or lazy:
             return 1
         return max(1, int(os.environ.get("CASTREC_STEPS_PER_GRAPH", "4")))

@@ -249,10 +249,12 @@ def gbce(seq_emb, ld, table, pos, state, workspace, M, N, beta=1.0, precision=L.
 
 def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, state, beta1=0.9, beta2=0.98, eps=1e-8,
               stats=None, step_snapshot=None, lazy_ids=None, lazy_rows=0, lazy_D=0, lazy_flags=None, l2=0.0, n_l2=0,
-              slab_counts=None, ids_ring=None, ids_ring_slots=0, ids_slot_elems=0, ids_dst=None, ids_copy_elems=0, tg=None):
+              slab_counts=None, ids_ring=None, ids_ring_slots=0, ids_slot_elems=0, ids_dst=None, ids_copy_elems=0, tg=None,
+              lazy_ids2=None):
     """cr_adam_step (castrec.h cr_adam_desc).  l2 / n_l2: the embedding regulariser on the first n_l2 parameters; slab_counts: int32
     [ceil(n_dense / 256)]; ids_ring .. ids_copy_elems: the id ring whose next slot this launch moves to ids_dst; tg: an L.TgradDesc
-    (the table section's gradient from the occurrence index; table_grad may then be None)."""
+    (the table section's gradient from the occurrence index; table_grad may then be None); lazy_ids2: a second int32 device list of
+    rows for the row-sparse update (with lazy_ids only)."""
     d = L.AdamDesc(_p(p), _p(m), _p(v), _p(table_grad), _p(dense_slabs), n_table, n_dense, n_slabs, lr, beta1, beta2,
                    eps, _p(state), _p(stats) if stats is not None else None,
                    _p(step_snapshot) if step_snapshot is not None else None, float(l2), int(n_l2),
@@ -261,6 +263,8 @@ def adam_step(p, m, v, table_grad, dense_slabs, n_table, n_dense, n_slabs, lr, s
                    _p(_i32(ids_dst, "ids_dst")), int(ids_copy_elems))
     if tg is not None:
         d.tg = C.pointer(tg)
+    if lazy_ids2 is not None:
+        d.lazy_ids2, d.n_lazy_ids2 = _p(_i32(lazy_ids2, "lazy_ids2")), lazy_ids2.numel()
     L.call("cr_adam_step", C.byref(d), _stream())
 
 

@@ -749,6 +749,13 @@ typedef struct {
     const cr_tgrad_desc* tg;          /* optional (host pointer, copied at launch): the table section's gradient comes from the batch's
                                          occurrence index (cr_table_grad's description, its ring fields = this ring); table_grad is then
                                          not read and may be NULL.  Not together with lazy_ids. */
+    /* Optional, with lazy_ids only: a SECOND list of rows for the row-sparse update, walked behind lazy_ids as if the two were one
+     * list -- same rules: duplicates allowed (within a list and across the two), ids <= 0 or >= lazy_rows skipped, each row claimed
+     * once through lazy_flags.  n_lazy_ids2 >= 1 where the pointer is set, and n_lazy_ids + n_lazy_ids2 must fit an int; with NULL the
+     * launch is what it is without the field.  Device memory that earlier work on the same stream may have written: the engine
+     * passes cr_sampled_ce's / cr_gbce's samples_out, the one id list of a sampled step that no host buffer holds (the rows with a
+     * gradient are then seq | pos in lazy_ids and the step's draw here), so a captured graph follows every step's draw. */
+    const int32_t* lazy_ids2; int n_lazy_ids2;
 } cr_adam_desc;
 int cr_adam_step(const cr_adam_desc* d, void* stream);
 

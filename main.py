@@ -72,6 +72,10 @@ def parse_args(argv=None):
                              'occurrences in the training split + 1)^ce_pop_power, with the log-Q correction on every logit')
     parser.add_argument('--ce_pop_power', type=float, default=1.0,
                         help='popularity proposal: the exponent on the item counts (1 = unigram, 0.75 = word2vec\'s, 0 = uniform)')
+    parser.add_argument('--row_sparse_adam', action='store_true',
+                        help='Adam moves only the item rows that have a gradient in the step (bce: seq, pos and neg ids; sampled_ce, '
+                             'gbce: seq and pos ids and the step\'s shared negatives) -- a deviation from the reference\'s dense update, '
+                             'which moves every row on its momentum; for large catalogues.  Every loss but ce')
     return parser.parse_args(argv)
 
 
