@@ -1,10 +1,15 @@
 """Static forward/backward programs of the SASRec / CAST graphs, composed of libcastrec kernels.
 
 The reference builds a TensorFlow graph once (models/sasrec.py, models/cast_N.py) and runs it with
-``sess.run``; here the graph of a model is compiled ONCE into two flat lists of pre-built C-ABI
-launches (forward, backward) over persistent device buffers, which makes the whole step capturable
-as a HIP graph (launch-bound problem sizes).  Gradients are hand-derived per op; there is no autograd
-and no CPU fallback.
+``sess.run``; here the graph of a model is compiled ONCE into flat lists of pre-built C-ABI launches
+over persistent device buffers -- ``fwd`` and ``bwd``, and the single entries that end a step: ``_l2``,
+``_adam`` (plain step), ``_tgrad`` / ``_reduce`` / ``_adam_flat`` (data-parallel step) -- which makes
+the whole step capturable as a HIP graph (launch-bound problem sizes).  Gradients are hand-derived per
+op; there is no autograd and no CPU fallback.
+
+The launch planner is Engine.op_embed .. Engine._finalize: every op_* emits its
+forward launches and registers a factory for its backward, which _finalize runs in reverse order; every
+environment switch is a field of Switches, read once per engine.
 
 Memory layout (all fp32, resident in HBM for the life of the engine):
   P / M / V   flat parameter, Adam-m, Adam-v vectors: [table section | dense section]
@@ -17,6 +22,8 @@ import ctypes as C
 import math
 import os
 import zlib
+from collections import namedtuple
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -191,6 +198,58 @@ class ParamLayout:
         return flat
 
 
+# ---- the launch planner's switches and records ------------------------------------------------------
+class Switches(NamedTuple):
+    """The environment switches of the engine (field x is CASTREC_X), read once at the top of Engine.__init__.  A flag is on when
+    its variable is "1" (bf_two_kernels: when it is set at all); each line says what it turns off and what runs instead."""
+    two_pass_attn_bwd: bool    # fp32 attention, one head: no delta / dQ partials from the FFN backward -> two-pass cr_attn_bwd
+    no_tails: bool             # the next block's LN1 + QKV, the final LayerNorm inside the FFN kernel -> cr_block_ln_ffn_fwd, own launches
+    no_embed_fusion: bool      # a stack's input gathered by its first kernel -> cr_embed_fwd in front of the stack
+    no_stack_kernel: bool      # up to four blocks forward in one cr_stack_fwd -> cr_block_* / cr_attn_fwd per block
+    no_stack_bwd: bool         # register-layout row phases backward (cr_stack_*_bwd*) and their slab count -> cr_block_ln_*_bwd
+    no_wide: bool              # D = 128 / 192 / 256 row phases as cr_wide_* -> cr_layernorm_* / cr_gemm_rows / cr_eltwise
+    no_block_bwd: bool         # a block's backward as one cr_stack_block_bwd -> cr_stack_ffn_bwd*, cr_attn_bwd, cr_stack_qkv_bwd*
+    no_head_ln: bool           # the final LayerNorm's backward inside the head -> cr_head_fwd_bwd + cr_layernorm_bwd
+    no_id_check: bool          # (no planner switch) set_batch() / feed() do not range check host ids
+    no_head_fusion: bool       # the head as the tail of the last forward launch (and its 2 B slabs) -> cr_head_fwd_bwd_ln
+    wslabs: int                # (default 32) slabs of cr_gemm_wgrad at D > 128 outside the fused path: n_wslabs = min(n_slabs, this)
+    no_index: bool             # table gradients by the occurrence index's gather -> float atomics from head and embedding backward
+    wide_no_wgrad: bool        # D = 128: cr_wide_* form the weight gradients themselves -> cr_gemm_wgrad
+    wide_no_delta: bool        # cr_wide_ln_ffn_bwd emits the per-head delta -> two-launch cr_attn_bwd
+    bf_two_kernels: bool       # (also read by the C side) one-launch bf16 attention backward: no per-head delta is asked for
+    no_head_delta: bool        # two heads at D = 64: cr_stack_ffn_bwd_heads -> cr_stack_ffn_bwd / _ln, two-launch cr_attn_bwd
+    wide_no_tails: bool        # D = 128: cr_wide_ln_ffn_fwd_tail -> cr_wide_ln_ffn_fwd + cr_wide_ln_qkv_fwd / cr_layernorm_fwd
+    no_lnf_fusion: bool        # a stack's final LayerNorm backward inside its last block's backward -> cr_layernorm_bwd
+    stack_pair_max_b: int      # (default 160) batch sizes up to which n_kernel_launches() counts a launch per block of cr_stack_fwd
+    lazy_adam: bool            # default of Engine(lazy_adam=None): row-sparse Adam over seq | pos | neg
+    attn_precision: str        # default of Engine(attn_precision=None), in front of hp.attn_precision; None: unset or empty
+
+    @classmethod
+    def from_env(cls, env):
+        on = lambda f: env.get("CASTREC_" + f.upper()) == "1"
+        special = dict(wslabs=int(env.get("CASTREC_WSLABS", "32")), stack_pair_max_b=int(env.get("CASTREC_STACK_PAIR_MAX_B", 160)),
+                       bf_two_kernels=env.get("CASTREC_BF_TWO_KERNELS") is not None,
+                       lazy_adam=bool(int(env.get("CASTREC_LAZY_ADAM", "0"))), attn_precision=env.get("CASTREC_ATTN_PRECISION") or None)
+        return cls(**{f: special[f] if f in special else on(f) for f in cls._fields})
+
+
+# what op_embed leaves for the first block behind it, which may apply the lookup's backward itself: make_desc(in_block) -> EmbedBwdDesc;
+# small: a context table (gradient written as slabs); indexed: the item table's seq lookup under the occurrence index (rows are left)
+ScatterRecipe = namedtuple("ScatterRecipe", "make_desc addend small table indexed scale")
+# a LayerNorm (input buffer, parameter prefix) whose backward op_head may take over
+LnRecipe = namedtuple("LnRecipe", "x pname")
+# a stack's final LayerNorm that its last block's backward may apply: yptr = out's pointer at column col, out of pitch ld
+LnfIntent = namedtuple("LnfIntent", "yptr pname out ld col")
+# what a block's FFN kernel runs behind it: "next" = LN1 + QKV of block pname with output out; "lnf" = LayerNorm pname into out[:, col:]
+Tail = namedtuple("Tail", "kind pname out ld col", defaults=(0, 0))
+# the gradient rows of the item table's seq lookup, left for the occurrence index's gather: scale * (rows + rows2), rows2 may be None
+TgRows = namedtuple("TgRows", "rows rows2 ld scale")
+# the activation buffers of one block, eng._bufs[<prefix><field>]; qkv is [3, M, D]: Q rows, K rows, V rows
+BlockBufs = namedtuple("BlockBufs", "q_in o f_in hid qkv kvalid qvalid")
+# ... and its parameters, in the order of cr_block_desc and (their gradients) cr_block_bwd_desc
+BLOCK_PARAMS = ("ln1.gamma", "ln1.beta", "wqkv", "bqkv", "ln2.gamma", "ln2.beta", "w1", "b1", "w2", "b2")
+
+
 # ---------------------------------------------------------------------------------------------------
 class Engine:
     def __init__(self, model, usernum, itemnum, hp, batch_size, training=True, seed=None, n_slabs=None,
@@ -220,128 +279,48 @@ class Engine:
         the loss launch left them: neg has no gradient under these losses and is not listed); "ce" refuses it (every item row has a
         gradient).  It sets eng.lazy_adam.  The older spelling lazy_adam=True / CASTREC_LAZY_ADAM=1 lists seq | pos | neg only and
         stays refused for the three softmax-route losses."""
+        self.sw = sw = Switches.from_env(os.environ)
         if model not in MODELS:
             raise ValueError("model must be one of %s" % MODELS)
         if not torch.cuda.is_available():
             raise RuntimeError("castrec_amd needs a ROCm GPU (gfx950); there is no CPU fallback")
         self.model, self.hp, self.B, self.T, self.D = model, hp, batch_size, hp.maxlen, hp.hidden_units
         self.H = hp.num_heads
-        if attn_precision is None:
-            attn_precision = os.environ.get("CASTREC_ATTN_PRECISION") or getattr(hp, "attn_precision", None) or DEFAULT_ATTN_PRECISION
-        if attn_precision not in ATTN_PRECISIONS:
-            raise ValueError("attn_precision must be one of %s" % sorted(ATTN_PRECISIONS))
-        self.attn_precision = attn_precision
-        if attn_precision == "f32" and hp.hidden_units > 64:
-            import warnings
-            warnings.warn("attn_precision='f32' at hidden_units %d leaves the tuned path: the exact-fp32 row phases above 64 columns are "
-                          "the unfused kernels (2.6x slower at the C4 shape, 11x at C5; profiles/r02d_other_shapes.log); the "
-                          "fp32-grade default is 'bf16x3'" % hp.hidden_units, RuntimeWarning, stacklevel=2)
-        # row-sparse Adam on the item table (DEVIATION from the reference's dense update, for tables like C5's 10 M rows;
-        # castrec.h cr_adam_desc.lazy_ids): off unless asked for
-        self.lazy_adam = bool(int(os.environ.get("CASTREC_LAZY_ADAM", "0"))) if lazy_adam is None else bool(lazy_adam)
-        if row_sparse_adam is None:
-            row_sparse_adam = getattr(hp, "row_sparse_adam", False)
-        row_sparse_adam = bool(row_sparse_adam)
-        if loss is None:
-            loss = getattr(hp, "loss", None) or "bce"
-        if loss not in ALL_LOSSES:
-            raise ValueError("loss must be one of %s, got %r" % (ALL_LOSSES, loss))
-        self.loss = loss if training else "bce"
-        if ce_negatives is None:
-            ce_negatives = getattr(hp, "ce_negatives", None) or 256
-        self.ce_negatives = int(ce_negatives)
-        if gbce_t is None:
-            gbce_t = getattr(hp, "gbce_t", None)
-            gbce_t = 0.75 if gbce_t is None else gbce_t
-        self.gbce_t = float(gbce_t)
-        if ce_proposal is None:
-            ce_proposal = getattr(hp, "ce_proposal", None) or "uniform"
-        if ce_proposal not in CE_PROPOSALS:
-            raise ValueError("ce_proposal must be one of %s, got %r" % (CE_PROPOSALS, ce_proposal))
-        self.ce_proposal = ce_proposal if training else "uniform"
-        if self.ce_proposal == "popularity" and self.loss != "sampled_ce":
-            raise ValueError("ce_proposal='popularity' needs loss='sampled_ce', got loss=%r (gbce's beta is derived for uniform "
-                             "sampling; bce and ce draw no shared negatives)" % self.loss)
-        if self.loss in SOFTMAX_LOSSES:
-            op = {"ce": "cr_softmax_ce", "sampled_ce": "cr_sampled_ce", "gbce": "cr_gbce"}[self.loss]
-            if self.loss == "ce" and (self.lazy_adam or row_sparse_adam):
-                raise ValueError("loss='%s' does not take row-sparse Adam (lazy_adam): every item row has a gradient" % self.loss)
-            if self.lazy_adam:
-                raise ValueError("loss='%s' does not take lazy_adam / CASTREC_LAZY_ADAM (its id list is seq | pos | neg: the step's samples "
-                                 "have a gradient too); ask for row_sparse_adam=True, which lists them" % self.loss)
-            if (batch_global is not None and batch_global != batch_size) or row_offset:
-                raise ValueError("loss='%s' does not take data parallelism (the item table's gradient is not in the exchanged bucket)"
-                                 % self.loss)
-            if not 8 <= hp.hidden_units <= 256:
-                raise ValueError("loss='%s' needs 8 <= hidden_units <= 256 (%s), got %d" % (self.loss, op, hp.hidden_units))
-        if self.loss in SAMPLED_LOSSES and not 1 <= self.ce_negatives <= L.CR_SCE_MAX_SAMPLES:
-            raise ValueError("loss='%s' needs 1 <= ce_negatives <= %d (%s), got %d"
-                             % (self.loss, L.CR_SCE_MAX_SAMPLES, op, self.ce_negatives))
-        if self.loss == "gbce":
-            if not 0.0 <= self.gbce_t <= 1.0:                      # (NaN fails too)
-                raise ValueError("loss='gbce' needs 0 <= gbce_t <= 1, got %r" % (gbce_t,))
-            # the sampling rate over the pool of negatives (the itemnum - 1 items that are not the target), gSASRec eq. for beta
-            alpha = min(1.0, self.ce_negatives / max(1, itemnum - 1))
-            self.gbce_beta = 1.0 - self.gbce_t * (1.0 - alpha)
-        # the public spelling of the row-sparse update: from here on everything (dist.py, models.py, set_step) reads lazy_adam alone
-        self.row_sparse_adam = row_sparse_adam
-        if row_sparse_adam:
-            self.lazy_adam = True
+        self.usernum, self.itemnum, self.training = usernum, itemnum, training
+        self._resolve_options(attn_precision, lazy_adam, loss, ce_negatives, gbce_t, ce_proposal, row_sparse_adam, fused,
+                              data_parallel=(batch_global is not None and batch_global != batch_size) or bool(row_offset))
         self.M = self.B * self.T
-        self.usernum, self.itemnum = usernum, itemnum
-        self.training = training
-        # fused row-phase kernels (cr_block_*) need the hidden size to fit one 64-column tile
-        self.single_pass_bwd = os.environ.get("CASTREC_TWO_PASS_ATTN_BWD") != "1"
-        self.fuse_tails = os.environ.get("CASTREC_NO_TAILS") != "1"
-        self.fuse_embed = os.environ.get("CASTREC_NO_EMBED_FUSION") != "1"
-        self.fuse_stack = os.environ.get("CASTREC_NO_STACK_KERNEL") != "1"
-        self.fuse_stack_bwd = os.environ.get("CASTREC_NO_STACK_BWD") != "1"
-        self.fuse_wide = os.environ.get("CASTREC_NO_WIDE") != "1"
         self._pending_embed = {}
-        self._scatter_recipe, self._scatter_claimed = {}, set()
-        self._ln_recipe, self._ln_claimed = {}, set()
-        self._lnf_intent = {}                         # y buffer of a stack's last block -> (LN output pointer, param prefix, out, ld, col)
+        self._scatter_recipe, self._scatter_claimed = {}, set()      # out buffer of an embedding lookup -> ScatterRecipe
+        self._ln_recipe, self._ln_claimed = {}, set()                # LayerNorm output pointer -> LnRecipe
+        self._lnf_intent = {}                                        # y buffer of a stack's last block -> LnfIntent
         # one launch per block backward (cr_stack_block_bwd): the gradient of a block input then exists as TWO partials;
         # _grad2 maps an activation buffer to the second addend of its gradient until a consumer takes it (see _second_grad)
-        self.fuse_block_bwd = os.environ.get("CASTREC_NO_BLOCK_BWD") != "1"
-        self._grad2 = {}
-        self._grad2_bufs = {}                         # data_ptr -> (activation buffer, second-addend buffer)
+        self._grad2, self._grad2_bufs = {}, {}        # (the second: data_ptr -> (activation buffer, second-addend buffer))
         self._block_bwd_ranges = []                   # slab-0 float ranges written by cr_stack_block_bwd (one slab per sequence)
-        self.fuse_head_ln = os.environ.get("CASTREC_NO_HEAD_LN") != "1" and self.loss == "bce"
-        self._check_ids = os.environ.get("CASTREC_NO_ID_CHECK") != "1"
-        self.fused = (4 <= hp.hidden_units <= 64) if fused is None else bool(fused)
-        if self.fused and not 4 <= hp.hidden_units <= 64:
-            raise ValueError("fused block kernels need 4 <= hidden_units <= 64")
         self.dev = torch.device(device)
         self.seed = hp.seed if seed is None else seed
-        self.layout = share.layout if share is not None else ParamLayout(model, usernum, itemnum, hp)
-        lay = self.layout
+        self.layout = lay = share.layout if share is not None else ParamLayout(model, usernum, itemnum, hp)
         if not n_slabs:
             n_slabs = auto_slabs(batch_size * hp.maxlen)
             # the register-layout backward kernels (cr_stack_bwd.hip) deal (sequence, round) items to the slab workgroups:
             # with a slab per item every workgroup runs one round (B = 128 sequences of 13 tiles: 256 workgroups, 256 CUs)
-            if (self.fused and self.attn_precision != "f32" and 8 <= self.D <= 64 and self.T <= 224
-                    and os.environ.get("CASTREC_NO_STACK_BWD") != "1"):
+            if self.fused and self.attn_precision != "f32" and 8 <= self.D <= 64 and self.T <= 224 and not sw.no_stack_bwd:
                 items = batch_size * (2 if self.T > 112 else 1)
                 if n_slabs < items <= 512:
                     n_slabs = items
                 # the prediction head as the tail of the trunk's last forward launch (cr_stack_fwd_head): its two workgroups per sequence
                 # write a slab each of the final LayerNorm's gradient
-                if (training and self.T > 16 and batch_size <= 160 and n_slabs < 2 * batch_size <= 512
-                        and os.environ.get("CASTREC_NO_HEAD_FUSION") != "1"):
+                if training and self.T > 16 and batch_size <= 160 and n_slabs < 2 * batch_size <= 512 and not sw.no_head_fusion:
                     n_slabs = 2 * batch_size
         self.n_slabs = n_slabs
         # cr_gemm_wgrad reduces over rows in n_wslabs workgroups per output tile: at the large hidden sizes of the unfused / wide
         # path (D x D weights, 4 blocks) a slab per 128 rows is 264 MB written and read again per step (config C4); 32 suffice
         # to fill the chip (tiles x slabs workgroups).  cr_adam_step learns per 256-parameter block how many slabs are in use.
-        self.n_wslabs = n_slabs if (self.fused or self.D <= 128) else min(n_slabs, int(os.environ.get("CASTREC_WSLABS", "32")))
-        self._wgrad_ranges = []
-        self.slab_counts = None
+        self.n_wslabs = n_slabs if (self.fused or self.D <= 128) else min(n_slabs, sw.wslabs)
+        self._wgrad_ranges, self.slab_counts = [], None
         f32 = dict(dtype=torch.float32, device=self.dev)
-        if share is not None:
-            self.P = share.P
-        else:
-            self.P = torch.from_numpy(lay.init_host(self.seed)).to(self.dev)
+        self.P = share.P if share is not None else torch.from_numpy(lay.init_host(self.seed)).to(self.dev)
         self.state = torch.zeros(L.CR_STATE_FLOATS, **f32)
         self.state[4:5].view(torch.int32)[0] = 1                      # number of the first step (see set_step)
         if training:
@@ -366,11 +345,9 @@ class Engine:
                 self._have_item_weights = False
         self.drop = O.Drop(hp.dropout_rate if training else 0.0, self.seed, self.state, row_offset)
         self.batch_global = self.B if batch_global is None else batch_global
-        self.want_attn = want_attn
-        self.attn_weights = None
+        self.want_attn, self.attn_weights = want_attn, None
         self._bufs, self._keep = {}, []
-        self.fwd, self.bwd = [], []
-        self._bwd_factories = []
+        self.fwd, self.bwd, self._bwd_factories = [], [], []
         self._grad_written = set()
         i32 = dict(dtype=torch.int32, device=self.dev)
         # the six id inputs of one batch live in ONE [6, M] buffer so a staged batch is a single D2D copy
@@ -381,7 +358,7 @@ class Engine:
         # head and the embedding backward.  Off (CASTREC_NO_INDEX=1, row-sparse Adam, hidden sizes the gather does not take): the
         # atomics of rounds 1-4.
         ng, ent = C.c_int(0), C.c_int(0)                        # the gather's geometry at this hidden size (0: a size it does not take)
-        self.use_index = bool(training and not self.lazy_adam and self.loss == "bce" and os.environ.get("CASTREC_NO_INDEX") != "1"
+        self.use_index = bool(training and not self.lazy_adam and self.loss == "bce" and not sw.no_index
                               and L.lib.cr_tgrad_geometry(self.D, C.byref(ng), C.byref(ent)))
         self.ids_words = 6 * self.M
         self.index_off = (self.ids_words + 3) // 4 * 4
@@ -401,13 +378,77 @@ class Engine:
         self.ids_all = self.batch_buf[:self.ids_words].view(6, self.M)
         self.ids = {k: self.ids_all[i] for i, k in enumerate(self.ID_KEYS)}
         self._host_slot = np.zeros(self.slot_words, np.int32)          # host mirror of the static batch buffer (set_batch builds the index in it)
-        self._tg_rows = None                                            # (rows, rows2 or None, ld, scale): the seq lookup's gradient rows
+        self._tg_rows = None                                            # TgRows: the seq lookup's gradient rows
         self.bitwise_reproducible = self.use_index                      # no float atomics left in a step's gradients (loss sums apart)
         self.static_pe = torch.from_numpy(positional_encoding(self.D, self.T)).to(self.dev)
         self._build()
         self._finalize()
         self.graph = None
         self._id_ring, self._ring_next = None, None
+
+    def _resolve_options(self, attn_precision, lazy_adam, loss, ce_negatives, gbce_t, ce_proposal, row_sparse_adam, fused, data_parallel):
+        """The constructor's options (argument, else environment, else hp, else default) as attributes, and every refusal."""
+        hp, training, itemnum = self.hp, self.training, self.itemnum
+        if attn_precision is None:
+            attn_precision = self.sw.attn_precision or getattr(hp, "attn_precision", None) or DEFAULT_ATTN_PRECISION
+        if attn_precision not in ATTN_PRECISIONS:
+            raise ValueError("attn_precision must be one of %s" % sorted(ATTN_PRECISIONS))
+        self.attn_precision = attn_precision
+        if attn_precision == "f32" and hp.hidden_units > 64:
+            import warnings
+            warnings.warn("attn_precision='f32' at hidden_units %d leaves the tuned path: the exact-fp32 row phases above 64 columns are "
+                          "the unfused kernels (2.6x slower at the C4 shape, 11x at C5; profiles/r02d_other_shapes.log); the "
+                          "fp32-grade default is 'bf16x3'" % hp.hidden_units, RuntimeWarning, stacklevel=3)
+        # row-sparse Adam on the item table (DEVIATION from the reference's dense update, for tables like C5's 10 M rows;
+        # castrec.h cr_adam_desc.lazy_ids): off unless asked for
+        self.lazy_adam = self.sw.lazy_adam if lazy_adam is None else bool(lazy_adam)
+        from_hp = lambda v, name, default: v if v is not None else (getattr(hp, name, None) or default)
+        row_sparse_adam = bool(from_hp(row_sparse_adam, "row_sparse_adam", False))
+        loss = from_hp(loss, "loss", "bce")
+        if loss not in ALL_LOSSES:
+            raise ValueError("loss must be one of %s, got %r" % (ALL_LOSSES, loss))
+        self.loss = loss if training else "bce"
+        self.ce_negatives = int(from_hp(ce_negatives, "ce_negatives", 256))
+        if gbce_t is None:
+            gbce_t = getattr(hp, "gbce_t", None)
+            gbce_t = 0.75 if gbce_t is None else gbce_t
+        self.gbce_t = float(gbce_t)
+        ce_proposal = from_hp(ce_proposal, "ce_proposal", "uniform")
+        if ce_proposal not in CE_PROPOSALS:
+            raise ValueError("ce_proposal must be one of %s, got %r" % (CE_PROPOSALS, ce_proposal))
+        self.ce_proposal = ce_proposal if training else "uniform"
+        if self.ce_proposal == "popularity" and self.loss != "sampled_ce":
+            raise ValueError("ce_proposal='popularity' needs loss='sampled_ce', got loss=%r (gbce's beta is derived for uniform "
+                             "sampling; bce and ce draw no shared negatives)" % self.loss)
+        if self.loss in SOFTMAX_LOSSES:
+            op = {"ce": "cr_softmax_ce", "sampled_ce": "cr_sampled_ce", "gbce": "cr_gbce"}[self.loss]
+            if self.loss == "ce" and (self.lazy_adam or row_sparse_adam):
+                raise ValueError("loss='%s' does not take row-sparse Adam (lazy_adam): every item row has a gradient" % self.loss)
+            if self.lazy_adam:
+                raise ValueError("loss='%s' does not take lazy_adam / CASTREC_LAZY_ADAM (its id list is seq | pos | neg: the step's samples "
+                                 "have a gradient too); ask for row_sparse_adam=True, which lists them" % self.loss)
+            if data_parallel:
+                raise ValueError("loss='%s' does not take data parallelism (the item table's gradient is not in the exchanged bucket)"
+                                 % self.loss)
+            if not 8 <= hp.hidden_units <= 256:
+                raise ValueError("loss='%s' needs 8 <= hidden_units <= 256 (%s), got %d" % (self.loss, op, hp.hidden_units))
+        if self.loss in SAMPLED_LOSSES and not 1 <= self.ce_negatives <= L.CR_SCE_MAX_SAMPLES:
+            raise ValueError("loss='%s' needs 1 <= ce_negatives <= %d (%s), got %d"
+                             % (self.loss, L.CR_SCE_MAX_SAMPLES, op, self.ce_negatives))
+        if self.loss == "gbce":
+            if not 0.0 <= self.gbce_t <= 1.0:                      # (NaN fails too)
+                raise ValueError("loss='gbce' needs 0 <= gbce_t <= 1, got %r" % (gbce_t,))
+            # the sampling rate over the pool of negatives (the itemnum - 1 items that are not the target), gSASRec eq. for beta
+            alpha = min(1.0, self.ce_negatives / max(1, itemnum - 1))
+            self.gbce_beta = 1.0 - self.gbce_t * (1.0 - alpha)
+        # the public spelling of the row-sparse update: from here on everything (dist.py, models.py, set_step) reads lazy_adam alone
+        self.row_sparse_adam = row_sparse_adam
+        if row_sparse_adam:
+            self.lazy_adam = True
+        # fused row-phase kernels (cr_block_*) need the hidden size to fit one 64-column tile
+        self.fused = (4 <= hp.hidden_units <= 64) if fused is None else bool(fused)
+        if self.fused and not 4 <= hp.hidden_units <= 64:
+            raise ValueError("fused block kernels need 4 <= hidden_units <= 64")
 
     # ---- small helpers -------------------------------------------------------------------------
     def buf(self, name, cols, rows=None):
@@ -457,6 +498,7 @@ class Engine:
         fn = getattr(L.lib, name)
         self._keep.append(args)
         lst.append((name, fn, args))
+        return lst
 
     def rng(self, site_name, enabled=True):
         return self.drop.rng(site_id(site_name), enabled and self.training)
@@ -464,21 +506,18 @@ class Engine:
     # ---- graph pieces --------------------------------------------------------------------------
     def op_embed(self, ids_key, table, out, ld_out, col_off, scale, pos=None, addend=None, drop_site=None,
                  mask=False, small=False, into_stack=False):
-        """modules.py:83-164 + the input composition of each graph. `addend` = (buffer, gradbuffer).
+        """modules.py:83-164 + the input composition of each graph. `addend`: a [M, D] buffer added to the looked-up rows.
         into_stack: `out` is the dense input of a transformer stack that follows immediately; on the fused path the
         gather then runs inside the first block's LN1 + QKV kernel (cr_block_ln_qkv_fwd_gather) instead of here."""
         V, D = self.layout.entries[table][1]
-        pos_ptr = None
-        if pos == "static":
-            pos_ptr = self.static_pe.data_ptr()
-        elif pos == "learned":
-            pos_ptr = self._pptr("pos_emb")
-        add_buf = addend[0] if addend else None
+        pos_ptr = self.static_pe.data_ptr() if pos == "static" else self._pptr("pos_emb") if pos == "learned" else None
+        has_add = addend is not None
+        d_add = self._grad_of(addend) if has_add else None
         d = L.EmbedDesc(self.ids[ids_key].data_ptr(), self._pptr(table), self.M, self.T, D, V, 1, float(scale), pos_ptr,
-                        add_buf.data_ptr() if addend else None, add_buf.shape[1] if addend else 0,
+                        addend.data_ptr() if has_add else None, addend.shape[1] if has_add else 0,
                         self.rng(drop_site) if drop_site else O.NO_DROP,
                         self.ids["seq"].data_ptr() if mask else None, out.data_ptr(), ld_out, col_off)
-        if into_stack and self.fused and self.fuse_embed and ld_out == D and col_off == 0:
+        if into_stack and self.fused and not self.sw.no_embed_fusion and ld_out == D and col_off == 0:
             self._pending_embed[out.data_ptr()] = d                  # emitted by the first block of op_stack
         else:
             self._call(self.fwd, "cr_embed_fwd", C.byref(d))
@@ -495,22 +534,22 @@ class Engine:
             f = L.EmbedDesc.from_buffer_copy(d)
             f.out = self._grad_of(out).data_ptr()
             dadd = None
-            if addend:
-                assert self._acc(id(addend[1])) == 0, "addend gradient must be first-written here"
-                dadd = addend[1].data_ptr()
+            if has_add:
+                assert self._acc(id(d_add)) == 0, "addend gradient must be first-written here"
+                dadd = d_add.data_ptr()
             g2 = self._second_grad(out) if (ld_out == D and col_off == 0) else None   # a gradient in two partials: the kernels add them
             if indexed:
                 if not in_block:
                     # cr_embed_bwd writes the rows as `d_addend` (the addend's gradient where the graph has one -- it IS the row --
                     # else a buffer of their own)
-                    if addend:
-                        rows = addend[1]
+                    if has_add:
+                        rows = d_add
                         assert rows.shape[1] % (4 if D % 4 == 0 else (2 if D % 2 == 0 else 1)) == 0
                     else:
                         rows = self.buf("item_rows", D)
                         f.ld_add = D
                         dadd = rows.data_ptr()
-                    self._tg_rows = (rows, None, rows.shape[1], float(scale))
+                    self._tg_rows = TgRows(rows, None, rows.shape[1], float(scale))
                 return L.EmbedBwdDesc(f, None, None, dadd, 0, 0, g2.data_ptr() if g2 is not None else None)
             return L.EmbedBwdDesc(f, self._gptr(table), self._gptr("pos_emb") if pos == "learned" else None, dadd,
                                   self.Gs.shape[1] if small else 0, self.n_slabs if small else 0, g2.data_ptr() if g2 is not None else None)
@@ -520,16 +559,14 @@ class Engine:
         # section is zero at that point); the block's factory (it runs before this one) claims it
         # (a small context table: only cr_stack_block_bwd takes it -- reduced in LDS, written as slabs -- and only with two slabs
         #  per sequence pair to write to)
-        if (out.data_ptr() in self._pending_embed and (addend is None or addend[0].shape[1] == D)
+        if (out.data_ptr() in self._pending_embed and (not has_add or addend.shape[1] == D)
                 and (not small or (V <= 256 and D <= 64 and pos is None and self.n_slabs >= 2 * min(self.B, self.n_slabs)))):
-            self._scatter_recipe[out.data_ptr()] = (make_bwd_desc, addend[0] if addend else None, small, table, indexed, float(scale))
+            self._scatter_recipe[out.data_ptr()] = ScatterRecipe(make_bwd_desc, addend, small, table, indexed, float(scale))
 
         def factory():
             if out.data_ptr() in self._scatter_claimed:
                 return []
-            lst = []
-            self._call(lst, "cr_embed_bwd", C.byref(make_bwd_desc()))
-            return lst
+            return self._call([], "cr_embed_bwd", C.byref(make_bwd_desc()))
         factory.pair_aware = ld_out == D and col_off == 0
         self._bwd_factories.append(factory)
 
@@ -555,10 +592,10 @@ class Engine:
                               O.NO_DROP, None, 0)
                 self._call(lst, "cr_eltwise", C.byref(e))
                 del self._grad2[ptr]
-                if self._tg_rows is not None and self._tg_rows[0] is g and self._tg_rows[1] is g2:
+                if self._tg_rows is not None and self._tg_rows.rows is g and self._tg_rows.rows2 is g2:
                     # the occurrence index's row pair was this pair: g now holds the SUM (the add above is in place), so the gather
                     # reads one partial
-                    self._tg_rows = (g, None) + self._tg_rows[2:]
+                    self._tg_rows = self._tg_rows._replace(rows=g, rows2=None)
         return lst
 
     def op_layernorm(self, x, y, y_ld, y_col, pname, flags=None, skip_fwd=False):
@@ -572,26 +609,35 @@ class Engine:
             self._call(self.fwd, "cr_layernorm_fwd", C.byref(d))
         if not self.training:
             return
-        self._ln_recipe[yptr] = (x, pname)            # op_head may take this backward over (cr_head_fwd_bwd_ln)
+        self._ln_recipe[yptr] = LnRecipe(x, pname)    # op_head may take this backward over (cr_head_fwd_bwd_ln)
 
         def factory():
             if yptr in self._ln_claimed or self._lnf_fused(x):
                 return []
-            dy = self._grad_of(y)
-            dx = self._grad_of(x)
-            bd = L.LnBwdDesc(x.data_ptr(), D, self._pptr(pname + ".gamma"), dy.data_ptr() + 4 * y_col, y_ld,
-                             dx.data_ptr(), D, self._acc(id(dx)), self._gptr(pname + ".gamma"), self._gptr(pname + ".beta"),
-                             self.Gs.shape[1], self.n_slabs, M, D, 1e-8)
-            lst = []
-            self._call(lst, "cr_layernorm_bwd", C.byref(bd))
-            return lst
+            dy, dx = self._grad_of(y), self._grad_of(x)
+            bd = self._ln_bwd_desc(x, pname, dy.data_ptr() + 4 * y_col, y_ld, dx.data_ptr(), self._acc(id(dx)))
+            return self._call([], "cr_layernorm_bwd", C.byref(bd))
         self._bwd_factories.append(factory)
 
+    def _ln_bwd_desc(self, x, pname, dy_ptr, lddy, dx_ptr, accumulate):
+        """Backward descriptor of the LayerNorm with parameters `pname` over the [M, D] rows of buffer x."""
+        D = self.D
+        return L.LnBwdDesc(x.data_ptr(), D, self._pptr(pname + ".gamma"), dy_ptr, lddy, dx_ptr, D, accumulate,
+                           self._gptr(pname + ".gamma"), self._gptr(pname + ".beta"), self.Gs.shape[1], self.n_slabs, self.M, D, 1e-8)
+
+    def _lnf_bwd_desc(self, y, dy):
+        """(descriptor, intent) of the final LayerNorm behind block output y, for the block backward kernel that applies it on its way in."""
+        it = self._lnf_intent[y.data_ptr()]
+        dlo = self._grad_of(it.out)
+        nd = self._ln_bwd_desc(y, it.pname, dlo.data_ptr() + 4 * it.col, it.ld, None, 0)
+        assert id(dy) not in self._grad_written, "the final LayerNorm must be the only consumer of the stack's output"
+        self._keep.append(nd)
+        return nd, it
+
     def _lnf_fused(self, x):
-        """True when the final LayerNorm whose input is buffer x has its backward applied inside the last block's FFN
-        backward (cr_stack_ffn_bwd_ln) -- decided the same way by the LayerNorm's factory and by the block's."""
+        """True when the final LayerNorm behind buffer x has its backward applied inside the last block's (both factories ask)."""
         it = self._lnf_intent.get(x.data_ptr())
-        return it is not None and it[0] not in self._ln_claimed
+        return it is not None and it.yptr not in self._ln_claimed
 
     def op_dropout_inplace(self, c, ncols, site):
         """tf.layers.dropout on the first `ncols` columns of concat buffer c (cast_2.py:90-92, cast_4.py:115-124)."""
@@ -604,9 +650,7 @@ class Engine:
         def factory():
             g = self._grad_of(c)
             bd = L.EltDesc(L.ELT_DROPOUT, g.data_ptr(), ld, None, 0, g.data_ptr(), ld, self.M, ncols, self.rng(site), None, 0)
-            lst = []
-            self._call(lst, "cr_eltwise", C.byref(bd))
-            return lst
+            return self._call([], "cr_eltwise", C.byref(bd))
         self._bwd_factories.append(factory)
 
     def op_mlp(self, c, out, k, mask_out=False):
@@ -614,14 +658,9 @@ class Engine:
         M, D = self.M, self.D
         K = k * D
         h = self.buf("mlp.h", K)
-        d1 = O.gemm_desc(c, K, None, K, h, K, M, K, K, relu=True)
-        d1.B, d1.bias = self._pptr("mlp.w1"), self._pptr("mlp.b1")
-        d2 = O.gemm_desc(h, K, None, D, out, out.shape[1], M, D, K, relu=True,
-                         mask_ids=self.ids["seq"] if mask_out else None)
-        d2.B, d2.bias = self._pptr("mlp.w2"), self._pptr("mlp.b2")
-        for d in (d1, d2):
-            arr = (L.GemmDesc * 1)(d)
-            self._call(self.fwd, "cr_gemm_rows", arr, 1)
+        self._gemm(self.fwd, c, self._pptr("mlp.w1"), K, h, K, K, bias=self._pptr("mlp.b1"), relu=True)
+        self._gemm(self.fwd, h, self._pptr("mlp.w2"), D, out, D, K, bias=self._pptr("mlp.b2"), relu=True,
+                   mask_ids=self.ids["seq"] if mask_out else None)
         if not self.training:
             return
 
@@ -632,87 +671,122 @@ class Engine:
             e = L.EltDesc(L.ELT_GRADPREP, dout.data_ptr(), out.shape[1], out.data_ptr(), out.shape[1], g2.data_ptr(), D, M, D,
                           O.NO_DROP, self.ids["seq"].data_ptr() if mask_out else None, 0)
             self._call(lst, "cr_eltwise", C.byref(e))
-            b = O.gemm_desc(g2, D, None, D, dh, K, M, K, D, trans_b=True, accumulate=bool(self._acc(id(dh))))
-            b.B = self._pptr("mlp.w2")
-            self._call(lst, "cr_gemm_rows", (L.GemmDesc * 1)(b), 1)
+            self._gemm(lst, g2, self._pptr("mlp.w2"), D, dh, K, D, trans_b=True, accumulate=bool(self._acc(id(dh))))
             e2 = L.EltDesc(L.ELT_GRADPREP, dh.data_ptr(), K, h.data_ptr(), K, dh.data_ptr(), K, M, K, O.NO_DROP, None, 0)
             self._call(lst, "cr_eltwise", C.byref(e2))
             w = (L.WgradDesc * 2)(L.WgradDesc(h.data_ptr(), K, g2.data_ptr(), D, self._gptr("mlp.w2"), D, self._gptr("mlp.b2"), M, D, K),
                                   L.WgradDesc(c.data_ptr(), K, dh.data_ptr(), K, self._gptr("mlp.w1"), K, self._gptr("mlp.b1"), M, K, K))
             self._call(lst, "cr_gemm_wgrad", w, 2, self.Gs.shape[1], self.n_slabs)
-            b1 = O.gemm_desc(dh, K, None, K, dc, K, M, K, K, trans_b=True, accumulate=bool(self._acc(id(dc))))
-            b1.B = self._pptr("mlp.w1")
-            self._call(lst, "cr_gemm_rows", (L.GemmDesc * 1)(b1), 1)
+            self._gemm(lst, dh, self._pptr("mlp.w1"), K, dc, K, K, trans_b=True, accumulate=bool(self._acc(id(dc))))
             return lst
         self._bwd_factories.append(factory)
 
+    def _gemm(self, lst, A, B, ldb, Cm, N, K, bias=None, **kw):
+        """One cr_gemm_rows launch: buffer Cm[M, N] = buffer A[M, K] x the weight at pointer B, pitch ldb; kw: O.gemm_desc's epilogue."""
+        d = O.gemm_desc(A, A.shape[1], None, ldb, Cm, Cm.shape[1], self.M, N, K, **kw)
+        d.B, d.bias = B, bias
+        self._call(lst, "cr_gemm_rows", (L.GemmDesc * 1)(d), 1)
+
     def op_block(self, x, y, pfx, attn_out=None, skip_qkv=False, tail=None, collect=None):
-        """One transformer block (sasrec.py:65-83): y = mask * FFN(LN2(MHA(LN1(x), x))).
-        Fused path only: `skip_qkv` = the LN1 + QKV phase was run as the tail of the previous block's FFN kernel;
-        `tail` = ("next", next block's prefix, its output buffer) or ("lnf", param prefix, out, ld, col)."""
-        M, D, H, B, T = self.M, self.D, self.H, self.B, self.T
-        d_head = D // H
-        q_in, o, f_in, hid = (self.buf(pfx + n, D) for n in ("q_in", "o", "f_in", "hid"))
-        qkv = self.buf(pfx + "qkv", D, rows=3 * M)            # [3, M, D]: Q rows, K rows, V rows
-        kvalid, qvalid = self.vec(pfx + "kvalid"), self.vec(pfx + "qvalid")
-        ids = self.ids["seq"]
-        wqkv, bqkv = self._pptr(pfx + "wqkv"), self._pptr(pfx + "bqkv")
+        """One transformer block (sasrec.py:65-83): y = mask * FFN(LN2(MHA(LN1(x), x))), by one of three routes, each of which emits
+        the forward and registers the backward: fused (hidden sizes 4..64), wide (128 / 192 / 256 on bf16 arithmetic), unfused.
+        Fused and wide: `skip_qkv` = the LN1 + QKV phase was run as the tail of the previous block's FFN kernel; `tail`: a Tail.
+        Fused: `collect` = a list: no forward is emitted; (block desc, attention desc) is appended for op_stack's cr_stack_fwd launch."""
+        b = self._block_bufs(pfx)
+        bd = self._block_desc(x, y, pfx, b)
+        ad = self._attn_desc(pfx, b, attn_out)
         if self.fused:
-            return self._op_block_fused(x, y, pfx, attn_out, q_in, o, f_in, hid, qkv, kvalid, qvalid, skip_qkv, tail, collect)
-        # hidden sizes 128 / 192 / 256 on bf16 arithmetic: the row phases as ONE launch each (cr_wide.hip)
-        prec = ATTN_PRECISIONS[self.attn_precision]
-        wbd = self._block_desc(x, y, pfx)
-        wide = bool(self.fuse_wide and prec != L.PREC_F32 and L.lib.cr_wide_supported(C.byref(wbd), prec))
-        MD4 = 4 * M * D
-        if wide and skip_qkv:
-            pass                                          # ran as the tail of the previous block's FFN kernel
-        elif wide:
-            self._call(self.fwd, "cr_wide_ln_qkv_fwd", C.byref(wbd), prec)
-        else:
-            assert not skip_qkv and tail is None, "tails need the fused or the wide (D = 128) row kernels"
-            # LN1 (+ data-dependent key / query masks, modules.py:222,248-249)
-            ln1 = L.LnDesc(x.data_ptr(), D, self._pptr(pfx + "ln1.gamma"), self._pptr(pfx + "ln1.beta"), q_in.data_ptr(), D, M, D,
-                           1e-8, kvalid.data_ptr(), qvalid.data_ptr())
-            self._call(self.fwd, "cr_layernorm_fwd", C.byref(ln1))
-            # Q = LN1(x) Wq + bq ; K = x Wk + bk ; V = x Wv + bv   (modules.py:203-205), one batched launch
-            gs = []
-            for part, src in enumerate((q_in, x, x)):
-                gd = O.gemm_desc(src, D, None, 3 * D, None, D, M, D, D)
-                gd.B, gd.bias, gd.C = wqkv + 4 * part * D, bqkv + 4 * part * D, qkv.data_ptr() + part * MD4
-                gs.append(gd)
-            self._call(self.fwd, "cr_gemm_rows", (L.GemmDesc * 3)(*gs), 3)
-        # attention core (modules.py:208-269), residual = queries
-        ad = O.attn_desc(qkv, None, None, D, kvalid, qvalid, q_in, D, o, D, B, T, H, d_head,
-                         rng=self.rng(pfx + "attn"), batch_global=self.batch_global,
-                         dead_ids=None if attn_out is not None else ids, attn_weights=attn_out)
-        ad.K, ad.V = qkv.data_ptr() + MD4, qkv.data_ptr() + 2 * MD4
-        ad.precision = ATTN_PRECISIONS[self.attn_precision]
-        if self.training and ad.precision != L.PREC_F32:
+            return self._block_fused(x, y, pfx, bd, ad, skip_qkv, tail, collect)
+        prec = ad.precision
+        if self.training and prec != L.PREC_F32:
             # the bf16-MFMA backward recomputes the probabilities from the forward's row statistics
-            ad.row_stats = self.vec(pfx + "row_stats", H * B * T * 4).data_ptr()
+            ad.row_stats = self.vec(pfx + "row_stats", self.H * self.B * self.T * 4).data_ptr()
+        if not self.sw.no_wide and prec != L.PREC_F32 and L.lib.cr_wide_supported(C.byref(bd), prec):
+            return self._block_wide(x, y, pfx, b, bd, ad, skip_qkv, tail)
+        assert not skip_qkv and tail is None, "tails need the fused or the wide (D = 128) row kernels"
+        return self._block_unfused(x, y, pfx, b, ad)
+
+    def _block_bufs(self, pfx):
+        D = self.D
+        return BlockBufs(*(self.buf(pfx + n, D) for n in ("q_in", "o", "f_in", "hid")), self.buf(pfx + "qkv", D, rows=3 * self.M),
+                         self.vec(pfx + "kvalid"), self.vec(pfx + "qvalid"))
+
+    def _block_desc(self, x, y, pfx, b):
+        """cr_block_desc of the block with parameter prefix `pfx` and buffers b."""
+        bufs = (x, b.q_in, b.qkv, b.kvalid, b.qvalid, b.o, b.f_in, b.hid, y, self.ids["seq"])
+        return L.BlockDesc(self.M, self.D, *(self._pptr(pfx + n) for n in BLOCK_PARAMS), *(t.data_ptr() for t in bufs),
+                           self.rng(pfx[:-1] + ".ffn1"), self.rng(pfx[:-1] + ".ffn2"))
+
+    def _attn_desc(self, pfx, b, attn_out):
+        """Attention core of a block (modules.py:208-269) over its [3, M, D] qkv buffer, residual = queries."""
+        D, H, MD4 = self.D, self.H, 4 * self.M * self.D
+        ad = O.attn_desc(b.qkv, None, None, D, b.kvalid, b.qvalid, b.q_in, D, b.o, D, self.B, self.T, H, D // H,
+                         rng=self.rng(pfx + "attn"), batch_global=self.batch_global,
+                         dead_ids=None if attn_out is not None else self.ids["seq"], attn_weights=attn_out)
+        ad.K, ad.V = b.qkv.data_ptr() + MD4, b.qkv.data_ptr() + 2 * MD4
+        ad.precision = ATTN_PRECISIONS[self.attn_precision]
+        return ad
+
+    def _tail_desc(self, y, tail):
+        """cr_block_tail_desc of a Tail behind the block with output y."""
+        if tail.kind == "next":
+            nbd = self._block_desc(y, tail.out, tail.pname, self._block_bufs(tail.pname))
+            self._keep.append(nbd)
+            return L.BlockTailDesc(1, C.pointer(nbd), None, None, None, 0, 0)
+        return L.BlockTailDesc(2, None, self._pptr(tail.pname + ".gamma"), self._pptr(tail.pname + ".beta"), tail.out.data_ptr(),
+                               tail.ld, tail.col)
+
+    def _attn_bwd_desc(self, ad, pfx, do):
+        """cr_attn_bwd_desc of a block: d_o -> dQ | dK | dV, the [3, M, D] rows of its dqkv buffer."""
+        M, D, MD4 = self.M, self.D, 4 * self.M * self.D
+        dqkv = self.buf(pfx + "dqkv", D, rows=3 * M)
+        stats = self.vec(pfx + "stats", self.H * self.B * self.T * 4)
+        return L.AttnBwdDesc(L.AttnDesc.from_buffer_copy(ad), do.data_ptr(), D, dqkv.data_ptr(), dqkv.data_ptr() + MD4,
+                             dqkv.data_ptr() + 2 * MD4, D, stats.data_ptr())
+
+    def _block_bwd_desc(self, bd, pfx, dy, abd, dx):
+        """cr_block_bwd_desc of a block beside its attention backward abd: dy -> d_o, dQ | dK | dV -> dx (first writer of dx or not)."""
+        return L.BlockBwdDesc(L.BlockDesc.from_buffer_copy(bd), dy.data_ptr(), abd.dout, abd.dQ, dx.data_ptr(), self._acc(id(dx)),
+                              *(self._gptr(pfx + n) for n in BLOCK_PARAMS), self.Gs.shape[1], self.n_slabs)
+
+    def _ffn_wgrad(self, lst, pfx, b, g2, g1):
+        """dW2, db2, dW1, db1 of a block by cr_gemm_wgrad."""
+        M, D, G = self.M, self.D, self._gptr
+        w = (L.WgradDesc * 2)(L.WgradDesc(b.hid.data_ptr(), D, g2.data_ptr(), D, G(pfx + "w2"), D, G(pfx + "b2"), M, D, D),
+                              L.WgradDesc(b.f_in.data_ptr(), D, g1.data_ptr(), D, G(pfx + "w1"), D, G(pfx + "b1"), M, D, D))
+        self._call(lst, "cr_gemm_wgrad", w, 2, self.Gs.shape[1], self.n_slabs)
+
+    def _qkv_wgrad(self, lst, pfx, b, x, abd):
+        """dWq, dbq ; dWk, dbk ; dWv, dbv of a block by cr_gemm_wgrad (column blocks of the fused [D, 3D] weight gradient)."""
+        M, D = self.M, self.D
+        gw, gb = self._gptr(pfx + "wqkv"), self._gptr(pfx + "bqkv")
+        w = (L.WgradDesc * 3)(L.WgradDesc(b.q_in.data_ptr(), D, abd.dQ, D, gw, 3 * D, gb, M, D, D),
+                              L.WgradDesc(x.data_ptr(), D, abd.dK, D, gw + 4 * D, 3 * D, gb + 4 * D, M, D, D),
+                              L.WgradDesc(x.data_ptr(), D, abd.dV, D, gw + 8 * D, 3 * D, gb + 8 * D, M, D, D))
+        self._call(lst, "cr_gemm_wgrad", w, 3, self.Gs.shape[1], self.n_slabs)
+
+    def _block_unfused(self, x, y, pfx, b, ad):
+        """The block as the chain cr_layernorm_* / cr_gemm_rows / cr_attn_* / cr_eltwise (any hidden size, exact fp32 above 64)."""
+        M, D, P, ids = self.M, self.D, self._pptr, self.ids["seq"]
+        wqkv = P(pfx + "wqkv")
+        # LN1 (+ data-dependent key / query masks, modules.py:222,248-249)
+        ln1 = L.LnDesc(x.data_ptr(), D, P(pfx + "ln1.gamma"), P(pfx + "ln1.beta"), b.q_in.data_ptr(), D, M, D,
+                       1e-8, b.kvalid.data_ptr(), b.qvalid.data_ptr())
+        self._call(self.fwd, "cr_layernorm_fwd", C.byref(ln1))
+        # Q = LN1(x) Wq + bq ; K = x Wk + bk ; V = x Wv + bv   (modules.py:203-205), one batched launch
+        gs = []
+        for part, src in enumerate((b.q_in, x, x)):
+            gd = O.gemm_desc(src, D, None, 3 * D, None, D, M, D, D)
+            gd.B, gd.bias, gd.C = wqkv + 4 * part * D, P(pfx + "bqkv") + 4 * part * D, b.qkv.data_ptr() + part * 4 * M * D
+            gs.append(gd)
+        self._call(self.fwd, "cr_gemm_rows", (L.GemmDesc * 3)(*gs), 3)
         self._call(self.fwd, "cr_attn_fwd", C.byref(ad))
         # LN2 + FFN (modules.py:280-318), residual = LN2 output, then * mask (sasrec.py:83)
-        if wide and tail is not None and tail[0] == "next":
-            nbd = self._block_desc(y, tail[2], tail[1])
-            td = L.BlockTailDesc(1, C.pointer(nbd), None, None, None, 0, 0)
-            self._keep.append(nbd)
-            self._call(self.fwd, "cr_wide_ln_ffn_fwd_tail", C.byref(wbd), C.byref(td), prec)
-        elif wide and tail is not None:
-            _, pname, lo, lo_ld, lo_col = tail
-            td = L.BlockTailDesc(2, None, self._pptr(pname + ".gamma"), self._pptr(pname + ".beta"), lo.data_ptr(), lo_ld, lo_col)
-            self._call(self.fwd, "cr_wide_ln_ffn_fwd_tail", C.byref(wbd), C.byref(td), prec)
-        elif wide:
-            self._call(self.fwd, "cr_wide_ln_ffn_fwd", C.byref(wbd), prec)
-        else:
-            ln2 = L.LnDesc(o.data_ptr(), D, self._pptr(pfx + "ln2.gamma"), self._pptr(pfx + "ln2.beta"), f_in.data_ptr(), D, M, D,
-                           1e-8, None, None)
-            self._call(self.fwd, "cr_layernorm_fwd", C.byref(ln2))
-            f1 = O.gemm_desc(f_in, D, None, D, hid, D, M, D, D, relu=True, rng=self.rng(pfx[:-1] + ".ffn1"))
-            f1.B, f1.bias = self._pptr(pfx + "w1"), self._pptr(pfx + "b1")
-            self._call(self.fwd, "cr_gemm_rows", (L.GemmDesc * 1)(f1), 1)
-            f2 = O.gemm_desc(hid, D, None, D, y, D, M, D, D, rng=self.rng(pfx[:-1] + ".ffn2"), residual=f_in, ldr=D, mask_ids=ids)
-            f2.B, f2.bias = self._pptr(pfx + "w2"), self._pptr(pfx + "b2")
-            self._call(self.fwd, "cr_gemm_rows", (L.GemmDesc * 1)(f2), 1)
+        ln2 = L.LnDesc(b.o.data_ptr(), D, P(pfx + "ln2.gamma"), P(pfx + "ln2.beta"), b.f_in.data_ptr(), D, M, D, 1e-8, None, None)
+        self._call(self.fwd, "cr_layernorm_fwd", C.byref(ln2))
+        self._gemm(self.fwd, b.f_in, P(pfx + "w1"), D, b.hid, D, D, bias=P(pfx + "b1"), relu=True, rng=self.rng(pfx[:-1] + ".ffn1"))
+        self._gemm(self.fwd, b.hid, P(pfx + "w2"), D, y, D, D, bias=P(pfx + "b2"), rng=self.rng(pfx[:-1] + ".ffn2"), residual=b.f_in, ldr=D,
+                   mask_ids=ids)
         if not self.training:
             return
 
@@ -720,119 +794,86 @@ class Engine:
             lst = []
             dy, dx = self._grad_of(y), self._grad_of(x)
             g2, g1, df, do, dq_in = (self.buf(pfx + n, D) for n in ("g2", "g1", "df", "do", "dq_in"))
-            dqkv = self.buf(pfx + "dqkv", D, rows=3 * M)          # [3, M, D]
-            stats = self.vec(pfx + "stats", H * B * T * 4)
-            S = self.Gs.shape[1]
-            if wide:
-                G = self._gptr
-                bbd = L.BlockBwdDesc(L.BlockDesc.from_buffer_copy(wbd), dy.data_ptr(), do.data_ptr(), dqkv.data_ptr(), dx.data_ptr(),
-                                     self._acc(id(dx)), G(pfx + "ln1.gamma"), G(pfx + "ln1.beta"), G(pfx + "wqkv"), G(pfx + "bqkv"),
-                                     G(pfx + "ln2.gamma"), G(pfx + "ln2.beta"), G(pfx + "w1"), G(pfx + "b1"), G(pfx + "w2"), G(pfx + "b2"),
-                                     S, self.n_slabs)
-                # dy -> g2, g1, d_o, slabs of dgamma2 dbeta2 (and dW2 db2 dW1 db1 unless left to cr_gemm_wgrad)
-                # (the kernels form the weight gradients themselves at D = 128: a [D, D] slab per 128 rows is what an activation
-                #  row block costs; at 192 / 256 the slab of a 64-row block is 4 x its rows, and cr_gemm_wgrad reduces more rows
-                #  per slab)
-                own_w = D == 128 and os.environ.get("CASTREC_WIDE_NO_WGRAD") != "1"
-                if not own_w:
-                    bbd.g_w1 = bbd.g_b1 = bbd.g_w2 = bbd.g_b2 = bbd.g_wqkv = bbd.g_bqkv = None
-                # The one-launch attention backward (both passes side by side, tiles dealt to eight waves) needs the per-head row
-                # term delta up front; the FFN backward emits it (it reads o and q_in once more for that).  C4 shape: 1.136 ->
-                # 1.094 ms per step since the fused kernel deals its tiles by iteration count (before that: equal).
-                dh = D // H
-                fuse_attn = (T <= 256 and 8 <= dh <= 64 and dh % 16 == 0 and os.environ.get("CASTREC_WIDE_NO_DELTA") != "1"
-                             and os.environ.get("CASTREC_BF_TWO_KERNELS") is None)
-                if fuse_attn:
-                    delta = self.vec("attn_delta_heads", H * M)
-                    bbd.attn_delta = delta.data_ptr()
-                self._call(lst, "cr_wide_ln_ffn_bwd", C.byref(bbd), g2.data_ptr(), g1.data_ptr(), H if fuse_attn else 0, prec)
-                if not own_w:
-                    w = (L.WgradDesc * 2)(L.WgradDesc(hid.data_ptr(), D, g2.data_ptr(), D, G(pfx + "w2"), D, G(pfx + "b2"), M, D, D),
-                                          L.WgradDesc(f_in.data_ptr(), D, g1.data_ptr(), D, G(pfx + "w1"), D, G(pfx + "b1"), M, D, D))
-                    self._call(lst, "cr_gemm_wgrad", w, 2, S, self.n_slabs)
-                dq, dk, dv = dqkv.data_ptr(), dqkv.data_ptr() + MD4, dqkv.data_ptr() + 2 * MD4
-                abd = L.AttnBwdDesc(L.AttnDesc.from_buffer_copy(ad), do.data_ptr(), D, dq, dk, dv, D, stats.data_ptr())
-                if fuse_attn:
-                    abd.delta = delta.data_ptr()
-                self._call(lst, "cr_attn_bwd", C.byref(abd))
-                if not own_w:
-                    gw, gb = G(pfx + "wqkv"), G(pfx + "bqkv")
-                    w2 = (L.WgradDesc * 3)(L.WgradDesc(q_in.data_ptr(), D, dq, D, gw, 3 * D, gb, M, D, D),
-                                           L.WgradDesc(x.data_ptr(), D, dk, D, gw + 4 * D, 3 * D, gb + 4 * D, M, D, D),
-                                           L.WgradDesc(x.data_ptr(), D, dv, D, gw + 8 * D, 3 * D, gb + 8 * D, M, D, D))
-                    self._call(lst, "cr_gemm_wgrad", w2, 3, S, self.n_slabs)
-                # (dQ | dK | dV, d_o) -> dx (+ dgamma1 / dbeta1 slabs)
-                self._call(lst, "cr_wide_ln_qkv_bwd", C.byref(bbd), prec)
-                return lst
+            abd = self._attn_bwd_desc(ad, pfx, do)
             # (a) gradient wrt FFN2 pre-dropout output: dy * mask * keep/(1-rate)
             e = L.EltDesc(L.ELT_GRADPREP, dy.data_ptr(), D, None, 0, g2.data_ptr(), D, M, D, self.rng(pfx[:-1] + ".ffn2"), ids.data_ptr(), 0)
             self._call(lst, "cr_eltwise", C.byref(e))
             # (b) dhid = g2 W2^T ; (c) gate by the stored post-dropout ReLU output
-            b = O.gemm_desc(g2, D, None, D, g1, D, M, D, D, trans_b=True)
-            b.B = self._pptr(pfx + "w2")
-            self._call(lst, "cr_gemm_rows", (L.GemmDesc * 1)(b), 1)
-            e1 = L.EltDesc(L.ELT_GRADPREP, g1.data_ptr(), D, hid.data_ptr(), D, g1.data_ptr(), D, M, D, self.rng(pfx[:-1] + ".ffn1"), None, 0)
+            self._gemm(lst, g2, P(pfx + "w2"), D, g1, D, D, trans_b=True)
+            e1 = L.EltDesc(L.ELT_GRADPREP, g1.data_ptr(), D, b.hid.data_ptr(), D, g1.data_ptr(), D, M, D, self.rng(pfx[:-1] + ".ffn1"), None, 0)
             self._call(lst, "cr_eltwise", C.byref(e1))
             # (d) dW2, db2, dW1, db1
-            w = (L.WgradDesc * 2)(L.WgradDesc(hid.data_ptr(), D, g2.data_ptr(), D, self._gptr(pfx + "w2"), D, self._gptr(pfx + "b2"), M, D, D),
-                                  L.WgradDesc(f_in.data_ptr(), D, g1.data_ptr(), D, self._gptr(pfx + "w1"), D, self._gptr(pfx + "b1"), M, D, D))
-            self._call(lst, "cr_gemm_wgrad", w, 2, S, self.n_slabs)
+            self._ffn_wgrad(lst, pfx, b, g2, g1)
             # (e) df_in = (g1 W1^T + dy) * mask     (residual branch of modules.py:313)
-            b1 = O.gemm_desc(g1, D, None, D, df, D, M, D, D, trans_b=True, residual=dy, ldr=D, mask_ids=ids)
-            b1.B = self._pptr(pfx + "w1")
-            self._call(lst, "cr_gemm_rows", (L.GemmDesc * 1)(b1), 1)
+            self._gemm(lst, g1, P(pfx + "w1"), D, df, D, D, trans_b=True, residual=dy, ldr=D, mask_ids=ids)
             # (f) LN2 backward -> do
-            l2 = L.LnBwdDesc(o.data_ptr(), D, self._pptr(pfx + "ln2.gamma"), df.data_ptr(), D, do.data_ptr(), D, 0,
-                             self._gptr(pfx + "ln2.gamma"), self._gptr(pfx + "ln2.beta"), S, self.n_slabs, M, D, 1e-8)
-            self._call(lst, "cr_layernorm_bwd", C.byref(l2))
-            # (g) attention backward -> dQ | dK | dV
-            dq, dk, dv = dqkv.data_ptr(), dqkv.data_ptr() + MD4, dqkv.data_ptr() + 2 * MD4
-            abd = L.AttnBwdDesc(L.AttnDesc.from_buffer_copy(ad), do.data_ptr(), D, dq, dk, dv, D, stats.data_ptr())
+            self._call(lst, "cr_layernorm_bwd", C.byref(self._ln_bwd_desc(b.o, pfx + "ln2", df.data_ptr(), D, do.data_ptr(), 0)))
+            # (g) attention backward -> dQ | dK | dV ; (h) their weight gradients
             self._call(lst, "cr_attn_bwd", C.byref(abd))
-            # (h) dWq, dbq ; dWk, dbk ; dWv, dbv  (column blocks of the fused [D,3D] weight gradient)
-            gw = self._gptr(pfx + "wqkv"); gb = self._gptr(pfx + "bqkv")
-            w2 = (L.WgradDesc * 3)(L.WgradDesc(q_in.data_ptr(), D, dq, D, gw, 3 * D, gb, M, D, D),
-                                   L.WgradDesc(x.data_ptr(), D, dk, D, gw + 4 * D, 3 * D, gb + 4 * D, M, D, D),
-                                   L.WgradDesc(x.data_ptr(), D, dv, D, gw + 8 * D, 3 * D, gb + 8 * D, M, D, D))
-            self._call(lst, "cr_gemm_wgrad", w2, 3, S, self.n_slabs)
+            self._qkv_wgrad(lst, pfx, b, x, abd)
             # (i) dq_in = dQ Wq^T + do (residual, modules.py:269) ; dx (+)= dK Wk^T, then dx += dV Wv^T
             bq = O.gemm_desc(None, D, None, 3 * D, dq_in, D, M, D, D, trans_b=True, residual=do, ldr=D)
-            bq.A, bq.B = dq, wqkv
+            bq.A, bq.B = abd.dQ, wqkv
             bk = O.gemm_desc(None, D, None, 3 * D, dx, D, M, D, D, trans_b=True, accumulate=bool(self._acc(id(dx))))
-            bk.A, bk.B = dk, wqkv + 4 * D
+            bk.A, bk.B = abd.dK, wqkv + 4 * D
             self._call(lst, "cr_gemm_rows", (L.GemmDesc * 2)(bq, bk), 2)
             bv = O.gemm_desc(None, D, None, 3 * D, dx, D, M, D, D, trans_b=True, accumulate=True)
-            bv.A, bv.B = dv, wqkv + 8 * D
+            bv.A, bv.B = abd.dV, wqkv + 8 * D
             self._call(lst, "cr_gemm_rows", (L.GemmDesc * 1)(bv), 1)
             # (j) LN1 backward accumulates into dx
-            l1 = L.LnBwdDesc(x.data_ptr(), D, self._pptr(pfx + "ln1.gamma"), dq_in.data_ptr(), D, dx.data_ptr(), D, 1,
-                             self._gptr(pfx + "ln1.gamma"), self._gptr(pfx + "ln1.beta"), S, self.n_slabs, M, D, 1e-8)
-            self._call(lst, "cr_layernorm_bwd", C.byref(l1))
+            self._call(lst, "cr_layernorm_bwd", C.byref(self._ln_bwd_desc(x, pfx + "ln1", dq_in.data_ptr(), D, dx.data_ptr(), 1)))
             return lst
         self._bwd_factories.append(factory)
 
-    def _block_desc(self, x, y, pfx):
-        """cr_block_desc of the block with parameter prefix `pfx` (buffers are created on first use, by name)."""
-        M, D = self.M, self.D
-        q_in, o, f_in, hid = (self.buf(pfx + n, D) for n in ("q_in", "o", "f_in", "hid"))
-        qkv = self.buf(pfx + "qkv", D, rows=3 * M)
-        kvalid, qvalid = self.vec(pfx + "kvalid"), self.vec(pfx + "qvalid")
-        P = self._pptr
-        return L.BlockDesc(M, D, P(pfx + "ln1.gamma"), P(pfx + "ln1.beta"), P(pfx + "wqkv"), P(pfx + "bqkv"),
-                           P(pfx + "ln2.gamma"), P(pfx + "ln2.beta"), P(pfx + "w1"), P(pfx + "b1"), P(pfx + "w2"), P(pfx + "b2"),
-                           x.data_ptr(), q_in.data_ptr(), qkv.data_ptr(), kvalid.data_ptr(), qvalid.data_ptr(), o.data_ptr(),
-                           f_in.data_ptr(), hid.data_ptr(), y.data_ptr(), self.ids["seq"].data_ptr(),
-                           self.rng(pfx[:-1] + ".ffn1"), self.rng(pfx[:-1] + ".ffn2"))
+    def _block_wide(self, x, y, pfx, b, bd, ad, skip_qkv, tail):
+        """Hidden sizes 128 / 192 / 256 on bf16 arithmetic: the row phases as ONE launch each (cr_wide.hip)."""
+        D, H, T, prec = self.D, self.H, self.T, ad.precision
+        if not skip_qkv:                                  # (else: ran as the tail of the previous block's FFN kernel)
+            self._call(self.fwd, "cr_wide_ln_qkv_fwd", C.byref(bd), prec)
+        self._call(self.fwd, "cr_attn_fwd", C.byref(ad))
+        if tail is None:
+            self._call(self.fwd, "cr_wide_ln_ffn_fwd", C.byref(bd), prec)
+        else:
+            self._call(self.fwd, "cr_wide_ln_ffn_fwd_tail", C.byref(bd), C.byref(self._tail_desc(y, tail)), prec)
+        if not self.training:
+            return
 
-    def _op_block_fused(self, x, y, pfx, attn_out, q_in, o, f_in, hid, qkv, kvalid, qvalid, skip_qkv=False, tail=None,
-                        collect=None):
-        """Same block through the fused row-phase kernels (cr_block_*): 3 launches forward, 3 backward; with tails
-        (the next block's LN1 + QKV, or the stack's final LayerNorm, inside the FFN kernel) 2 forward.
-        collect: a list -- the forward is not emitted here; (block desc, attention desc) is appended for op_stack's
-        one cr_stack_fwd launch.  The backward is the same in both cases."""
-        M, D, H, B, T = self.M, self.D, self.H, self.B, self.T
-        ids = self.ids["seq"]
-        bd = self._block_desc(x, y, pfx)
+        def factory():
+            lst = []
+            dy, dx = self._grad_of(y), self._grad_of(x)
+            g2, g1, df, do, dq_in = (self.buf(pfx + n, D) for n in ("g2", "g1", "df", "do", "dq_in"))     # (df, dq_in: not read here; kept in eng._bufs)
+            abd = self._attn_bwd_desc(ad, pfx, do)
+            bbd = self._block_bwd_desc(bd, pfx, dy, abd, dx)
+            # dy -> g2, g1, d_o, slabs of dgamma2 dbeta2 (and dW2 db2 dW1 db1 unless left to cr_gemm_wgrad)
+            # (the kernels form the weight gradients themselves at D = 128: a [D, D] slab per 128 rows is what an activation
+            #  row block costs; at 192 / 256 the slab of a 64-row block is 4 x its rows, and cr_gemm_wgrad reduces more rows
+            #  per slab)
+            own_w = D == 128 and not self.sw.wide_no_wgrad
+            if not own_w:
+                bbd.g_w1 = bbd.g_b1 = bbd.g_w2 = bbd.g_b2 = bbd.g_wqkv = bbd.g_bqkv = None
+            # The one-launch attention backward (both passes side by side, tiles dealt to eight waves) needs the per-head row
+            # term delta up front; the FFN backward emits it (it reads o and q_in once more for that).  C4 shape: 1.136 ->
+            # 1.094 ms per step since the fused kernel deals its tiles by iteration count (before that: equal).
+            dh = D // H
+            fuse_attn = T <= 256 and 8 <= dh <= 64 and dh % 16 == 0 and not self.sw.wide_no_delta and not self.sw.bf_two_kernels
+            if fuse_attn:
+                bbd.attn_delta = abd.delta = self.vec("attn_delta_heads", H * self.M).data_ptr()
+            self._call(lst, "cr_wide_ln_ffn_bwd", C.byref(bbd), g2.data_ptr(), g1.data_ptr(), H if fuse_attn else 0, prec)
+            if not own_w:
+                self._ffn_wgrad(lst, pfx, b, g2, g1)
+            self._call(lst, "cr_attn_bwd", C.byref(abd))
+            if not own_w:
+                self._qkv_wgrad(lst, pfx, b, x, abd)
+            # (dQ | dK | dV, d_o) -> dx (+ dgamma1 / dbeta1 slabs)
+            self._call(lst, "cr_wide_ln_qkv_bwd", C.byref(bbd), prec)
+            return lst
+        self._bwd_factories.append(factory)
+
+    def _block_fused(self, x, y, pfx, bd, ad, skip_qkv, tail, collect):
+        """Hidden sizes 4..64 through the fused row-phase kernels (cr_block_*): 3 launches forward; with tails (the next block's
+        LN1 + QKV, or the stack's final LayerNorm, inside the FFN kernel) 2; collected for cr_stack_fwd none of its own.  The
+        backward is the same in every case: one launch (cr_stack_block_bwd) where the kernel takes the block, else three."""
+        D, H, B, T = self.D, self.H, self.B, self.T
         if not skip_qkv and collect is None:
             e = self._pending_embed.pop(x.data_ptr(), None)
             if e is not None:
@@ -840,161 +881,122 @@ class Engine:
                 self._call(self.fwd, "cr_block_ln_qkv_fwd_gather", C.byref(bd), C.byref(e))
             else:
                 self._call(self.fwd, "cr_block_ln_qkv_fwd", C.byref(bd))
-        MD4 = 4 * M * D
-        ad = O.attn_desc(qkv, None, None, D, kvalid, qvalid, q_in, D, o, D, B, T, H, D // H,
-                         rng=self.rng(pfx + "attn"), batch_global=self.batch_global,
-                         dead_ids=None if attn_out is not None else ids, attn_weights=attn_out)
-        ad.K, ad.V = qkv.data_ptr() + MD4, qkv.data_ptr() + 2 * MD4
         # single-pass attention backward (H = 1): the forward saves its row statistics, the FFN backward emits
         # delta, the attention backward returns dQ as two partials that the QKV backward adds
-        ad.precision = ATTN_PRECISIONS[self.attn_precision]
-        bf = ad.precision != L.PREC_F32 and 8 <= D // H <= 64 and T <= 1024     # shapes the bf16-MFMA kernels take
-        one_pass = self.training and H == 1 and self.single_pass_bwd and not bf
+        prec = ad.precision
+        bf = prec != L.PREC_F32 and 8 <= D // H <= 64 and T <= 1024     # shapes the bf16-MFMA kernels take
+        one_pass = self.training and H == 1 and not self.sw.two_pass_attn_bwd and not bf
         if one_pass or (self.training and bf):
-            row_stats = self.vec(pfx + "row_stats", H * B * T * 4)
-            ad.row_stats = row_stats.data_ptr()
+            ad.row_stats = self.vec(pfx + "row_stats", H * B * T * 4).data_ptr()
         if collect is not None:
             collect.append((bd, ad))
         else:
             self._call(self.fwd, "cr_attn_fwd", C.byref(ad))
-        if collect is not None:
-            pass
-        elif tail is None:
-            self._call(self.fwd, "cr_block_ln_ffn_fwd", C.byref(bd))
-        elif tail[0] == "next":
-            nbd = self._block_desc(y, tail[2], tail[1])
-            td = L.BlockTailDesc(1, C.pointer(nbd), None, None, None, 0, 0)
-            self._keep.append(nbd)
-            self._call(self.fwd, "cr_block_ln_ffn_fwd_tail", C.byref(bd), C.byref(td))
-        else:
-            _, pname, out, out_ld, out_col = tail
-            td = L.BlockTailDesc(2, None, self._pptr(pname + ".gamma"), self._pptr(pname + ".beta"), out.data_ptr(), out_ld, out_col)
-            self._call(self.fwd, "cr_block_ln_ffn_fwd_tail", C.byref(bd), C.byref(td))
+            if tail is None:
+                self._call(self.fwd, "cr_block_ln_ffn_fwd", C.byref(bd))
+            else:
+                self._call(self.fwd, "cr_block_ln_ffn_fwd_tail", C.byref(bd), C.byref(self._tail_desc(y, tail)))
         if not self.training:
             return
 
         def factory():
-            lst = []
             dy, dx = self._grad_of(y), self._grad_of(x)
-            do = self.buf(pfx + "do", D)
-            dqkv = self.buf(pfx + "dqkv", D, rows=3 * M)          # [3, M, D]
-            stats = self.vec(pfx + "stats", H * B * T * 4)
-            G = self._gptr
-            bbd = L.BlockBwdDesc(L.BlockDesc.from_buffer_copy(bd), dy.data_ptr(), do.data_ptr(), dqkv.data_ptr(), dx.data_ptr(),
-                                 self._acc(id(dx)), G(pfx + "ln1.gamma"), G(pfx + "ln1.beta"), G(pfx + "wqkv"), G(pfx + "bqkv"),
-                                 G(pfx + "ln2.gamma"), G(pfx + "ln2.beta"), G(pfx + "w1"), G(pfx + "b1"), G(pfx + "w2"), G(pfx + "b2"),
-                                 self.Gs.shape[1], self.n_slabs)
-            abd = L.AttnBwdDesc(L.AttnDesc.from_buffer_copy(ad), do.data_ptr(), D, dqkv.data_ptr(), dqkv.data_ptr() + MD4,
-                                dqkv.data_ptr() + 2 * MD4, D, stats.data_ptr())
+            abd = self._attn_bwd_desc(ad, pfx, self.buf(pfx + "do", D))
+            bbd = self._block_bwd_desc(bd, pfx, dy, abd, dx)
+            if one_pass or (bf and H == 1):
+                # one head: the FFN backward emits delta (its row sum IS the head's; shared between the blocks: consumed within the
+                # same block); with it the bf16-MFMA backward runs both passes side by side in one launch and dQ comes back whole
+                bbd.attn_delta = abd.delta = self.vec("attn_delta", self.M).data_ptr()
             if one_pass:
-                delta = self.vec("attn_delta", M)                   # shared: consumed within the same block
-                dq_part = self.buf("attn_dq_part", D)
-                bbd.attn_delta, bbd.dq_part = delta.data_ptr(), dq_part.data_ptr()
-                abd.delta, abd.dQ_part = delta.data_ptr(), dq_part.data_ptr()
-            elif bf and H == 1:
-                # bf16-MFMA backward: the FFN backward emits delta (one head: its row sum IS the head's), which lets
-                # both passes run side by side in one launch; dQ comes back whole
-                delta = self.vec("attn_delta", M)
-                bbd.attn_delta = delta.data_ptr()
-                abd.delta = delta.data_ptr()
+                bbd.dq_part = abd.dQ_part = self.buf("attn_dq_part", D).data_ptr()
             # bf16 arithmetic: the row phases run on the register-layout kernels (cr_stack_bwd.hip) where they take the shape
-            prec = ATTN_PRECISIONS[self.attn_precision]
-            rows_bf = bool(self.fuse_stack_bwd and bf and not one_pass and L.lib.cr_stack_bwd_supported(C.byref(bbd), B, T, prec))
+            rows_bf = bool(not self.sw.no_stack_bwd and bf and not one_pass and L.lib.cr_stack_bwd_supported(C.byref(bbd), B, T, prec))
             # ... and where the whole block fits one launch (cr_stack_bwd1.hip: one head, D < 64): ffn_bwd -> attn_bwd -> qkv_bwd per
             # sequence on a pair of workgroups; the input gradient leaves as two partials (dx, dx2)
-            if (rows_bf and self.fuse_block_bwd and (H == 1 or (H == 2 and D == 64))
+            if (rows_bf and not self.sw.no_block_bwd and (H == 1 or (H == 2 and D == 64))
                     and L.lib.cr_stack_block_bwd_supported(C.byref(bbd), C.byref(abd.f), B, T, prec)):
-                dx2 = self.buf(pfx + "dx2", D)
-                dy2 = self._second_grad(y)
-                ext = L.BlockBwd1Ext(dy2.data_ptr() if dy2 is not None else None, dx2.data_ptr(), None, None)
-                nd = None
-                if self._lnf_fused(y):
-                    _, pname, lo, lo_ld, lo_col = self._lnf_intent[y.data_ptr()]
-                    dlo = self._grad_of(lo)
-                    nd = L.LnBwdDesc(y.data_ptr(), D, self._pptr(pname + ".gamma"), dlo.data_ptr() + 4 * lo_col, lo_ld, None, D, 0,
-                                     self._gptr(pname + ".gamma"), self._gptr(pname + ".beta"), self.Gs.shape[1], self.n_slabs, M, D, 1e-8)
-                    assert id(dy) not in self._grad_written and dy2 is None, "the final LayerNorm must be the only consumer of the stack's output"
-                    dlo2 = self._second_grad(lo)
-                    if dlo2 is not None:
-                        assert dlo2.shape == dlo.shape
-                        ext.lnf_dy2 = dlo2.data_ptr() + 4 * lo_col
-                    self._keep.append(nd)
-                    self._block_slab_range(pname + ".gamma", pname + ".beta")
-                sc = None
-                rec = self._scatter_recipe.get(x.data_ptr())
-                if rec is not None and not bbd.dx_accumulate:
-                    self._scatter_claimed.add(x.data_ptr())
-                    sc = rec[0](True) if rec[4] else rec[0]()
-                    if rec[2]:                                             # small table: two slabs per sequence pair
-                        self._block_slab_range(rec[3], rec[3], 2 * min(self.B, self.n_slabs))
-                    if sc.d_addend:
-                        dadd2 = self.buf(pfx + "dadd2", D)
-                        ext.d_addend2 = dadd2.data_ptr()
-                        self._grad2[rec[1].data_ptr()] = dadd2            # the addend's gradient is d_addend + d_addend2
-                        self._grad2_bufs[rec[1].data_ptr()] = (rec[1], dadd2)
-                    if rec[4]:
-                        # occurrence index: the kernel leaves the two masked partials of the input gradient where they wait (the
-                        # addend's gradient pair, else dx / dx2) and scatters nothing; cr_adam_step gathers scale * (rows + rows2)
-                        if sc.d_addend:
-                            self._tg_rows = (self._grad_of(rec[1]), dadd2, D, rec[5])
-                        else:
-                            self._tg_rows = (dx, dx2, D, rec[5])
-                    self._keep.append(sc)
-                else:
-                    self._grad2[x.data_ptr()] = dx2                       # the block input's gradient is dx + dx2
-                    self._grad2_bufs[x.data_ptr()] = (x, dx2)
-                self._keep.append(ext)
-                self._block_slab_range(pfx + "ln1.gamma", pfx + "b2")
-                self._call(lst, "cr_stack_block_bwd", C.byref(bbd), C.byref(abd.f), C.byref(ext), C.byref(nd) if nd is not None else None,
-                           C.byref(sc) if sc is not None else None, B, T, prec)
-                return lst
-            lst += self._fold_pairs()                              # the kernels below read one gradient pointer
-            two_heads = (rows_bf and H == 2 and D == 64 and T <= 256 and os.environ.get("CASTREC_BF_TWO_KERNELS") is None
-                         and os.environ.get("CASTREC_NO_HEAD_DELTA") != "1")
-            if two_heads:
-                # config C3's shape: the register-layout FFN backward emits delta per head ([2, M]), so the attention backward is
-                # ONE launch here too
-                delta = self.vec("attn_delta_heads", H * M)
-                bbd.attn_delta = delta.data_ptr()
-                abd.delta = delta.data_ptr()
-                nd = None
-                if self._lnf_fused(y):
-                    _, pname, lo, lo_ld, lo_col = self._lnf_intent[y.data_ptr()]
-                    dlo = self._grad_of(lo)
-                    nd = L.LnBwdDesc(y.data_ptr(), D, self._pptr(pname + ".gamma"), dlo.data_ptr() + 4 * lo_col, lo_ld, None, D, 0,
-                                     self._gptr(pname + ".gamma"), self._gptr(pname + ".beta"), self.Gs.shape[1], self.n_slabs, M, D, 1e-8)
-                    assert id(dy) not in self._grad_written, "the final LayerNorm must be the only consumer of the stack's output"
-                    self._keep.append(nd)
-                self._call(lst, "cr_stack_ffn_bwd_heads", C.byref(bbd), C.byref(nd) if nd is not None else None, B, T, H, prec)
-            elif rows_bf and self._lnf_fused(y):
-                _, pname, lo, lo_ld, lo_col = self._lnf_intent[y.data_ptr()]
-                dlo = self._grad_of(lo)
-                nd = L.LnBwdDesc(y.data_ptr(), D, self._pptr(pname + ".gamma"), dlo.data_ptr() + 4 * lo_col, lo_ld, None, D, 0,
-                                 self._gptr(pname + ".gamma"), self._gptr(pname + ".beta"), self.Gs.shape[1], self.n_slabs, M, D, 1e-8)
-                assert id(dy) not in self._grad_written, "the final LayerNorm must be the only consumer of the stack's output"
-                self._call(lst, "cr_stack_ffn_bwd_ln", C.byref(bbd), C.byref(nd), B, T, prec)
-            elif rows_bf:
-                self._call(lst, "cr_stack_ffn_bwd", C.byref(bbd), B, T, prec)
-            else:
-                assert not self._lnf_fused(y), "final LayerNorm backward was left to a kernel that does not take it"
-                self._call(lst, "cr_block_ln_ffn_bwd", C.byref(bbd))
-            self._call(lst, "cr_attn_bwd", C.byref(abd))
-            recipe = self._scatter_recipe.get(x.data_ptr())
-            if recipe is not None and recipe[4]:
-                recipe = None                                              # (indexed: these kernels only know the atomic scatter; cr_embed_bwd leaves the rows)
-            if recipe is not None and not recipe[2] and not bbd.dx_accumulate:
-                self._scatter_claimed.add(x.data_ptr())
-                if rows_bf:
-                    self._call(lst, "cr_stack_qkv_bwd_scatter", C.byref(bbd), C.byref(recipe[0]()), B, T, prec)
-                else:
-                    self._call(lst, "cr_block_ln_qkv_bwd_scatter", C.byref(bbd), C.byref(recipe[0]()))
-            elif rows_bf:
-                self._call(lst, "cr_stack_qkv_bwd", C.byref(bbd), B, T, prec)
-            else:
-                self._call(lst, "cr_block_ln_qkv_bwd", C.byref(bbd))
-            return lst
+                return self._block_bwd_one_launch(x, y, pfx, bbd, abd, dy, dx)
+            return self._block_bwd_three_launches(x, y, bbd, abd, dy, rows_bf)
         factory.pair_aware = True                      # (takes dy2 where it can; any other pending pair is not its input)
         self._bwd_factories.append(factory)
+
+    def _block_bwd_one_launch(self, x, y, pfx, bbd, abd, dy, dx):
+        """cr_stack_block_bwd: the whole block, with the final LayerNorm behind it and the embedding scatter in front of it where
+        the graph has them there.  Gradients arrive and leave as two partials each (BlockBwd1Ext)."""
+        D, B, T = self.D, self.B, self.T
+        dx2 = self.buf(pfx + "dx2", D)
+        dy2 = self._second_grad(y)
+        ext = L.BlockBwd1Ext(dy2.data_ptr() if dy2 is not None else None, dx2.data_ptr(), None, None)
+        nd = None
+        if self._lnf_fused(y):
+            nd, it = self._lnf_bwd_desc(y, dy)
+            assert dy2 is None, "the final LayerNorm must be the only consumer of the stack's output"
+            dlo2 = self._second_grad(it.out)
+            if dlo2 is not None:
+                assert dlo2.shape == it.out.shape
+                ext.lnf_dy2 = dlo2.data_ptr() + 4 * it.col
+            self._block_slab_range(it.pname + ".gamma", it.pname + ".beta")
+        sc = None
+        rec = self._scatter_recipe.get(x.data_ptr())
+        if rec is not None and not bbd.dx_accumulate:
+            self._scatter_claimed.add(x.data_ptr())
+            sc = rec.make_desc(in_block=rec.indexed)
+            if rec.small:                                          # small table: two slabs per sequence pair
+                self._block_slab_range(rec.table, rec.table, 2 * min(self.B, self.n_slabs))
+            dadd2 = None
+            if sc.d_addend:
+                dadd2 = self.buf(pfx + "dadd2", D)
+                ext.d_addend2 = dadd2.data_ptr()
+                self._grad2[rec.addend.data_ptr()] = dadd2         # the addend's gradient is d_addend + d_addend2
+                self._grad2_bufs[rec.addend.data_ptr()] = (rec.addend, dadd2)
+            if rec.indexed:
+                # occurrence index: the kernel leaves the two masked partials of the input gradient where they wait (the
+                # addend's gradient pair, else dx / dx2) and scatters nothing; cr_adam_step gathers scale * (rows + rows2)
+                self._tg_rows = TgRows(self._grad_of(rec.addend), dadd2, D, rec.scale) if sc.d_addend else TgRows(dx, dx2, D, rec.scale)
+            self._keep.append(sc)
+        else:
+            self._grad2[x.data_ptr()] = dx2                       # the block input's gradient is dx + dx2
+            self._grad2_bufs[x.data_ptr()] = (x, dx2)
+        self._keep.append(ext)
+        self._block_slab_range(pfx + "ln1.gamma", pfx + "b2")
+        return self._call([], "cr_stack_block_bwd", C.byref(bbd), C.byref(abd.f), C.byref(ext), C.byref(nd) if nd is not None else None,
+                          C.byref(sc) if sc is not None else None, B, T, abd.f.precision)
+
+    def _block_bwd_three_launches(self, x, y, bbd, abd, dy, rows_bf):
+        """FFN backward, attention backward, QKV backward as a launch each: the register-layout kernels (cr_stack_*_bwd*) where
+        rows_bf says they take the shape, else the tile kernels (cr_block_ln_*_bwd*)."""
+        D, H, B, T, prec = self.D, self.H, self.B, self.T, abd.f.precision
+        lst = self._fold_pairs()                               # the kernels below read one gradient pointer
+        two_heads = rows_bf and H == 2 and D == 64 and T <= 256 and not self.sw.bf_two_kernels and not self.sw.no_head_delta
+        if two_heads:
+            # config C3's shape: the register-layout FFN backward emits delta per head ([2, M]), so the attention backward is
+            # ONE launch here too
+            bbd.attn_delta = abd.delta = self.vec("attn_delta_heads", H * self.M).data_ptr()
+        nd = self._lnf_bwd_desc(y, dy)[0] if rows_bf and self._lnf_fused(y) else None
+        if two_heads:
+            self._call(lst, "cr_stack_ffn_bwd_heads", C.byref(bbd), C.byref(nd) if nd is not None else None, B, T, H, prec)
+        elif nd is not None:
+            self._call(lst, "cr_stack_ffn_bwd_ln", C.byref(bbd), C.byref(nd), B, T, prec)
+        elif rows_bf:
+            self._call(lst, "cr_stack_ffn_bwd", C.byref(bbd), B, T, prec)
+        else:
+            assert not self._lnf_fused(y), "final LayerNorm backward was left to a kernel that does not take it"
+            self._call(lst, "cr_block_ln_ffn_bwd", C.byref(bbd))
+        self._call(lst, "cr_attn_bwd", C.byref(abd))
+        # the embedding scatter of the block's input: the atomic scatter of a large table only (indexed: cr_embed_bwd leaves the
+        # rows; a small table: only cr_stack_block_bwd takes it)
+        rec = self._scatter_recipe.get(x.data_ptr())
+        if rec is not None and not rec.indexed and not rec.small and not bbd.dx_accumulate:
+            self._scatter_claimed.add(x.data_ptr())
+            if rows_bf:
+                self._call(lst, "cr_stack_qkv_bwd_scatter", C.byref(bbd), C.byref(rec.make_desc()), B, T, prec)
+            else:
+                self._call(lst, "cr_block_ln_qkv_bwd_scatter", C.byref(bbd), C.byref(rec.make_desc()))
+        elif rows_bf:
+            self._call(lst, "cr_stack_qkv_bwd", C.byref(bbd), B, T, prec)
+        else:
+            self._call(lst, "cr_block_ln_qkv_bwd", C.byref(bbd))
+        return lst
 
     def _block_slab_range(self, first, last, count=None):
         """Parameters first..last (contiguous in the layout) get their gradient from cr_stack_block_bwd: one slab per sequence
@@ -1007,7 +1009,7 @@ class Engine:
         """Shapes cr_stack_fwd takes (castrec.h): one head (or two of 32 columns), D 8..64, bf16 arithmetic, K / V images +
         weights within the LDS."""
         heads_ok = self.H == 1 or (self.H == 2 and self.D == 64)          # two heads: head dim 32 = one k-step of the score product
-        if not (self.fused and self.fuse_stack and nblocks >= 1 and not want_attn and heads_ok and 8 <= self.D <= 64):
+        if not (self.fused and not self.sw.no_stack_kernel and nblocks >= 1 and not want_attn and heads_ok and 8 <= self.D <= 64):
             return False
         if self.attn_precision == "f32" or self.T > 256:
             return False
@@ -1022,9 +1024,9 @@ class Engine:
         Fused path: block i+1's LN1 + QKV phase and the final LayerNorm run as tails of the FFN kernels; where the
         whole-stack kernel fits (cr_stack_fwd) the forward of up to four blocks + the final LayerNorm is ONE launch."""
         # (the wide row kernels take the same tails at D = 128: cr_wide_ln_ffn_fwd_tail)
-        wide_tails = (not self.fused and self.fuse_wide and self.attn_precision != "f32" and self.D == 128
-                      and os.environ.get("CASTREC_WIDE_NO_TAILS") != "1")
-        tails = (self.fused or wide_tails) and self.fuse_tails and nblocks > 0
+        sw = self.sw
+        wide_tails = not self.fused and not sw.no_wide and self.attn_precision != "f32" and self.D == 128 and not sw.wide_no_tails
+        tails = (self.fused or wide_tails) and not sw.no_tails and nblocks > 0
         stack = self._stack_kernel_fits(nblocks, want_attn)
         emb = None
         if stack and x.data_ptr() in self._pending_embed:                # the stack kernel composes its input itself
@@ -1038,18 +1040,17 @@ class Engine:
             nxt = ys[i]
             aw = None
             if want_attn and i == nblocks - 1:
-                self.attn_weights = torch.zeros(self.H * self.B, self.T, self.T, dtype=torch.float32, device=self.dev)
-                aw = self.attn_weights
+                aw = self.attn_weights = torch.zeros(self.H * self.B, self.T, self.T, dtype=torch.float32, device=self.dev)
             tail = None
             if tails:
-                tail = ("next", "%s.%d." % (prefix, i + 1), ys[i + 1]) if i + 1 < nblocks else ("lnf", prefix + ".lnf", out, out_ld, out_col)
+                tail = Tail("next", "%s.%d." % (prefix, i + 1), ys[i + 1]) if i + 1 < nblocks else Tail("lnf", prefix + ".lnf", out, out_ld, out_col)
             self.op_block(cur, nxt, "%s.%d." % (prefix, i), attn_out=aw, skip_qkv=tails and i > 0, tail=tail, collect=collect)
             cur = nxt
         if stack:
             for i0 in range(0, nblocks, 4):
                 part = collect[i0:i0 + 4]
-                bds = (L.BlockDesc * len(part))(*[c[0] for c in part])
-                ads = (L.AttnDesc * len(part))(*[c[1] for c in part])
+                bds = (L.BlockDesc * len(part))(*[bd for bd, _ in part])
+                ads = (L.AttnDesc * len(part))(*[ad for _, ad in part])
                 fin = i0 + 4 >= nblocks
                 sd = L.StackDesc(len(part), C.cast(bds, C.POINTER(L.BlockDesc)), C.cast(ads, C.POINTER(L.AttnDesc)),
                                  self._pptr(prefix + ".lnf.gamma") if fin else None, self._pptr(prefix + ".lnf.beta") if fin else None,
@@ -1060,10 +1061,9 @@ class Engine:
                     raise RuntimeError("cr_stack_fwd does not take the stack %s it was sized for" % prefix)
                 self._keep.append((bds, ads))
                 self._call(self.fwd, "cr_stack_fwd", C.byref(sd))
-        if (stack and self.training and self.fuse_stack_bwd and self.D <= 64 and self.T <= 224
-                and os.environ.get("CASTREC_NO_LNF_FUSION") != "1"):
+        if stack and self.training and not sw.no_stack_bwd and self.D <= 64 and self.T <= 224 and not sw.no_lnf_fusion:
             # the register-layout FFN backward of the last block can apply this LayerNorm's backward on its way in
-            self._lnf_intent[cur.data_ptr()] = (out.data_ptr() + 4 * out_col, prefix + ".lnf", out, out_ld, out_col)
+            self._lnf_intent[cur.data_ptr()] = LnfIntent(out.data_ptr() + 4 * out_col, prefix + ".lnf", out, out_ld, out_col)
         self.op_layernorm(cur, out, out_ld, out_col, prefix + ".lnf", skip_fwd=tails or stack)
 
     def op_head(self, seq_emb):
@@ -1080,61 +1080,60 @@ class Engine:
             ds = self._grad_of(seq_emb)
             self._grad_written.add(id(ds))
             prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
-            row, pos, neg, V = seq_emb.data_ptr(), self.ids["pos"].data_ptr(), self.ids["neg"].data_ptr(), self.itemnum + 1
-            tail = (ds.data_ptr(), ds.shape[1], self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
+            state = self.state.data_ptr()
+            head = (seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(), self.ids["neg"].data_ptr(),
+                    M, D, self.itemnum + 1)
+            tail = (state, ds.data_ptr(), ds.shape[1], self._gptr("item_emb"), None, self._ce_ws.data_ptr(), self._ce_ws.numel())
             if self.loss == "ce":
-                op = "cr_softmax_ce"
-                d = L.SoftmaxCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, prec, self.state.data_ptr(), *tail)
-            elif self.loss == "gbce":
-                op = "cr_gbce"
-                d = L.GbceDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, self.ce_negatives, prec, self.gbce_beta,
-                               None, self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
-                               *tail)
-            else:
-                op = "cr_sampled_ce"
-                pop = self.ce_proposal == "popularity"
-                d = L.SampledCeDesc(row, seq_emb.shape[1], self._pptr("item_emb"), pos, neg, M, D, V, self.ce_negatives, prec, None,
-                                    self.seed & 0xFFFFFFFF, self.state.data_ptr() + 16, self.samples.data_ptr(), self.state.data_ptr(),
-                                    *tail, self.item_cdf.data_ptr() if pop else None, self.item_logq.data_ptr() if pop else None)
-            self._call(self.fwd, op, C.byref(d))
-            return
-        rec = self._ln_recipe.get(seq_emb.data_ptr()) if self.fuse_head_ln else None
+                return self._call(self.fwd, "cr_softmax_ce", C.byref(L.SoftmaxCeDesc(*head, prec, *tail)))
+            draw = (None, self.seed & 0xFFFFFFFF, state + 16, self.samples.data_ptr())       # no ids handed in: drawn from (seed, step)
+            if self.loss == "gbce":
+                return self._call(self.fwd, "cr_gbce", C.byref(L.GbceDesc(*head, self.ce_negatives, prec, self.gbce_beta, *draw, *tail)))
+            pop = self.ce_proposal == "popularity"
+            d = L.SampledCeDesc(*head, self.ce_negatives, prec, *draw, *tail,
+                                self.item_cdf.data_ptr() if pop else None, self.item_logq.data_ptr() if pop else None)
+            return self._call(self.fwd, "cr_sampled_ce", C.byref(d))
+        rec = self._ln_recipe.get(seq_emb.data_ptr()) if not self.sw.no_head_ln else None
+        dx = ds = self._grad_of(rec.x if rec is not None else seq_emb)      # (allocated in front of head.coef, as ever: buffer order)
+        d = L.HeadDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
+                       self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, self.state.data_ptr(), None, 0,
+                       None if self.use_index else self._gptr("item_emb"), None, None, self._head_coef())
         if rec is not None:
             # seq_emb is the output of a LayerNorm (the stack's final one): its backward runs inside the head kernel,
             # on the gradient rows while they are in registers; d(seq_emb) is never stored
-            x, pname = rec
-            dx = self._grad_of(x)
             assert self._acc(id(dx)) == 0
             self._ln_claimed.add(seq_emb.data_ptr())
-            d = L.HeadDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
-                           self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, self.state.data_ptr(), None, 0,
-                           None if self.use_index else self._gptr("item_emb"), None, None, self._head_coef())
-            n = L.LnBwdDesc(x.data_ptr(), D, self._pptr(pname + ".gamma"), None, 0, dx.data_ptr(), D, 0,
-                            self._gptr(pname + ".gamma"), self._gptr(pname + ".beta"), self.Gs.shape[1], self.n_slabs, M, D, 1e-8)
+            n = self._ln_bwd_desc(rec.x, rec.pname, None, 0, dx.data_ptr(), 0)
             # the head as the tail of the stack's last forward launch (cr_stack_fwd_head): no launch of its own.  Needs the occurrence
             # index (nothing is scattered from there) and the launch form with two workgroups per sequence.
-            last = self.fwd[-1] if self.fwd else None
-            if (self.use_index and last is not None and last[0] == "cr_stack_fwd" and os.environ.get("CASTREC_NO_HEAD_FUSION") != "1"
-                    and last[2][0]._obj.out == seq_emb.data_ptr()
-                    and L.lib.cr_stack_fwd_head_supported(last[2][0], C.byref(d), C.byref(n))):
+            sd = self._stack_desc(self.fwd[-1]) if self.fwd else None
+            if (self.use_index and sd is not None and not self.sw.no_head_fusion and sd.out == seq_emb.data_ptr()
+                    and L.lib.cr_stack_fwd_head_supported(C.byref(sd), C.byref(d), C.byref(n))):
                 self._keep += [d, n]
-                self.fwd[-1] = ("cr_stack_fwd_head", L.lib.cr_stack_fwd_head, (last[2][0], C.byref(d), C.byref(n)))
-                self._block_slab_range(pname + ".gamma", pname + ".beta", 2 * self.B)      # workgroup (sequence, half) writes slab half * B + sequence
+                self.fwd[-1] = ("cr_stack_fwd_head", L.lib.cr_stack_fwd_head, (C.byref(sd), C.byref(d), C.byref(n)))
+                self._block_slab_range(rec.pname + ".gamma", rec.pname + ".beta", 2 * self.B)      # workgroup (sequence, half) writes slab half * B + sequence
                 return
             self._call(self.fwd, "cr_head_fwd_bwd_ln", C.byref(d), C.byref(n))
             return
-        ds = self._grad_of(seq_emb)
         self._grad_written.add(id(ds))
-        d = L.HeadDesc(seq_emb.data_ptr(), seq_emb.shape[1], self._pptr("item_emb"), self.ids["pos"].data_ptr(),
-                       self.ids["neg"].data_ptr(), M, D, self.itemnum + 1, self.state.data_ptr(), ds.data_ptr(), ds.shape[1],
-                       None if self.use_index else self._gptr("item_emb"), None, None, self._head_coef())
+        d.d_seq_emb, d.ldd = ds.data_ptr(), ds.shape[1]
         self._call(self.fwd, "cr_head_fwd_bwd", C.byref(d))
+
+    @staticmethod
+    def _stack_desc(entry):
+        """The cr_stack_desc of a cr_stack_fwd / cr_stack_fwd_head launch entry; None for any other entry."""
+        return entry[2][0]._obj if entry[0] in ("cr_stack_fwd", "cr_stack_fwd_head") else None
+
+    @staticmethod
+    def _scatter_desc(entry):
+        """The embedding scatter (EmbedBwdDesc) a backward launch entry applies, or None."""
+        name, _, args = entry
+        i = 0 if name == "cr_embed_bwd" else 4 if name == "cr_stack_block_bwd" else 1 if name.endswith("_scatter") else None
+        return args[i]._obj if i is not None and args[i] is not None else None
 
     def _head_coef(self):
         """[2, M] d loss_sum / d logit of the pos / neg item per row: what the occurrence index's gather multiplies seq_emb rows with."""
-        if not self.use_index:
-            return None
-        return self.vec("head.coef", 2 * self.M).data_ptr()
+        return self.vec("head.coef", 2 * self.M).data_ptr() if self.use_index else None
 
     # ---- the eleven graphs -----------------------------------------------------------------------
     def _build(self):
@@ -1159,7 +1158,7 @@ class Engine:
             tseq = self.buf("tseq", D)
             ctx_stack("time_emb", "time", "ctx_time", tseq, D, 0, want=wa_ctx)
             x = self.buf("x0", D)
-            self.op_embed("seq", "item_emb", x, D, 0, sq, pos="static", addend=(tseq, self._grad_of(tseq)),
+            self.op_embed("seq", "item_emb", x, D, 0, sq, pos="static", addend=tseq,
                           drop_site="emb", mask=True, into_stack=True)                      # cast_1.py:86-91
             s = self.buf("seq_emb", D)
             self.op_stack(x, "trunk", L_, s, D, 0)
@@ -1175,7 +1174,7 @@ class Engine:
                 ctx_stack("time_emb", "time", "ctx_time", tseq, D, 0, want=wa_ctx)
                 self.op_embed("hours", "hours_emb", c, k * D, D, sq, small=True)            # cast_3.py:32-41
                 self.op_embed("days", "days_emb", c, k * D, 2 * D, sq, small=True)          # cast_3.py:43-52
-                self.op_embed("seq", "item_emb", c, k * D, 0, sq, pos="static", addend=(tseq, self._grad_of(tseq)),
+                self.op_embed("seq", "item_emb", c, k * D, 0, sq, pos="static", addend=tseq,
                               mask=True)                                                    # cast_3.py:112-114
                 self.op_dropout_inplace(c, 3 * D, "concat1")                                # cast_3.py:117-120
             elif m == "cast_4":
@@ -1211,7 +1210,7 @@ class Engine:
             if m == "cast_5":
                 tseq = self.buf("tseq", D)
                 ctx_stack("time_emb", "time", "ctx_time", tseq, D, 0, want=wa_ctx)
-                self.op_embed("seq", "item_emb", x, D, 0, sq, pos="static", addend=(tseq, self._grad_of(tseq)),
+                self.op_embed("seq", "item_emb", x, D, 0, sq, pos="static", addend=tseq,
                               into_stack=True)                                              # cast_5.py:113-114
                 self.op_stack(x, "trunk", L_, c, k * D, 0)                                  # cast_5.py:118-139
                 self.op_embed("hours", "hours_emb", c, k * D, D, sq, small=True)
@@ -1241,9 +1240,9 @@ class Engine:
             # launch that adds to the table gradient has been issued: the embedding backward of a looked-up table (its own launch,
             # or inside a block's backward) -- the head's rows are in from the start
             self.bwd_table_done = 0
-            for i, (name, _, a) in enumerate(self.bwd):
-                sc = a[0] if name == "cr_embed_bwd" else (a[4] if name == "cr_stack_block_bwd" else (a[1] if name.endswith("_scatter") else None))
-                if sc is not None and sc._obj.n_slabs == 0:              # (n_slabs > 0: a small context table, written as slabs)
+            for i, entry in enumerate(self.bwd):
+                sc = self._scatter_desc(entry)
+                if sc is not None and sc.n_slabs == 0:                   # (n_slabs > 0: a small context table, written as slabs)
                     self.bwd_table_done = i + 1
             lay = self.layout
             # the step ends inside Adam (castrec.h, state block): sums and step number are read from the snapshot the
@@ -1281,29 +1280,29 @@ class Engine:
                 cnt = pad.reshape(nb, 256).max(1).astype(np.int32)   # a block shared with a parameter of more slabs reads them all (zeros)
                 self.slab_counts = torch.from_numpy(cnt).to(self.dev)
                 counts = self.slab_counts.data_ptr()
-            ad = L.AdamDesc(self.P.data_ptr(), self.Mom.data_ptr(), self.Vel.data_ptr(), self.Gt.data_ptr(), self.Gs.data_ptr(),
-                            lay.n_table, lay.n_dense, self.n_slabs, float(self.hp.lr), 0.9, 0.98, 1e-8, self.state.data_ptr(),
-                            snap, tsnap, l2, n_l2, *lazy, counts)
+
+            def adam_desc(dense, n_slabs, stats, slab_counts):
+                """cr_adam_desc over the dense gradient `dense` of n_slabs slabs, the loss sums read from `stats`."""
+                d = L.AdamDesc(self.P.data_ptr(), self.Mom.data_ptr(), self.Vel.data_ptr(), self.Gt.data_ptr(), dense,
+                               lay.n_table, lay.n_dense, n_slabs, float(self.hp.lr), 0.9, 0.98, 1e-8, self.state.data_ptr(),
+                               stats, tsnap, l2, n_l2, *lazy, slab_counts)
+                if lazy2 is not None:
+                    d.lazy_ids2, d.n_lazy_ids2 = lazy2.data_ptr(), lazy2.numel()
+                return d
+            ad = adam_desc(self.Gs.data_ptr(), self.n_slabs, snap, counts)                  # the plain step: the slabs themselves
+            ad1 = adam_desc(self.Gflat.data_ptr() + 4 * lay.n_table, 1, self.Gflat.data_ptr() + 4 * lay.n_total, None)   # the reduced bucket
             self._tgd, self._tgrad = None, None
             if self.use_index:
                 # the table section's gradient by gather (castrec.h cr_tgrad_desc): inside the plain step's Adam launch; as a launch of
                 # its own (cr_table_grad -> Gt) in front of the data-parallel exchange, and for grads()
                 assert self._tg_rows is not None, "occurrence index: no gradient-row buffer for the item table's seq lookup"
-                rows, rows2, ld_rows, scale = self._tg_rows
-                se = self.seq_emb
+                tg, se = self._tg_rows, self.seq_emb
                 self._tgd = L.TgradDesc(self.batch_buf.data_ptr() + 4 * self.index_off, None, 0, 0, 0, self.state.data_ptr() + 4 * 4,
-                                        self.index_lay, rows.data_ptr(), rows2.data_ptr() if rows2 is not None else None, ld_rows, scale,
+                                        self.index_lay, tg.rows.data_ptr(), tg.rows2.data_ptr() if tg.rows2 is not None else None, tg.ld, tg.scale,
                                         se.data_ptr(), se.shape[1], self._head_coef(), self.D, self._tg_part.data_ptr(), self._tg_tickets.data_ptr())
                 ad.tg = C.pointer(self._tgd)
                 self._tgrad = ("cr_table_grad", L.lib.cr_table_grad, (C.byref(self._tgd), self.Gt.data_ptr()))
-            if lazy2 is not None:
-                ad.lazy_ids2, ad.n_lazy_ids2 = lazy2.data_ptr(), lazy2.numel()
             self._adam = ("cr_adam_step", L.lib.cr_adam_step, (C.byref(ad),))
-            ad1 = L.AdamDesc(self.P.data_ptr(), self.Mom.data_ptr(), self.Vel.data_ptr(), self.Gt.data_ptr(),
-                             self.Gflat.data_ptr() + 4 * lay.n_table, lay.n_table, lay.n_dense, 1, float(self.hp.lr), 0.9, 0.98,
-                             1e-8, self.state.data_ptr(), self.Gflat.data_ptr() + 4 * lay.n_total, tsnap, l2, n_l2, *lazy, None)
-            if lazy2 is not None:
-                ad1.lazy_ids2, ad1.n_lazy_ids2 = lazy2.data_ptr(), lazy2.numel()
             self._adam_flat = ("cr_adam_step", L.lib.cr_adam_step, (C.byref(ad1),))
             self._reduce = ("cr_reduce_slabs", L.lib.cr_reduce_slabs,
                             (self.Gs.data_ptr(), self.n_slabs, lay.n_dense, self.Gflat.data_ptr() + 4 * lay.n_table,
@@ -1325,7 +1324,7 @@ class Engine:
         for k, a in (("seq", seq), ("pos", pos), ("neg", neg), ("time", time), ("hours", hours), ("days", days)):
             if a is None:
                 continue
-            if self._check_ids and k in used and not isinstance(a, torch.Tensor):
+            if not self.sw.no_id_check and k in used and not isinstance(a, torch.Tensor):
                 a = np.asarray(a)
                 if a.size and (int(a.min()) < 0 or int(a.max()) > limits[k]):
                     raise ValueError("%s ids outside [0, %d] (min %d, max %d): the lookup table has %d rows"
@@ -1506,7 +1505,7 @@ class Engine:
                 hid[i] = 0
             else:
                 hid[i] = np.asarray(a).reshape(-1)
-        if self._check_ids:
+        if not self.sw.no_id_check:
             lo, hi = hid.min(axis=1), hid.max(axis=1)
             for i, key, lim in self._feed_limits:
                 if lo[i] < 0 or hi[i] > lim:
@@ -1730,12 +1729,11 @@ class Engine:
         workgroups (B <= 160, more than one tile: cr_stack.hip, g_stack_pair_max_b), cr_stack_block_bwd once per min(B, n_slabs)
         sequences; every other entry of the fused path is one kernel."""
         n = 0
-        pair_max = int(os.environ.get("CASTREC_STACK_PAIR_MAX_B", 160))
-        for name, _, args in self.fwd + self.bwd:
-            if name in ("cr_stack_fwd", "cr_stack_fwd_head"):
-                sd = args[0]._obj
-                n += sd.n_blocks if (self.B <= pair_max and self.T > 16) else 1
-            elif name == "cr_stack_block_bwd":
+        for entry in self.fwd + self.bwd:
+            sd = self._stack_desc(entry)
+            if sd is not None:
+                n += sd.n_blocks if (self.B <= self.sw.stack_pair_max_b and self.T > 16) else 1
+            elif entry[0] == "cr_stack_block_bwd":
                 per = min(self.B, self.n_slabs)
                 n += -(-self.B // per)
             else:

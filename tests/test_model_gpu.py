@@ -1051,3 +1051,40 @@ def test_l2_emb_regulariser_matches_oracle(E, model):
     assert len(untouched) > 50
     for k in ("item_emb",) + (("time_emb", "hours_emb", "days_emb") if model == "cast_3" else ("pos_emb",)):
         assert float((now[k].cpu().double() - P[k]).abs().max()) < 2e-5, k          # incl. rows the batch never touched
+
+
+def _plan_dump():
+    """tools/plan_dump.py: the canonical text of an engine's launch plan (every entry, every descriptor field, every pointer as
+    <allocation>+<offset>) and the shape at which each planner switch takes effect."""
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "plan_dump.py")
+    spec = importlib.util.spec_from_file_location("plan_dump", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+PLAN = _plan_dump()
+
+
+@pytest.mark.parametrize("switch", PLAN.PLANNER_SWITCHES)
+def test_every_planner_switch_changes_the_plan(E, switch):
+    """test_alternative_kernel_paths_stay_green and its neighbours set a switch and check parity -- which the default path passes too.
+    Here: every switch of engine.Switches (CASTREC_NO_ID_CHECK apart: no planner switch), at the smallest shape whose default plan
+    takes the path it turns off (plan_dump.SWITCH_CHECKS), gives another canonical plan text than the engine without it, and the
+    entries it removes are there without it and gone with it.  Engines are only constructed; nothing is launched."""
+    assert {"CASTREC_" + f.upper() for f in E.Switches._fields} == set(PLAN.SWITCHES)
+    PLAN.switch_check(E, switch)
+
+
+@pytest.mark.parametrize("spec", [dict(model="cast_1", D=50, H=1, T=40, B=3, prec="bf16x3", n_slabs=None),
+                                  dict(model="sasrec", D=128, H=4, T=40, B=3, prec="bf16x3")], ids=["cast_1-50", "sasrec-128"])
+def test_the_plan_is_a_function_of_its_arguments(E, spec):
+    """Two engines of the same arguments in one process: other allocations, the same names and offsets in every launch argument.
+    (The planner keys its records by device pointers: _scatter_recipe, _ln_recipe, _lnf_intent, _grad2.)"""
+    with PLAN.environment({}):
+        a = PLAN.make_engine(E, **spec)
+        b = PLAN.make_engine(E, **spec)
+        assert a.P.data_ptr() != b.P.data_ptr()
+        assert PLAN.canonical(a) == PLAN.canonical(b)
