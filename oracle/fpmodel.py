@@ -155,16 +155,47 @@ def _dropout(x, rate, site, drop):
     return x * keep / (1.0 - rate)
 
 
+# Optional matrix product (test infrastructure): callable(a, b, site) -> a @ b in some model of a narrower arithmetic.  Every
+# matrix product of the graphs -- the q / k / v projections, scores, probabilities x V, w1, w2, mlp.w1, mlp.w2 -- goes through
+# _mm; the head's pos / neg dot products and the element-wise sums do not.  None (the default) = a @ b, the same bits as ever.
+MM_PRODUCT = None
+
+
+def _mm(a, b, site):
+    if MM_PRODUCT is not None:
+        return MM_PRODUCT(a, b, site)
+    return a @ b
+
+
+class rounded_products(object):
+    """with rounded_products(product): ... -- the oracle forms its matrix products with product(a, b, site) (site: "trunk.0.attn.q",
+    ".k", ".v", ".scores", ".pv", "trunk.0.w1", ".w2", "mlp.w1", "mlp.w2"); tests/bf16_ref.py holds the bf16 rounding product."""
+
+    def __init__(self, product):
+        self.product = product
+
+    def __enter__(self):
+        global MM_PRODUCT
+        assert MM_PRODUCT is None, "rounded_products does not nest"
+        MM_PRODUCT = self.product
+        return self
+
+    def __exit__(self, et, ev, tb):
+        global MM_PRODUCT
+        MM_PRODUCT = None
+        return False
+
+
 def multihead_attention(queries, keys, P, pfx, num_heads, rate, drop, site):
     """modules.py:167-277 with causality=True. Returns (outputs, attention_weights[h*N,T,T])."""
     N, T, C = queries.shape
-    Q = queries @ P[pfx + "wq"] + P[pfx + "bq"]                                      # :203
-    K = keys @ P[pfx + "wk"] + P[pfx + "bk"]                                         # :204
-    V = keys @ P[pfx + "wv"] + P[pfx + "bv"]                                         # :205
+    Q = _mm(queries, P[pfx + "wq"], site + ".q") + P[pfx + "bq"]                     # :203
+    K = _mm(keys, P[pfx + "wk"], site + ".k") + P[pfx + "bk"]                        # :204
+    V = _mm(keys, P[pfx + "wv"], site + ".v") + P[pfx + "bv"]                        # :205
     Q_ = torch.cat(torch.split(Q, C // num_heads, dim=2), 0)                         # :208-213 (head j = rows jN..)
     K_ = torch.cat(torch.split(K, C // num_heads, dim=2), 0)
     V_ = torch.cat(torch.split(V, C // num_heads, dim=2), 0)
-    out = Q_ @ K_.transpose(1, 2)                                                    # :216
+    out = _mm(Q_, K_.transpose(1, 2), site + ".scores")                              # :216
     out = out / (K_.shape[-1] ** 0.5)                                                # :219
     key_masks = torch.sign(torch.abs(keys.sum(-1)))                                  # :222
     key_masks = key_masks.repeat(num_heads, 1)[:, None, :].expand(-1, T, -1)         # :223-225
@@ -178,7 +209,7 @@ def multihead_attention(queries, keys, P, pfx, num_heads, rate, drop, site):
     out = out * query_masks                                                          # :253
     out = _dropout(out, rate, site, drop)                                            # :256-257
     attention_weights = out                                                          # :259
-    out = out @ V_                                                                   # :262
+    out = _mm(out, V_, site + ".pv")                                                 # :262
     out = torch.cat(torch.split(out, N, dim=0), 2)                                   # :265-266
     out = out + queries                                                              # :269
     return out, attention_weights
@@ -239,17 +270,17 @@ class handed_over_gates(object):
 
 def feedforward(x, P, pfx, rate, drop, site):
     """modules.py:280-318 (two kernel-size-1 conv1d = per-position dense)."""
-    h = _relu(x @ P[pfx + "w1"] + P[pfx + "b1"], site + ".relu")                     # :300-302
+    h = _relu(_mm(x, P[pfx + "w1"], site + ".w1") + P[pfx + "b1"], site + ".relu")   # :300-302
     h = _dropout(h, rate, site + ".ffn1", drop)                                      # :303-304
-    y = h @ P[pfx + "w2"] + P[pfx + "b2"]                                            # :306-308
+    y = _mm(h, P[pfx + "w2"], site + ".w2") + P[pfx + "b2"]                          # :306-308
     y = _dropout(y, rate, site + ".ffn2", drop)                                      # :309-310
     return y + x                                                                     # :313
 
 
 def mlp(x, P):
     """modules.py:321-335 (ReLU on BOTH layers)."""
-    h = _relu(x @ P["mlp.w1"] + P["mlp.b1"], "mlp.relu1")
-    return _relu(h @ P["mlp.w2"] + P["mlp.b2"], "mlp.relu2")
+    h = _relu(_mm(x, P["mlp.w1"], "mlp.w1") + P["mlp.b1"], "mlp.relu1")
+    return _relu(_mm(h, P["mlp.w2"], "mlp.w2") + P["mlp.b2"], "mlp.relu2")
 
 
 def transformer_stack(x, mask, P, prefix, L, hp, drop, final_ln=True):

@@ -7,9 +7,12 @@ counter-based generator).  Tolerance: 1e-3 is the north-star bound for fp32 forw
                           activations (the quantity the 1e-3 bound is stated on): observed ~1e-5, asserted 2e-4; gradients,
                           against each parameter's own largest gradient: typically 1e-4, up to 9e-4 over 144 surveyed draws of
                           the unfused dropout case (dense layers on the split form as well), asserted 2e-3
-  attn_precision "bf16"   (plain bf16 attention operands; BASELINE.json configs[1] names bf16, the reference is fp32):
-                          asserted 3e-2 on activations and the loss, 2e-1 of the gradient scale on gradients (score errors of
-                          2^-8 |s| are exponentiated by the softmax): the throughput option, not a parity claim"""
+  attn_precision "bf16"   (plain bf16 operands; BASELINE.json configs[1] names bf16, the reference is fp32): every parameter's
+                          gradient, the forward rows and the loss within three times what a rounding model of the oracle itself --
+                          the operands of every matrix product rounded to bf16, tests/bf16_ref.py -- deviates from the exact oracle
+                          at that shape, plus the bf16x3 bound for what the model does not describe; per parameter, relative to its
+                          OWN largest entry.  (Until the model existed: 2e-1 of the GLOBAL gradient scale, which let a parameter
+                          with a small gradient be wrong altogether.)  The old 3e-2 / 2e-2 on activations / loss stay beside it."""
 import math
 import types
 
@@ -17,7 +20,9 @@ import numpy as np
 import pytest
 import torch
 
+import bf16_ref as br
 import dropout_ref as dr
+from bf16_ref import make_batch
 from oracle import fpmodel as fm
 
 pytestmark = pytest.mark.gpu
@@ -28,21 +33,6 @@ def E():
     import castrec_amd  # noqa: F401
     from castrec_amd import engine
     return engine
-
-
-def make_batch(rs, B, T, itemnum, max_bins, all_zero_time_rows=True):
-    seq = rs.randint(1, itemnum + 1, (B, T)); pos = rs.randint(1, itemnum + 1, (B, T)); neg = rs.randint(1, itemnum + 1, (B, T))
-    for b in range(B):
-        n = rs.randint(0, T - 2)
-        seq[b, :n] = 0; pos[b, :n] = 0; neg[b, :n] = 0
-    seq[0, :] = 0; pos[0, :] = 0; neg[0, :] = 0                  # an all-padding sequence
-    seq[0, -1] = 3; pos[0, -1] = 4; neg[0, -1] = 5               # ... with a single real position
-    time = rs.randint(0, max_bins + 1, (B, T)) * (seq != 0)
-    time[:, -1] = 0                                              # most recent item is always bin 0 (sampler.py:61-64)
-    if all_zero_time_rows and B > 2:
-        time[2, :] = 0                                           # all interactions in one bin: no valid context key
-    hours = rs.randint(1, 25, (B, T)) * (seq != 0); days = rs.randint(1, 8, (B, T)) * (seq != 0)
-    return seq, pos, neg, time, hours, days
 
 
 def oracle_drop(eng_mod, seed, step, rate, B, T, H):
@@ -62,10 +52,17 @@ def rel(a, b):
 
 
 def same_run(a, b):
-    """Two engines after the same batches in the same order: the dense parameters agree to rounding (the table gradients are
-    float atomics, so runs of several steps are not bit-identical, and Adam turns a rounding-level change of a near-zero gradient
-    into a step of ~lr on a few parameters: medians of 1e-8 .. 7e-6 over repeated runs), where a swapped or stale batch moves MOST
-    parameters by ~lr (median 3e-3 when the first version of feed() let a copy overtake the step that still read its slot)."""
+    """Two engines after the same batches in the same order.  Where both report bitwise_reproducible (the occurrence index: no float
+    atomics in a step's gradients, dense Adam) they hold the same bits: parameters and both moments.  Otherwise -- CASTREC_NO_INDEX
+    brings the float-atomic table scatters back, and the row-sparse / lazy Adam engines make no such promise -- the runs agree to
+    rounding: Adam turns a rounding-level change of a near-zero gradient into a step of ~lr on a few parameters (medians of
+    1e-8 .. 7e-6 over repeated runs), where a swapped or stale batch moves MOST parameters by ~lr (median 3e-3 when the first
+    version of feed() let a copy overtake the step that still read its slot)."""
+    if a.bitwise_reproducible and b.bitwise_reproducible:
+        same = [torch.equal(x, y) for x, y in ((a.P, b.P), (a.Mom, b.Mom), (a.Vel, b.Vel))]
+        if not all(same):
+            print("same_run: P / Mom / Vel bit-equal: %s; largest |difference| of P %.3g" % (same, float((a.P - b.P).abs().max())))
+        return all(same)
     d = (a.P - b.P).abs()
     st = (float(d.median()), float(torch.quantile(d[:1 << 20], 0.99)), float(d.max()))
     ok = st[0] <= 2e-4 and st[1] <= 1.5e-3 and st[2] <= 5e-3
@@ -81,8 +78,11 @@ CASES = [c + ("f32",) for c in CASES]
 # the bf16-MFMA attention kernels (csrc/cr_attn_bf.hip), fused and unfused row phases, one and two heads
 CASES += [("sasrec", 0.3, True, "bf16x3"), ("cast_1", 0.3, True, "bf16x3"), ("cast_5", 0.0, True, "bf16x3"), ("cast_9", 0.2, True, "bf16x3"),
           ("cast_1", 0.3, False, "bf16x3"), ("sasrec", 0.0, False, "bf16x3"), ("cast_1", 0.3, True, "bf16"), ("sasrec", 0.0, False, "bf16")]
+# ("bf16": what stays of the bounds from before the rounding model, beside the envelope's -- act and loss as they were; grad only sizes
+#  the check that d loss / d bk vanishes)
 TOL = {"f32": dict(grad=2e-4, act=2e-5, loss=2e-5, auc=1e-6), "bf16x3": dict(grad=2e-3, act=2e-4, loss=2e-4, auc=1e-6),
        "bf16": dict(grad=2e-1, act=3e-2, loss=2e-2, auc=None)}
+assert br.GRAD_ABS == TOL["bf16x3"]["grad"] and br.ACT_ABS == TOL["bf16x3"]["act"] and br.LOSS_ABS == TOL["bf16x3"]["loss"]
 
 
 def engine_relu_gates(eng, B, T, drop):
@@ -125,15 +125,40 @@ def oracle_with_engine_gates(eng, B, T, drop, prec, fn):
 SEED_SHIFT = 0          # tools: shift to survey other draws
 
 
-def worst_grad_error(got, G, prec):
+def oracle_or_envelope(eng, model, P, ohp, batch, B, T, drop, prec):
+    """(out, G, env): the oracle's run on the engine's masks (and, off f32, gates: oracle_with_engine_gates); plain bf16: with the
+    rounding model's envelope of that run env = (E, E_act, E_loss) (bf16_ref.envelope: three model runs on the same gates and masks,
+    a fourth where the plan holds the tile kernels cr_block_ln_*, whose row phases are fp32 products whatever the precision)."""
+    if prec != "bf16":
+        return oracle_with_engine_gates(eng, B, T, drop, prec, lambda: fm.loss_and_grads(model, P, ohp, batch, drop)) + (None,)
+    gates, care = engine_relu_gates(eng, B, T, drop)
+    tile_kernels = any(n.startswith("cr_block_ln_") for n, _, _ in eng.fwd + eng.bwd)
+    out, G, Eg, E_act, E_loss = br.envelope(model, P, ohp, batch, drop, gates, care, fp32_row_phases=tile_kernels)
+    return out, G, (Eg, E_act, E_loss)
+
+
+def act_loss_tol(prec, env):
+    """plain bf16: 3 E + the bf16x3 bound, and never looser than the bound from before the model"""
+    tol = TOL[prec]
+    if prec != "bf16":
+        return tol["act"], tol["loss"]
+    return min(tol["act"], br.GRAD_FACTOR * env[1] + br.ACT_ABS), min(tol["loss"], br.GRAD_FACTOR * env[2] + br.LOSS_ABS)
+
+
+def worst_grad_error(got, G, prec, env=None):
     """(error, parameter name, threshold): largest element error of a parameter against that parameter's largest
-    gradient (floored at 1e-3 of the global scale; plain bf16: against the global scale).  d loss / d bk == 0
-    identically (rounding noise on both sides): not compared."""
+    gradient (floored at 1e-3 of the global scale).  Plain bf16: the error as a share of the parameter's own bound
+    (3 E_k + 2e-3) of that scale (bf16_ref.grad_report), threshold 1.  d loss / d bk == 0 identically (rounding noise on both
+    sides): not compared."""
+    if prec == "bf16":
+        rep = br.grad_report(got, G, env[0])
+        share, k, err, Ek, bound = rep[0]
+        return share, "%s: error %.3g of its own scale, E %.3g, bound %.3g" % (k, err, Ek, bound), 1.0
     gmax = max(float(G[k].abs().max()) for k in G)
     names = [k for k in G if not k.endswith(".bk")]
     def emax(k):
         a = got[k].cpu().double().numpy(); b = G[k].numpy()
-        return float(np.abs(a - b).max() / (gmax if prec == "bf16" else max(np.abs(b).max(), 1e-3 * gmax)))
+        return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-3 * gmax))
     w = max((emax(k), k) for k in names)
     return w[0], w[1], TOL[prec]["grad"]
 
@@ -165,23 +190,24 @@ def test_model_grads_and_adam_match_oracle(E, model, rate, fused, prec):
         eng.set_batch(seq, pos, neg, time, hours, days)
         eng.launch_step(apply=False)
         torch.cuda.synchronize()
-        out, G = oracle_with_engine_gates(eng, B, T, drop, prec, lambda: fm.loss_and_grads(model, P, ohp, batch, drop))   # see _other_shapes
+        out, G, env = oracle_or_envelope(eng, model, P, ohp, batch, B, T, drop, prec)                                    # see _other_shapes
+        act_tol, loss_tol = act_loss_tol(prec, env)
         st = eng.state.cpu().numpy()
         n = st[2]
         assert n == float(out["istarget"].sum())
-        assert st[0] / n == pytest.approx(float(out["loss"]), rel=tol["loss"])
+        assert st[0] / n == pytest.approx(float(out["loss"]), rel=loss_tol)
         if tol["auc"] is not None:                       # (a sign(p - n) count: plain bf16 may flip near-ties)
             assert st[1] / n == pytest.approx(float(out["auc"]), abs=tol["auc"])
         got = eng.grads()
         # d loss / d bk == 0 identically (adding a per-query constant to all scores leaves softmax unchanged),
         # so both sides hold rounding noise there: errors are measured against the global gradient scale.
         gmax = max(float(G[k].abs().max()) for k in G)
-        worst = worst_grad_error(got, G, prec)                              # bk: asserted to vanish, below
+        worst = worst_grad_error(got, G, prec, env)                         # bk: asserted to vanish, below
         assert worst[0] < worst[2], worst
         for k in G:
             if k.endswith(".bk"):
                 assert float(got[k].abs().max()) < max(1e-5, 0.1 * tol["grad"]) * gmax and float(G[k].abs().max()) < 1e-9 * gmax
-        assert rel(eng.seq_emb, out["seq_emb"].reshape(B * T, -1)) < tol["act"]
+        assert rel(eng.seq_emb, out["seq_emb"].reshape(B * T, -1)) < act_tol
         # now apply Adam on both sides (engine: re-run the step with the update; grads are recomputed)
         eng.Gt.zero_()
         eng.set_step(step)
@@ -237,7 +263,7 @@ def test_model_grads_and_adam_match_oracle(E, model, rate, fused, prec):
             if k.endswith(".bk"):
                 eng.layout.view(eng.Mom, k).zero_(); eng.layout.view(eng.Vel, k).zero_()
         loss, auc = eng.loss_auc()
-        assert loss == pytest.approx(float(out["loss"]), rel=tol["loss"])
+        assert loss == pytest.approx(float(out["loss"]), rel=loss_tol)
         P = {k: v.detach() for k, v in P.items()}
 
 
@@ -426,9 +452,11 @@ def test_plain_bf16_weight_gradients_at_the_headline_length(monkeypatch, E):
 
 def test_plain_bf16_at_the_headline_length_against_the_oracle(E):
     """Plain bf16 (BASELINE configs[1] names bf16) at the bench workload's length and width -- cast_1, T 200, D 50 -- against the fp64
-    oracle, every parameter's gradient relative to that parameter's OWN largest entry (the small-shape cases compare with the global
+    oracle, every parameter's gradient relative to that parameter's OWN largest entry (the small-shape cases compared with the global
     gradient scale at 2e-1, which is how a 47 % error of one weight gradient at this length stayed unseen until round 5): measured
-    <= 2.7e-2 over two parameter draws (tools/probes/bf16_vs_oracle.py), asserted 6e-2; loss 2e-3."""
+    <= 2.7e-2 over two parameter draws (tools/probes/bf16_vs_oracle.py), asserted 6e-2; loss 2e-3.  That 6e-2 was set from the kernel's
+    own figure; beside it now the bound that is not: each parameter within 3 E_k + 2e-3, the forward rows and the loss likewise, E from
+    the oracle's rounding model at this very draw (tests/bf16_ref.py) -- whichever is tighter for a parameter decides."""
     B, T, D, H = 4, 200, 50, 1
     for init in ("oracle", "engine"):
         rs = np.random.RandomState(5)
@@ -447,10 +475,13 @@ def test_plain_bf16_at_the_headline_length_against_the_oracle(E):
         eng.launch_step(apply=False)
         torch.cuda.synchronize()
         drop = oracle_drop(E, 13, 1, 0.2, B, T, H)
-        out, G = oracle_with_engine_gates(eng, B, T, drop, "bf16", lambda: fm.loss_and_grads("cast_1", P, ohp, fm.to_batch(*batch), drop))
+        out, G, env = oracle_or_envelope(eng, "cast_1", P, ohp, fm.to_batch(*batch), B, T, drop, "bf16")
         st = eng.state.cpu().numpy()
-        assert st[0] / st[2] == pytest.approx(float(out["loss"]), rel=2e-3)
+        assert st[0] / st[2] == pytest.approx(float(out["loss"]), rel=min(2e-3, act_loss_tol("bf16", env)[1]))
         got = eng.grads()
+        worst = worst_grad_error(got, G, "bf16", env)                      # the rounding model's bound per parameter, beside the flat 6e-2
+        assert worst[0] < worst[2], (init, worst)
+        assert rel(eng.seq_emb, out["seq_emb"].reshape(B * T, -1)) < act_loss_tol("bf16", env)[0]
         errs = sorted(((float((got[k].cpu().double() - G[k]).abs().max() / max(float(G[k].abs().max()), 1e-12)), k)
                        for k in G if not k.endswith(".bk")), reverse=True)
         assert errs[0][0] < 6e-2, (init, errs[:5])
@@ -576,12 +607,12 @@ def test_index_and_atomics_paths_agree(E, monkeypatch):
     assert same_run(a, b)
 
 
-def _other_shapes(E, model, D, H, T, L, B=3, prec="f32", itemnum=41, max_bins=9, zipf=None, kink_free=False, n_slabs=5, dropout=0.1, grad_tol=None):
+def _other_shapes(E, model, D, H, T, L, B=3, prec="f32", itemnum=41, max_bins=9, zipf=None, kink_free=False, n_slabs=5, dropout=0.1, grad_tol=None,
+                  draw=0, report=None):
     """kink_free: the feed-forward pre-activations are pushed away from the ReLU kink (small W1, biases of +-1 alternating by
     unit), the oracle runs with ITS OWN gates (no hand-over), and the test first proves that the engine's gates are the
     same everywhere: gradient parity of the split-precision kernels with nothing taken from the engine but the dropout masks."""
-    tol = TOL[prec]
-    rs = np.random.RandomState(D + T)
+    rs = np.random.RandomState(D + T + draw)
     hp = E.Hyper(maxlen=T, hidden_units=D, num_blocks=L, num_heads=H, dropout_rate=dropout, max_bins=max_bins,
                  num_context_blocks=1, lr=1e-3, seed=11)
     ohp = fm.Hyper(maxlen=T, hidden_units=D, num_blocks=L, num_heads=H, dropout_rate=dropout, max_bins=max_bins,
@@ -612,7 +643,9 @@ def _other_shapes(E, model, D, H, T, L, B=3, prec="f32", itemnum=41, max_bins=9,
     drop = oracle_drop(E, 11, 1, dropout, B, T, H)
     # split-precision attention perturbs activations by ~1e-5: the oracle takes the engine's ReLU gates like it takes its
     # dropout masks, so that units within 1e-5 of the kink do not flip on one side only (see fpmodel.RELU_GATES)
-    run = lambda: fm.loss_and_grads(model, P, ohp, fm.to_batch(seq, pos, neg, time, hours, days), drop)
+    batch = fm.to_batch(seq, pos, neg, time, hours, days)
+    run = lambda: fm.loss_and_grads(model, P, ohp, batch, drop)
+    env = None
     if kink_free:
         gates, care = engine_relu_gates(eng, B, T, drop)
         with fm.handed_over_gates(gates, care, max_share=0.0, min_units=0) as audit:      # premise: not ONE gate differs ...
@@ -621,13 +654,24 @@ def _other_shapes(E, model, D, H, T, L, B=3, prec="f32", itemnum=41, max_bins=9,
         assert all(float(g.float().mean()) > 0.2 and float(g.float().mean()) < 0.8 for g in gates.values())   # ... on a real on / off mix
         out, G = run()                                                                    # the oracle on its own gates
     else:
-        out, G = oracle_with_engine_gates(eng, B, T, drop, prec, run)
+        out, G, env = oracle_or_envelope(eng, model, P, ohp, batch, B, T, drop, prec)
+    act_tol, loss_tol = act_loss_tol(prec, env)
     st = eng.state.cpu().numpy()
-    assert st[0] / st[2] == pytest.approx(float(out["loss"]), rel=tol["loss"])
+    loss_ref = float(out["loss"].detach())
+    loss_err = abs(float(st[0] / st[2]) - loss_ref) / abs(loss_ref)
     got = eng.grads()
-    worst = worst_grad_error(got, G, prec)
-    assert worst[0] < (2 * worst[2] if grad_tol is None else grad_tol), worst
-    assert rel(eng.seq_emb, out["seq_emb"].reshape(B * T, -1)) < tol["act"]     # forward parity (north-star bound 1e-3)
+    worst = worst_grad_error(got, G, prec, env)
+    act_err = rel(eng.seq_emb, out["seq_emb"].reshape(B * T, -1))
+    if prec == "bf16":
+        print("plain bf16 %s D %d H %d T %d B %d: loss %.3g (bound %.3g), rows %.3g (bound %.3g), worst gradient at %.2f of its bound (%s)"
+              % (model, D, H, T, B, loss_err, loss_tol, act_err, act_tol, worst[0], worst[1]))
+    if report is not None:                               # (tools/probes/bf16_vs_oracle.py: the figures, taken before anything is asserted)
+        report.append(dict(eng=eng, loss=(loss_err, loss_tol), act=(act_err, act_tol), worst=worst,
+                           grads=br.grad_report(got, G, env[0]) if env is not None else None, env=env))
+    assert loss_err <= loss_tol, (loss_err, loss_tol)
+    # (f32 / bf16x3: twice the bound of the small-shape cases; plain bf16: the parameter's own bound, nothing on top)
+    assert worst[0] < ((1 if prec == "bf16" else 2) * worst[2] if grad_tol is None else grad_tol), worst
+    assert act_err < act_tol, (act_err, act_tol)                                # forward parity (north-star bound 1e-3)
     return eng
 
 
@@ -798,9 +842,8 @@ def test_graph_replay_equals_eager(E):
     a.train_step(*batch)
     b.train_step(*batch)
     torch.cuda.synchronize()
-    nt = a.layout.n_table
-    assert torch.equal(a.P[nt:], b.P[nt:])                         # dense part: slab reduction, bit-identical
-    assert torch.allclose(a.P[:nt], b.P[:nt], rtol=0, atol=1e-6)   # item table: float atomics may reorder
+    # the occurrence index left no float atomics in the gradients: tables and dense part alike hold the same bits, moments included
+    assert a.bitwise_reproducible and b.bitwise_reproducible and same_run(a, b)
     assert a.loss_auc() == pytest.approx(b.loss_auc(), rel=1e-6)   # loss sums use float atomics across workgroups
     for _ in range(3):                                             # replay keeps tracking eager training
         batch = make_batch(rs, B, T, itemnum, 20)
@@ -812,8 +855,9 @@ def test_graph_replay_equals_eager(E):
 
 
 def same_loss_auc(a, b, pos, rel=2e-3):
-    """Loss to `rel`; the AUC (the fraction of target rows with pos logit > neg logit, sasrec.py:113-115) of two runs whose table
-    gradients were summed by float atomics in different orders may differ by ONE row whose two logits all but tie: 1 / n_targets."""
+    """Loss to `rel` (the loss sums are float atomics across workgroups still); the AUC (the fraction of target rows with pos logit >
+    neg logit, sasrec.py:113-115) of two runs that are not bit-equal (same_run) may differ by ONE row whose two logits all but tie:
+    1 / n_targets."""
     (la, aa), (lb, ab) = a.loss_auc(), b.loss_auc()
     n_t = max(int((pos != 0).sum()), 1)
     return la == pytest.approx(lb, rel=rel) and abs(aa - ab) <= 1.01 / n_t + rel * abs(ab)
@@ -874,7 +918,7 @@ def test_several_fed_steps_per_graph_launch(E):
     b.capture()
     b.enable_feed(n_slots=16, steps_per_graph=4)
     assert b.graph_multi is not None and b.graph_steps == 4
-    batches = [make_batch(rs, B, T, itemnum, 20) for _ in range(14)]       # (few steps: float-atomic table gradients let runs drift apart)
+    batches = [make_batch(rs, B, T, itemnum, 20) for _ in range(14)]
     for bt in batches:
         a.train_step(*bt)
     it = iter(batches)
@@ -908,7 +952,7 @@ def test_deep_feeding_around_multi_step_launches_keeps_slot_reuse_ordered(E):
     b.P.copy_(a.P)
     b.capture()
     b.enable_feed(n_slots=16, steps_per_graph=4)
-    batches = [make_batch(rs, B, T, itemnum, 20) for _ in range(26)]      # (float-atomic table gradients let longer runs drift: same_run)
+    batches = [make_batch(rs, B, T, itemnum, 20) for _ in range(26)]
     for bt in batches:
         a.train_step(*bt)
     it = iter(batches)
