@@ -185,7 +185,7 @@ def file_flags(source_name, timeline=False):
 
 
 # every object depends on these (a change rebuilds the library; the ISA summaries carry their digest)
-HEADERS = [os.path.join(CSRC, h) for h in ("cr_common.hpp", "cr_attn_common.hpp", "cr_bf16.hpp", "cr_rlayout.hpp", "cr_rbwd.hpp")] \
+HEADERS = [os.path.join(CSRC, h) for h in ("cr_common.hpp", "cr_attn_common.hpp", "cr_bf16.hpp", "cr_rlayout.hpp", "cr_rbwd.hpp", "cr_head.hpp")] \
     + [os.path.join(ROOT, "include", "castrec.h")]
 # ... and single sources on these besides
 EXTRA_DEPS = {"cr_adam.hip": ["cr_tgrad.hpp"], "cr_tgrad.hip": ["cr_tgrad.hpp"]}

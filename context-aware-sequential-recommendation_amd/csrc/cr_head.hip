@@ -2,10 +2,16 @@
 // and -- fused in the same pass -- the gradients wrt the sequence embedding and the item table.
 // Gradients are UN-normalised (scaled by n_target); cr_adam_step divides by n_target, which is only
 // known after the whole batch (all ranks) has been reduced (sasrec.py:104-108).
+//
+// Three kernels, one row body.  A lane holds N elements of each of the row's arrays; what is computed on them is written once, below
+// (head_row_bce, head_row_ln_bwd, head_scatter, head_sums_fold, head_slab_fold), over a column mapping: HeadColStrided (slot i of lane l
+// is column l + LPR i: dword accesses) or HeadColPacked (column N l + i: one 16- or 8-byte access).  The kernels keep what is theirs:
+// how rows are dealt to workgroups and how loads and stores are issued.  The BCE formula itself: cr_head.hpp (shared with cr_stack.hip).
 #include <math.h>
 
 #include <stdlib.h>
 #include "cr_common.hpp"
+#include "cr_head.hpp"
 
 // Row mapping as in cr_layernorm.hip: hidden sizes <= 64 give a row 16 lanes (4 rows per wave in flight,
 // DPP row sums); larger ones a whole wave.
@@ -19,90 +25,183 @@ __device__ __forceinline__ float head_row_sum(float v) {
     return wave_sum(v);
 }
 
-// (head_snapshot: cr_common.hpp)
+template <int LPR> struct HeadColStrided { static __device__ __forceinline__ int col(int l, int i) { return l + LPR * i; } };
+template <int VEC> struct HeadColPacked { static __device__ __forceinline__ int col(int l, int i) { return VEC * l + i; } };
+
+// (cr_head_desc BY VALUE into the helpers that store through it: behind a reference the compiler no longer knows the descriptor's
+// pointers for global ones in k_head<16, 4>, whose stores and atomics then become flat_ instructions)
+// The head of one row: s, ep, en hold the lane's elements of the sequence embedding and the two table rows (0 beyond D, 0 for id 0:
+// row 0 == zeros, modules.py:154-156).  Adds the row's terms to `acc`, writes its per-row outputs (first lane) and returns the
+// coefficients of the gradient row (head_dy) -- 0 unless `grad`.  p: the pos id, 0 for a lane group without a row.
+template <int LPR, int N>
+__device__ __forceinline__ HeadBce head_row_bce(const cr_head_desc d, int l, int m, bool act, bool grad, int p, const float (&s)[N],
+                                                const float (&ep)[N], const float (&en)[N], HeadSums& acc) {
+    float pl = 0.0f, nl = 0.0f;
+#pragma unroll
+    for (int i = 0; i < N; ++i) { pl += ep[i] * s[i]; nl += en[i] * s[i]; }
+    pl = head_row_sum<LPR>(pl);                                                // sasrec.py:100
+    nl = head_row_sum<LPR>(nl);                                                // sasrec.py:101
+    const float ist = (p != 0) ? 1.0f : 0.0f;                                  // sasrec.py:104
+    HeadBce b = head_bce(pl, nl, ist);
+    if (!grad) { b.dpl = 0.0f; b.dnl = 0.0f; }
+    if (l == 0 && act) {
+        const HeadSums r = head_bce_first_lane(d, m, pl, nl, ist, b);
+        acc.loss += r.loss; acc.auc += r.auc; acc.n += r.n;
+    }
+    return b;
+}
+
+// The gradient row dy and, while it is in registers, the LayerNorm backward of the row (modules.py:74-78; cr_layernorm.hip's arithmetic):
+// x -> dx, and the row's terms of dgamma / dbeta onto ag / ab.
+template <int LPR, int N, class COL>
+__device__ __forceinline__ void head_row_ln_bwd(int l, int D, float invD, float eps, const HeadBce& b, const float (&ep)[N], const float (&en)[N],
+                                                const float (&x)[N], const float (&gam)[N], float (&ag)[N], float (&ab)[N], float (&dy)[N],
+                                                float (&dx)[N]) {
+    float xs = 0.0f;
+#pragma unroll
+    for (int i = 0; i < N; ++i) xs += x[i];
+    const float mean = head_row_sum<LPR>(xs) * invD;
+    float v = 0.0f, xh[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        xh[i] = (COL::col(l, i) < D) ? (x[i] - mean) : 0.0f;
+        v += xh[i] * xh[i];
+    }
+    const float rstd = 1.0f / sqrtf(head_row_sum<LPR>(v) * invD + eps);
+    float c1 = 0.0f, c2 = 0.0f;
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        dy[i] = head_dy(b, ep[i], en[i]);
+        xh[i] *= rstd;
+        const float dg = dy[i] * gam[i];
+        c1 += dg;
+        c2 += dg * xh[i];
+        ag[i] += dy[i] * xh[i];
+        ab[i] += dy[i];
+    }
+    c1 = head_row_sum<LPR>(c1) * invD;
+    c2 = head_row_sum<LPR>(c2) * invD;
+#pragma unroll
+    for (int i = 0; i < N; ++i) dx[i] = cr_ln_bwd_tail(dy[i] * gam[i], c1, xh[i], c2, rstd);
+}
+
+// The item table's gradient by float atomics, for the wave's row group [mb, mb + 64 / LPR) below mend.  16 lanes per row: one CONTIGUOUS
+// 4*D-byte burst per table row (lane = column), the shape the atomic units take at full rate -- with the row mapping one instruction
+// would carry four 64-byte pieces of four different rows; the row's scalars come from its lane group, its s is re-read (L1 hit).
+// Wider rows: the lane's own strided columns.
+template <int LPR, int N>
+__device__ __forceinline__ void head_scatter(const cr_head_desc d, int lane, int l, int mb, int mend, bool act, int p, int ng,
+                                             const HeadBce& b, const float (&s)[N]) {
+    if (LPR == 16) {
+#pragma unroll
+        for (int rr = 0; rr < 64 / LPR; ++rr) {
+            const int mr = mb + rr;
+            const float gpr = __shfl(b.dpl, rr * LPR, 64), gnr = __shfl(b.dnl, rr * LPR, 64);
+            const int pr = __shfl(p, rr * LPR, 64), nr = __shfl(ng, rr * LPR, 64);
+            if (mr < mend && pr != 0 && lane < d.D) {                          // a row counts where its pos id is not 0
+                const float sv = d.seq_emb[(size_t)mr * d.ld + lane];
+                atomicAdd(d.table_grad + (size_t)pr * d.D + lane, gpr * sv);
+                if (nr != 0) atomicAdd(d.table_grad + (size_t)nr * d.D + lane, gnr * sv);
+            }
+        }
+    } else if (act && p != 0) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const int c = l + LPR * i;
+            if (c < d.D) {
+                atomicAdd(d.table_grad + (size_t)p * d.D + c, b.dpl * s[i]);
+                if (ng != 0) atomicAdd(d.table_grad + (size_t)ng * d.D + c, b.dnl * s[i]);
+            }
+        }
+    }
+}
+
+// The workgroup's three sums (SLOTS row slots: waves x rows per wave) onto state[0..2].  head_snapshot (cr_common.hpp) must follow once
+// the kernel has nothing else to write; the _ln kernels fold their slabs in between, under the atomics' round trip.
+template <int SLOTS>
+__device__ __forceinline__ void head_sums_fold(float* state, const HeadSums& acc, int l, int slot) {
+    __shared__ float red[3][SLOTS];
+    if (l == 0) { red[0][slot] = acc.loss; red[1][slot] = acc.auc; red[2][slot] = acc.n; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        float v = 0.0f;
+        for (int i = 0; i < SLOTS; ++i) v += red[threadIdx.x][i];
+        if (v != 0.0f) atomicAdd(state + threadIdx.x, v);
+    }
+}
+
+// dgamma / dbeta of a 16-wave workgroup -> its slab: the wave's row groups by shuffles, then the 16 waves in a fixed order
+// (cr_layernorm.hip).  One pass over two [16][COLS] arrays -- except at 512 columns, where the two do not fit the 64 KB of static LDS:
+// there one array, dgamma and dbeta in turn.
+template <int LPR, int N, class COL>
+__device__ __forceinline__ void head_slab_fold(const cr_ln_bwd_desc& n, int D, int wave, int sub, int l, float (&ag)[N], float (&ab)[N]) {
+    constexpr int COLS = LPR * N;
+    constexpr bool BOTH = COLS <= 256;
+    __shared__ float part[BOTH ? 2 : 1][16][COLS];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+#pragma unroll
+        for (int o = LPR; o < 64; o <<= 1) {
+            ag[i] += __shfl_xor(ag[i], o, 64);
+            ab[i] += __shfl_xor(ab[i], o, 64);
+        }
+    }
+#pragma unroll
+    for (int pass = 0; pass < (BOTH ? 1 : 2); ++pass) {
+        if (pass) __syncthreads();
+        if (sub == 0) {
+#pragma unroll
+            for (int i = 0; i < N; ++i) {
+                const int c = COL::col(l, i);
+                part[0][wave][c] = pass == 0 ? ag[i] : ab[i];
+                if (BOTH) part[BOTH][wave][c] = ab[i];
+            }
+        }
+        __syncthreads();
+        for (int c = threadIdx.x; c < D; c += 1024) {
+            float g = 0.0f, b = 0.0f;
+#pragma unroll
+            for (int w = 0; w < 16; ++w) {
+                g += part[0][w][c];
+                if (BOTH) b += part[BOTH][w][c];
+            }
+            (pass == 0 ? n.dgamma : n.dbeta)[(size_t)blockIdx.x * n.slab_stride + c] = g;
+            if (BOTH) n.dbeta[(size_t)blockIdx.x * n.slab_stride + c] = b;
+        }
+    }
+}
+
+// The head alone: 256 threads, row groups dealt to the waves of the whole grid in turn.
 template <int LPR, int MAXC>
 __global__ __launch_bounds__(256) void k_head(cr_head_desc d) {
     constexpr int RPW = 64 / LPR;
-    __shared__ float red[3][4 * RPW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, l = lane % LPR;
-    float loss_acc = 0.0f, auc_acc = 0.0f, n_acc = 0.0f;
+    const bool need = d.d_seq_emb || d.table_grad || d.coef_out;
+    HeadSums acc = {0.0f, 0.0f, 0.0f};
     for (int mb = (blockIdx.x * 4 + wave) * RPW; mb < d.M; mb += gridDim.x * 4 * RPW) {
         const int m = mb + sub;
         const bool act = m < d.M;
         const int mm = act ? m : d.M - 1;
         const int p = act ? d.pos[mm] : 0, ng = act ? d.neg[mm] : 0;
         float s[MAXC], ep[MAXC], en[MAXC];
-        float pl = 0.0f, nl = 0.0f, gp = 0.0f, gn = 0.0f;
 #pragma unroll
         for (int i = 0; i < MAXC; ++i) {
             const int c = l + LPR * i;
             const bool ok = c < d.D;
             s[i] = ok ? d.seq_emb[(size_t)mm * d.ld + c] : 0.0f;
-            ep[i] = (ok && p != 0) ? d.table[(size_t)p * d.D + c] : 0.0f;      // row 0 == zeros (modules.py:154-156)
+            ep[i] = (ok && p != 0) ? d.table[(size_t)p * d.D + c] : 0.0f;
             en[i] = (ok && ng != 0) ? d.table[(size_t)ng * d.D + c] : 0.0f;
-            pl += ep[i] * s[i];
-            nl += en[i] * s[i];
         }
-        pl = head_row_sum<LPR>(pl);                                            // sasrec.py:100
-        nl = head_row_sum<LPR>(nl);                                            // sasrec.py:101
-        const float ist = (p != 0) ? 1.0f : 0.0f;                              // sasrec.py:104
-        const float sp = 1.0f / (1.0f + expf(-pl)), sn = 1.0f / (1.0f + expf(-nl));
-        if (l == 0 && act) {
-            loss_acc += ist * (-logf(sp + 1e-24f) - logf(1.0f - sn + 1e-24f)); // sasrec.py:105-108
-            const float dlt = pl - nl;
-            const float sg = (dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? -1.0f : 0.0f);
-            auc_acc += ist * (sg + 1.0f) * 0.5f;                               // sasrec.py:113-115
-            n_acc += ist;
-            if (d.pos_logits) d.pos_logits[m] = pl;
-            if (d.neg_logits) d.neg_logits[m] = nl;
-        }
-        if (act && (d.d_seq_emb || d.table_grad || d.coef_out)) {
-            // d/dpl [-log(sig(pl)+e)] = -sig(1-sig)/(sig+e);  d/dnl [-log(1-sig(nl)+e)] = sig(1-sig)/(1-sig+e)
-            const float dpl = -ist * sp * (1.0f - sp) / (sp + 1e-24f);
-            const float dnl = ist * sn * (1.0f - sn) / (1.0f - sn + 1e-24f);
-            if (d.coef_out && l == 0) {                  // the item table's gradient is gathered from the batch's occurrence index
-                d.coef_out[m] = dpl;
-                d.coef_out[(size_t)d.M + m] = dnl;
-            }
+        const HeadBce b = head_row_bce<LPR>(d, l, m, act, act && need, p, s, ep, en, acc);
+        if (act && d.d_seq_emb) {
 #pragma unroll
-            for (int i = 0; i < MAXC; ++i) {
-                const int c = l + LPR * i;
-                if (c < d.D) {
-                    if (d.d_seq_emb) d.d_seq_emb[(size_t)m * d.ldd + c] = dpl * ep[i] + dnl * en[i];
-                    if (LPR != 16 && d.table_grad && ist != 0.0f) {
-                        if (p != 0) atomicAdd(d.table_grad + (size_t)p * d.D + c, dpl * s[i]);
-                        if (ng != 0) atomicAdd(d.table_grad + (size_t)ng * d.D + c, dnl * s[i]);
-                    }
-                }
-            }
-            gp = dpl;
-            gn = dnl;
+            for (int i = 0; i < MAXC; ++i)
+                if (l + LPR * i < d.D) d.d_seq_emb[(size_t)m * d.ldd + l + LPR * i] = head_dy(b, ep[i], en[i]);
         }
-        if (LPR == 16 && d.table_grad) {
-            // Table rows get one CONTIGUOUS 4*D-byte float-atomic burst each (lane = column), the shape the atomic
-            // units take at full rate; with the 16-lanes-per-row mapping above one instruction carried four 64-byte
-            // pieces of four different rows.  The row's scalars come from its lane group, s[] is re-read (L1 hit).
-#pragma unroll
-            for (int rr = 0; rr < RPW; ++rr) {
-                const int mr = mb + rr;
-                const float gpr = __shfl(gp, rr * LPR, 64), gnr = __shfl(gn, rr * LPR, 64);
-                const int pr = __shfl(p, rr * LPR, 64), nr = __shfl(ng, rr * LPR, 64);
-                if (mr < d.M && pr != 0 && lane < d.D) {                       // ist == (pos id != 0)
-                    const float sv = d.seq_emb[(size_t)mr * d.ld + lane];
-                    atomicAdd(d.table_grad + (size_t)pr * d.D + lane, gpr * sv);
-                    if (nr != 0) atomicAdd(d.table_grad + (size_t)nr * d.D + lane, gnr * sv);
-                }
-            }
-        }
+        if (d.table_grad) head_scatter<LPR>(d, lane, l, mb, d.M, act, p, ng, b, s);
     }
-    if (l == 0) { red[0][wave * RPW + sub] = loss_acc; red[1][wave * RPW + sub] = auc_acc; red[2][wave * RPW + sub] = n_acc; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float v = 0.0f;
-        for (int i = 0; i < 4 * RPW; ++i) v += red[threadIdx.x][i];
-        if (v != 0.0f) atomicAdd(d.state + threadIdx.x, v);
-    }
+    head_sums_fold<4 * RPW>(d.state, acc, l, wave * RPW + sub);
     head_snapshot(d.state, gridDim.x);
 }
 
@@ -110,19 +209,12 @@ extern "C" int cr_head_fwd_bwd(const cr_head_desc* d, void* stream) {
     CR_REQUIRE(d && d->seq_emb && d->table && d->pos && d->neg && d->state, "cr_head_fwd_bwd: NULL pointer");
     CR_REQUIRE(d->M > 0 && d->D > 0 && d->V > 0 && d->ld >= d->D, "cr_head_fwd_bwd: bad shape");
     if (d->D > 512) return cr_set_error(CR_ERR_UNSUPPORTED, "cr_head_fwd_bwd: D=%d > 512", d->D);
-    if (d->D <= 64) {
-        int grid = cr_ceil_div(d->M, 16);
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL((k_head<16, 4>), dim3(grid), dim3(256), 0, cr_stream(stream), *d);
-    } else if (d->D <= 128) {
-        int grid = cr_ceil_div(d->M, 8);
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL((k_head<32, 4>), dim3(grid), dim3(256), 0, cr_stream(stream), *d);
-    } else {
-        int grid = cr_ceil_div(d->M, 4);
-        if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL((k_head<64, 8>), dim3(grid), dim3(256), 0, cr_stream(stream), *d);
-    }
+    const int lpr = d->D <= 64 ? 16 : d->D <= 128 ? 32 : 64;
+    int grid = cr_ceil_div(d->M, 4 * (64 / lpr));                              // a workgroup's four waves hold 64 / lpr rows each
+    if (grid > 2048) grid = 2048;
+    if (lpr == 16) hipLaunchKernelGGL((k_head<16, 4>), dim3(grid), dim3(256), 0, cr_stream(stream), *d);
+    else if (lpr == 32) hipLaunchKernelGGL((k_head<32, 4>), dim3(grid), dim3(256), 0, cr_stream(stream), *d);
+    else hipLaunchKernelGGL((k_head<64, 8>), dim3(grid), dim3(256), 0, cr_stream(stream), *d);
     return cr_check_launch("cr_head_fwd_bwd");
 }
 
@@ -130,10 +222,11 @@ extern "C" int cr_head_fwd_bwd(const cr_head_desc* d, void* stream) {
 // dy = dpl * E[pos] + dnl * E[neg] never leaves the registers it is computed in -- it goes straight through the
 // LayerNorm backward of cr_layernorm.hip (same row mapping, same arithmetic, same slab reduction: n_slabs workgroups
 // of 16 waves, workgroup s owns rows [s*rps, (s+1)*rps) and writes slab s of dgamma / dbeta).
+// This form reads a row as LPR-strided dwords and requests the ids of a row group one iteration ahead.
 template <int LPR, int MAXC>
 __global__ __launch_bounds__(1024) void k_head_ln(cr_head_desc d, cr_ln_bwd_desc n) {
     constexpr int RPW = 64 / LPR;
-    __shared__ float red[3][16 * RPW];
+    using COL = HeadColStrided<LPR>;
     cr_kernarg_touch<sizeof(cr_head_desc) + sizeof(cr_ln_bwd_desc)>();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, l = lane % LPR;
@@ -142,12 +235,11 @@ __global__ __launch_bounds__(1024) void k_head_ln(cr_head_desc d, cr_ln_bwd_desc
     float gam[MAXC], ag[MAXC], ab[MAXC];
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
-        const int c = l + LPR * i;
-        gam[i] = (c < d.D) ? n.gamma[c] : 0.0f;
+        gam[i] = (COL::col(l, i) < d.D) ? n.gamma[COL::col(l, i)] : 0.0f;
         ag[i] = 0.0f; ab[i] = 0.0f;
     }
     const float invD = 1.0f / (float)d.D;
-    float loss_acc = 0.0f, auc_acc = 0.0f, n_acc = 0.0f;
+    HeadSums acc = {0.0f, 0.0f, 0.0f};
     // the ids of a row group are requested one iteration ahead: id -> table row is a dependent pair of memory round trips, and a
     // wave runs only two iterations (100 rows per workgroup, 16 waves x 4 rows)
     int p_n = 0, ng_n = 0;
@@ -165,152 +257,30 @@ __global__ __launch_bounds__(1024) void k_head_ln(cr_head_desc d, cr_ln_bwd_desc
             p_n = 0; ng_n = 0;
             if (mn < m1) { p_n = d.pos[mn]; ng_n = d.neg[mn]; }
         }
-        float s[MAXC], ep[MAXC], en[MAXC], x[MAXC];
-        float pl = 0.0f, nl = 0.0f, xs = 0.0f;
+        float s[MAXC], ep[MAXC], en[MAXC], x[MAXC], dy[MAXC], dx[MAXC];
 #pragma unroll
         for (int i = 0; i < MAXC; ++i) {
-            const int c = l + LPR * i;
+            const int c = COL::col(l, i);
             const bool ok = c < d.D;
             s[i] = ok ? d.seq_emb[(size_t)mm * d.ld + c] : 0.0f;
             x[i] = ok ? n.x[(size_t)mm * n.ldx + c] : 0.0f;
-            ep[i] = (ok && p != 0) ? d.table[(size_t)p * d.D + c] : 0.0f;      // row 0 == zeros (modules.py:154-156)
+            ep[i] = (ok && p != 0) ? d.table[(size_t)p * d.D + c] : 0.0f;
             en[i] = (ok && ng != 0) ? d.table[(size_t)ng * d.D + c] : 0.0f;
-            pl += ep[i] * s[i];
-            nl += en[i] * s[i];
-            xs += x[i];
         }
-        pl = head_row_sum<LPR>(pl);                                            // sasrec.py:100
-        nl = head_row_sum<LPR>(nl);                                            // sasrec.py:101
-        const float ist = (p != 0) ? 1.0f : 0.0f;                              // sasrec.py:104
-        const float sp = 1.0f / (1.0f + expf(-pl)), sn = 1.0f / (1.0f + expf(-nl));
-        if (l == 0 && act) {
-            loss_acc += ist * (-logf(sp + 1e-24f) - logf(1.0f - sn + 1e-24f)); // sasrec.py:105-108
-            const float dlt = pl - nl;
-            const float sgn = (dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? -1.0f : 0.0f);
-            auc_acc += ist * (sgn + 1.0f) * 0.5f;                              // sasrec.py:113-115
-            n_acc += ist;
-            if (d.pos_logits) d.pos_logits[m] = pl;
-            if (d.neg_logits) d.neg_logits[m] = nl;
-        }
-        const float dpl = act ? -ist * sp * (1.0f - sp) / (sp + 1e-24f) : 0.0f;
-        const float dnl = act ? ist * sn * (1.0f - sn) / (1.0f - sn + 1e-24f) : 0.0f;
-        if (d.coef_out && l == 0 && act) {               // the item table's gradient is gathered from the batch's occurrence index
-            d.coef_out[m] = dpl;
-            d.coef_out[(size_t)d.M + m] = dnl;
-        }
-        // ---- LayerNorm backward of this row (modules.py:74-78), dy in registers
-        const float mean = head_row_sum<LPR>(xs) * invD;
-        float v = 0.0f;
-#pragma unroll
-        for (int i = 0; i < MAXC; ++i) {
-            const float dxm = (l + LPR * i < d.D) ? (x[i] - mean) : 0.0f;
-            v += dxm * dxm;
-        }
-        const float rstd = 1.0f / sqrtf(head_row_sum<LPR>(v) * invD + n.eps);
-        float dy[MAXC], c1 = 0.0f, c2 = 0.0f;
-#pragma unroll
-        for (int i = 0; i < MAXC; ++i) {
-            const int c = l + LPR * i;
-            dy[i] = dpl * ep[i] + dnl * en[i];
-            if (act && c < d.D && d.d_seq_emb) d.d_seq_emb[(size_t)m * d.ldd + c] = dy[i];
-            const float xh = (c < d.D) ? (x[i] - mean) * rstd : 0.0f;
-            x[i] = xh;
-            const float dg = dy[i] * gam[i];
-            c1 += dg;
-            c2 += dg * xh;
-            ag[i] += dy[i] * xh;
-            ab[i] += dy[i];
-        }
-        c1 = head_row_sum<LPR>(c1) * invD;
-        c2 = head_row_sum<LPR>(c2) * invD;
+        const HeadBce b = head_row_bce<LPR>(d, l, m, act, act, p, s, ep, en, acc);
+        head_row_ln_bwd<LPR, MAXC, COL>(l, d.D, invD, n.eps, b, ep, en, x, gam, ag, ab, dy, dx);
         if (act) {
 #pragma unroll
             for (int i = 0; i < MAXC; ++i) {
-                const int c = l + LPR * i;
-                if (c < d.D) n.dx[(size_t)m * n.lddx + c] = cr_ln_bwd_tail(dy[i] * gam[i], c1, x[i], c2, rstd);
+                const int c = COL::col(l, i);
+                if (c < d.D && d.d_seq_emb) d.d_seq_emb[(size_t)m * d.ldd + c] = dy[i];
+                if (c < d.D) n.dx[(size_t)m * n.lddx + c] = dx[i];
             }
         }
-        if (d.table_grad) {
-            if (LPR == 16) {
-                // contiguous 4*D-byte float-atomic burst per table row (lane = column), as in k_head
-#pragma unroll
-                for (int rr = 0; rr < RPW; ++rr) {
-                    const int mr = mb + rr;
-                    const float gpr = __shfl(dpl, rr * LPR, 64), gnr = __shfl(dnl, rr * LPR, 64);
-                    const int pr = __shfl(p, rr * LPR, 64), nr = __shfl(ng, rr * LPR, 64);
-                    if (mr < m1 && pr != 0 && lane < d.D) {
-                        const float sv = d.seq_emb[(size_t)mr * d.ld + lane];
-                        atomicAdd(d.table_grad + (size_t)pr * d.D + lane, gpr * sv);
-                        if (nr != 0) atomicAdd(d.table_grad + (size_t)nr * d.D + lane, gnr * sv);
-                    }
-                }
-            } else if (act && ist != 0.0f) {
-#pragma unroll
-                for (int i = 0; i < MAXC; ++i) {
-                    const int c = l + LPR * i;
-                    if (c < d.D) {
-                        if (p != 0) atomicAdd(d.table_grad + (size_t)p * d.D + c, dpl * s[i]);
-                        if (ng != 0) atomicAdd(d.table_grad + (size_t)ng * d.D + c, dnl * s[i]);
-                    }
-                }
-            }
-        }
+        if (d.table_grad) head_scatter<LPR>(d, lane, l, mb, m1, act, p, ng, b, s);
     }
-    if (l == 0) { red[0][wave * RPW + sub] = loss_acc; red[1][wave * RPW + sub] = auc_acc; red[2][wave * RPW + sub] = n_acc; }
-    // dgamma / dbeta: row groups of the wave by shuffles, then the 16 waves in a fixed order (cr_layernorm.hip)
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float v = 0.0f;
-        for (int i = 0; i < 16 * RPW; ++i) v += red[threadIdx.x][i];
-        if (v != 0.0f) atomicAdd(d.state + threadIdx.x, v);
-    }
-#pragma unroll
-    for (int i = 0; i < MAXC; ++i) {
-#pragma unroll
-        for (int o = LPR; o < 64; o <<= 1) {
-            ag[i] += __shfl_xor(ag[i], o, 64);
-            ab[i] += __shfl_xor(ab[i], o, 64);
-        }
-    }
-    if (LPR == 16) {                                     // per-wave slots + one barrier, as in cr_layernorm.hip
-        __shared__ float wg[16][64], wb[16][64];
-        if (sub == 0) {
-#pragma unroll
-            for (int i = 0; i < MAXC; ++i) {
-                const int c = l + LPR * i;
-                if (c < 64) { wg[wave][c] = ag[i]; wb[wave][c] = ab[i]; }
-            }
-        }
-        __syncthreads();
-        if ((int)threadIdx.x < d.D) {
-            float g = 0.0f, b = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 16; ++w) { g += wg[w][threadIdx.x]; b += wb[w][threadIdx.x]; }
-            n.dgamma[(size_t)blockIdx.x * n.slab_stride + threadIdx.x] = g;
-            n.dbeta[(size_t)blockIdx.x * n.slab_stride + threadIdx.x] = b;
-        }
-    } else {
-        __shared__ float wide[16][512];
-#pragma unroll
-        for (int pass = 0; pass < 2; ++pass) {
-            if (sub == 0) {
-#pragma unroll
-                for (int i = 0; i < MAXC; ++i) {
-                    const int c = l + LPR * i;
-                    if (c < 512) wide[wave][c] = pass == 0 ? ag[i] : ab[i];
-                }
-            }
-            __syncthreads();
-            float* dst = pass == 0 ? n.dgamma : n.dbeta;
-            for (int c = threadIdx.x; c < d.D; c += 1024) {
-                float v = 0.0f;
-#pragma unroll
-                for (int w = 0; w < 16; ++w) v += wide[w][c];
-                dst[(size_t)blockIdx.x * n.slab_stride + c] = v;
-            }
-            __syncthreads();
-        }
-    }
+    head_sums_fold<16 * RPW>(d.state, acc, l, wave * RPW + sub);
+    head_slab_fold<LPR, MAXC, COL>(n, d.D, wave, sub, l, ag, ab);
     head_snapshot(d.state, gridDim.x);
 }
 
@@ -320,6 +290,7 @@ __global__ __launch_bounds__(1024) void k_head_ln(cr_head_desc d, cr_ln_bwd_desc
 // LPR-strided dwords (four load instructions per array and row group) and starts each iteration's loads behind the previous one's
 // stores: 14.3 us at the headline shape (two dependent iterations per wave), 81 us for one C5 step's 131 072 table rows (0.52 of the
 // HBM roof over all its bytes).  This kernel is bound by load ISSUE and dependent round trips, so both changes go straight to time.
+// Nothing scatters from it (the occurrence-index form: no table_grad).
 typedef float hd_f4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef float hd_f2 __attribute__((ext_vector_type(2), aligned(4)));
 template <int VEC> struct HdVec { float v[VEC]; };
@@ -346,8 +317,7 @@ __device__ __forceinline__ void hd_store(float* p, const float (&v)[VEC]) {
 template <int LPR, int VEC>
 __global__ __launch_bounds__(1024) void k_head_ln_v(cr_head_desc d, cr_ln_bwd_desc n) {
     constexpr int RPW = 64 / LPR;
-    __shared__ float red[3][16 * RPW];
-    __shared__ float wg[16][LPR * VEC], wb[16][LPR * VEC];
+    using COL = HeadColPacked<VEC>;
     cr_kernarg_touch<sizeof(cr_head_desc) + sizeof(cr_ln_bwd_desc)>();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sub = lane / LPR, l = lane % LPR;
@@ -355,12 +325,13 @@ __global__ __launch_bounds__(1024) void k_head_ln_v(cr_head_desc d, cr_ln_bwd_de
     const bool cok = c0 < d.D;
     const int rps = (d.M + gridDim.x - 1) / gridDim.x;
     const int m0 = blockIdx.x * rps, m1 = min(d.M, m0 + rps);
+    const int mz = min(m0, d.M - 1);                      // the row a lane group without a row reads (a workgroup may own none)
     constexpr int STEP = 16 * RPW;                        // rows per iteration of the workgroup
     float gam[VEC], ag[VEC], ab[VEC];
 #pragma unroll
     for (int u = 0; u < VEC; ++u) { gam[u] = (c0 + u < d.D) ? n.gamma[c0 + u] : 0.0f; ag[u] = 0.0f; ab[u] = 0.0f; }
     const float invD = 1.0f / (float)d.D;
-    float loss_acc = 0.0f, auc_acc = 0.0f, n_acc = 0.0f;
+    HeadSums acc = {0.0f, 0.0f, 0.0f};
     // pipeline: ids of iterations 0 and 1, rows of iteration 0
     const int mfirst = m0 + wave * RPW + sub;
     int p_a = 0, ng_a = 0, p_b = 0, ng_b = 0;             // ids of this iteration / the next one
@@ -368,8 +339,7 @@ __global__ __launch_bounds__(1024) void k_head_ln_v(cr_head_desc d, cr_ln_bwd_de
     if (mfirst + STEP < m1) { p_b = d.pos[mfirst + STEP]; ng_b = d.neg[mfirst + STEP]; }
     HdVec<VEC> s_n, x_n, ep_n, en_n;
     {
-        const bool act = mfirst < m1;
-        const int mm = act ? mfirst : m0;
+        const int mm = mfirst < m1 ? mfirst : mz;
         s_n = hd_load<VEC>(d.seq_emb + (size_t)mm * d.ld + c0, cok);
         x_n = hd_load<VEC>(n.x + (size_t)mm * n.ldx + c0, cok);
         ep_n = hd_load<VEC>(d.table + (size_t)p_a * d.D + c0, cok && p_a != 0);      // row 0 == zeros (modules.py:154-156)
@@ -394,88 +364,33 @@ __global__ __launch_bounds__(1024) void k_head_ln_v(cr_head_desc d, cr_ln_bwd_de
             p_b = 0; ng_b = 0;
             if (mn + STEP < m1) { p_b = d.pos[mn + STEP]; ng_b = d.neg[mn + STEP]; }
         }
-        float pl = 0.0f, nl = 0.0f, xs = 0.0f;
-#pragma unroll
-        for (int u = 0; u < VEC; ++u) { pl += ep.v[u] * s.v[u]; nl += en.v[u] * s.v[u]; xs += xv.v[u]; }
-        pl = head_row_sum<LPR>(pl);                                            // sasrec.py:100
-        nl = head_row_sum<LPR>(nl);                                            // sasrec.py:101
-        const float ist = (p != 0) ? 1.0f : 0.0f;                              // sasrec.py:104
-        const float sp = 1.0f / (1.0f + expf(-pl)), sn = 1.0f / (1.0f + expf(-nl));
-        if (l == 0 && act) {
-            loss_acc += ist * (-logf(sp + 1e-24f) - logf(1.0f - sn + 1e-24f)); // sasrec.py:105-108
-            const float dlt = pl - nl;
-            const float sgn = (dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? -1.0f : 0.0f);
-            auc_acc += ist * (sgn + 1.0f) * 0.5f;                              // sasrec.py:113-115
-            n_acc += ist;
-            if (d.pos_logits) d.pos_logits[m] = pl;
-            if (d.neg_logits) d.neg_logits[m] = nl;
-        }
-        const float dpl = act ? -ist * sp * (1.0f - sp) / (sp + 1e-24f) : 0.0f;
-        const float dnl = act ? ist * sn * (1.0f - sn) / (1.0f - sn + 1e-24f) : 0.0f;
-        if (d.coef_out && l == 0 && act) {
-            d.coef_out[m] = dpl;
-            d.coef_out[(size_t)d.M + m] = dnl;
-        }
-        // ---- LayerNorm backward of this row (modules.py:74-78), dy in registers
-        const float mean = head_row_sum<LPR>(xs) * invD;
-        float v = 0.0f, xh[VEC];
-#pragma unroll
-        for (int u = 0; u < VEC; ++u) {
-            const float dxm = (c0 + u < d.D) ? (xv.v[u] - mean) : 0.0f;
-            xh[u] = dxm;
-            v += dxm * dxm;
-        }
-        const float rstd = 1.0f / sqrtf(head_row_sum<LPR>(v) * invD + n.eps);
-        float dy[VEC], c1 = 0.0f, c2 = 0.0f;
-#pragma unroll
-        for (int u = 0; u < VEC; ++u) {
-            dy[u] = dpl * ep.v[u] + dnl * en.v[u];
-            xh[u] *= rstd;
-            const float dg = dy[u] * gam[u];
-            c1 += dg;
-            c2 += dg * xh[u];
-            ag[u] += dy[u] * xh[u];
-            ab[u] += dy[u];
-        }
+        float dy[VEC], dx[VEC];
+        const HeadBce b = head_row_bce<LPR>(d, l, m, act, act, p, s.v, ep.v, en.v, acc);
+        head_row_ln_bwd<LPR, VEC, COL>(l, d.D, invD, n.eps, b, ep.v, en.v, xv.v, gam, ag, ab, dy, dx);
         if (act && cok && d.d_seq_emb) hd_store<VEC>(d.d_seq_emb + (size_t)m * d.ldd + c0, dy);
-        c1 = head_row_sum<LPR>(c1) * invD;
-        c2 = head_row_sum<LPR>(c2) * invD;
-        if (act && cok) {
-            float o[VEC];
-#pragma unroll
-            for (int u = 0; u < VEC; ++u) o[u] = cr_ln_bwd_tail(dy[u] * gam[u], c1, xh[u], c2, rstd);
-            hd_store<VEC>(n.dx + (size_t)m * n.lddx + c0, o);
-        }
+        if (act && cok) hd_store<VEC>(n.dx + (size_t)m * n.lddx + c0, dx);
     }
-    if (l == 0) { red[0][wave * RPW + sub] = loss_acc; red[1][wave * RPW + sub] = auc_acc; red[2][wave * RPW + sub] = n_acc; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        float v = 0.0f;
-        for (int i = 0; i < 16 * RPW; ++i) v += red[threadIdx.x][i];
-        if (v != 0.0f) atomicAdd(d.state + threadIdx.x, v);
-    }
-    // dgamma / dbeta: the wave's row groups by shuffles, then the 16 waves in a fixed order
-#pragma unroll
-    for (int u = 0; u < VEC; ++u) {
-#pragma unroll
-        for (int o = LPR; o < 64; o <<= 1) {
-            ag[u] += __shfl_xor(ag[u], o, 64);
-            ab[u] += __shfl_xor(ab[u], o, 64);
-        }
-    }
-    if (sub == 0) {
-#pragma unroll
-        for (int u = 0; u < VEC; ++u) { wg[wave][c0 + u] = ag[u]; wb[wave][c0 + u] = ab[u]; }
-    }
-    __syncthreads();
-    for (int c = threadIdx.x; c < d.D; c += 1024) {
-        float g = 0.0f, b = 0.0f;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) { g += wg[w][c]; b += wb[w][c]; }
-        n.dgamma[(size_t)blockIdx.x * n.slab_stride + c] = g;
-        n.dbeta[(size_t)blockIdx.x * n.slab_stride + c] = b;
-    }
+    head_sums_fold<16 * RPW>(d.state, acc, l, wave * RPW + sub);
+    head_slab_fold<LPR, VEC, COL>(n, d.D, wave, sub, l, ag, ab);
     head_snapshot(d.state, gridDim.x);
+}
+
+// Which kernel takes a cr_head_fwd_bwd_ln call: the vector or the strided form, lanes per row, elements per lane (VEC / MAXC)
+struct HeadLnForm { bool vec; int lpr, n; };
+static HeadLnForm head_ln_form(const cr_head_desc* d, const cr_ln_bwd_desc* n) {
+    static const bool no_vec = getenv("CASTREC_HEAD_NO_VEC") != nullptr;
+    const int D = d->D, pitch = d->ld | n->ldx | n->lddx | (d->d_seq_emb ? d->ldd : 0);     // (low bits: every pitch even / a multiple of 4)
+    // vector row accesses where the shape allows them, and nothing scatters from this kernel (the occurrence-index form)
+    // (D = 50: 32 lanes x 8 bytes halve the rows a wave holds per iteration -- four dependent iterations instead of two at the headline
+    //  shape: 17.6 against 16.5 us; 16-byte lanes keep four rows per wave up to 64 columns, and above 64 the scalar form's strided dwords
+    //  lose outright: 82.2 -> 65.1 us for one C5 step's rows, 0.51 -> 0.65 of the HBM roof, bench.py gather.head_ln)
+    if (!no_vec && !d->table_grad && pitch % 2 == 0 && D % 2 == 0 && D <= 256 && (D % 4 == 0 || D > 64)) {
+        if (D % 4 == 0 && pitch % 4 == 0) return {true, D <= 64 ? 16 : D <= 128 ? 32 : 64, 4};
+        if (D <= 128) return {true, D <= 32 ? 16 : D <= 64 ? 32 : 64, 2};
+    }
+    // lanes per row: 16 (D <= 64), 32 (D <= 128: two rows per wave and DPP row sums -- with a whole wave per row the eight rows
+    // of a wave at config C4 were eight serial gather -> reduce -> atomics passes: 36 us), else 64
+    return {false, D <= 64 ? 16 : D <= 128 ? 32 : 64, D <= 128 ? 4 : 8};
 }
 
 extern "C" int cr_head_fwd_bwd_ln(const cr_head_desc* d, const cr_ln_bwd_desc* n, void* stream) {
@@ -486,34 +401,13 @@ extern "C" int cr_head_fwd_bwd_ln(const cr_head_desc* d, const cr_ln_bwd_desc* n
                "cr_head_fwd_bwd_ln: the LayerNorm description must match the head's rows");
     CR_REQUIRE(!n->accumulate, "cr_head_fwd_bwd_ln: accumulate is not supported");
     if (d->D > 512) return cr_set_error(CR_ERR_UNSUPPORTED, "cr_head_fwd_bwd_ln: D=%d > 512", d->D);
-    // lanes per row: 16 (D <= 64), 32 (D <= 128: two rows per wave and DPP row sums -- with a whole wave per row the eight rows
-    // of a wave at config C4 were eight serial gather -> reduce -> atomics passes: 36 us), else 64
-    // vector row accesses where the shape allows them, and nothing scatters from this kernel (the occurrence-index form)
-    static const bool no_vec = getenv("CASTREC_HEAD_NO_VEC") != nullptr;
-    const bool al = ((d->ld | n->ldx | n->lddx | (d->d_seq_emb ? d->ldd : 0)) % 2) == 0;
-    // (D = 50: 32 lanes x 8 bytes halve the rows a wave holds per iteration -- four dependent iterations instead of two at the headline
-    //  shape: 17.6 against 16.5 us; 16-byte lanes keep four rows per wave up to 64 columns, and above 64 the scalar form's strided dwords
-    //  lose outright: 82.2 -> 65.1 us for one C5 step's rows, 0.51 -> 0.65 of the HBM roof, bench.py gather.head_ln)
-    if (!no_vec && !d->table_grad && al && d->D % 2 == 0 && d->D <= 256 && (d->D % 4 == 0 || d->D > 64)) {
-        const bool v4 = d->D % 4 == 0 && ((d->ld | n->ldx | n->lddx | (d->d_seq_emb ? d->ldd : 0)) % 4) == 0;
-#define HD_LAUNCH(L, V) hipLaunchKernelGGL((k_head_ln_v<L, V>), dim3(n->n_slabs), dim3(1024), 0, cr_stream(stream), *d, *n)
-        if (v4 && d->D <= 64) HD_LAUNCH(16, 4);
-        else if (v4 && d->D <= 128) HD_LAUNCH(32, 4);
-        else if (v4) HD_LAUNCH(64, 4);
-        else if (d->D <= 32) HD_LAUNCH(16, 2);
-        else if (d->D <= 64) HD_LAUNCH(32, 2);
-        else if (d->D <= 128) HD_LAUNCH(64, 2);
-        else goto scalar_form;
-#undef HD_LAUNCH
-        return cr_check_launch("cr_head_fwd_bwd_ln");
-    }
-scalar_form:
-    if (d->D <= 64)
-        hipLaunchKernelGGL((k_head_ln<16, 4>), dim3(n->n_slabs), dim3(1024), 0, cr_stream(stream), *d, *n);
-    else if (d->D <= 128)
-        hipLaunchKernelGGL((k_head_ln<32, 4>), dim3(n->n_slabs), dim3(1024), 0, cr_stream(stream), *d, *n);
-    else
-        hipLaunchKernelGGL((k_head_ln<64, 8>), dim3(n->n_slabs), dim3(1024), 0, cr_stream(stream), *d, *n);
+    const HeadLnForm f = head_ln_form(d, n);
+#define HD_CASE(VEC, K, L, N) \
+    if (f.vec == VEC && f.lpr == L && f.n == N) hipLaunchKernelGGL((K<L, N>), dim3(n->n_slabs), dim3(1024), 0, cr_stream(stream), *d, *n)
+    HD_CASE(true, k_head_ln_v, 16, 4); HD_CASE(true, k_head_ln_v, 32, 4); HD_CASE(true, k_head_ln_v, 64, 4);
+    HD_CASE(true, k_head_ln_v, 16, 2); HD_CASE(true, k_head_ln_v, 32, 2); HD_CASE(true, k_head_ln_v, 64, 2);
+    HD_CASE(false, k_head_ln, 16, 4); HD_CASE(false, k_head_ln, 32, 4); HD_CASE(false, k_head_ln, 64, 8);
+#undef HD_CASE
     return cr_check_launch("cr_head_fwd_bwd_ln");
 }
 

@@ -23,6 +23,7 @@
 
 #include "cr_attn_common.hpp"
 #include "cr_bf16.hpp"
+#include "cr_head.hpp"
 
 #define ST_WAVES 8
 #define ST_THREADS (64 * ST_WAVES)
@@ -513,7 +514,7 @@ __global__ __launch_bounds__(64 * NW) void k_stack_fwd(StackArgs a) {
             }
             if (HEAD && last) {
                 const StackArgs& ah = stack_args_again();
-                // ---- prediction head on the rows in registers (sasrec.py:87-115; cr_head.hip k_head_ln, same arithmetic) ----
+                // ---- prediction head on the rows in registers (sasrec.py:87-115; cr_head.hip k_head_ln's arithmetic: cr_head.hpp) ----
                 f32x4 ep[4], en[4], pr[4];
                 r_finish(ep, hrp, dcx);
                 r_finish(en, hrn, dcx);
@@ -524,22 +525,11 @@ __global__ __launch_bounds__(64 * NW) void k_stack_fwd(StackArgs a) {
                 for (int ct = 0; ct < 4; ++ct) pr[ct] = en[ct] * fin[ct];
                 const float nl = r_rowsum(pr);                                             // sasrec.py:101
                 const float ist = (rok && hpid != 0) ? 1.0f : 0.0f;                        // sasrec.py:104
-                const float sp = 1.0f / (1.0f + expf(-pl)), sn = 1.0f / (1.0f + expf(-nl));
-                const float dpl = -ist * sp * (1.0f - sp) / (sp + 1e-24f);
-                const float dnl = ist * sn * (1.0f - sn) / (1.0f - sn + 1e-24f);
-                float h_loss = 0.0f, h_auc = 0.0f, h_n = 0.0f;
-                if (lg == 0 && rok) {
-                    h_loss = ist * (-logf(sp + 1e-24f) - logf(1.0f - sn + 1e-24f));        // sasrec.py:105-108
-                    const float dlt = pl - nl;
-                    const float sgn = (dlt > 0.0f) ? 1.0f : ((dlt < 0.0f) ? -1.0f : 0.0f);
-                    h_auc = ist * (sgn + 1.0f) * 0.5f;                                     // sasrec.py:113-115
-                    h_n = ist;
-                    if (ah.hd.pos_logits) ah.hd.pos_logits[m] = pl;
-                    if (ah.hd.neg_logits) ah.hd.neg_logits[m] = nl;
-                    if (ah.hd.coef_out) { ah.hd.coef_out[m] = dpl; ah.hd.coef_out[(size_t)ah.hd.M + m] = dnl; }
-                }
+                const HeadBce hb = head_bce(pl, nl, ist);                                  // the BCE row: cr_head.hpp
+                HeadSums hs = {0.0f, 0.0f, 0.0f};
+                if (lg == 0 && rok) hs = head_bce_first_lane(ah.hd, m, pl, nl, ist, hb);   // sasrec.py:105-115, and the per-row outputs
                 {                                         // the wave's three sums (one tile per wave: written, not added to)
-                    const float wl = wave_sum(h_loss), wa = wave_sum(h_auc), wn = wave_sum(h_n);
+                    const float wl = wave_sum(hs.loss), wa = wave_sum(hs.auc), wn = wave_sum(hs.n);
                     float* red = hpart + 2 * NW * 64;
                     if (ln == 0) { red[wave] = wl; red[NW + wave] = wa; red[2 * NW + wave] = wn; }
                 }
@@ -549,7 +539,7 @@ __global__ __launch_bounds__(64 * NW) void k_stack_fwd(StackArgs a) {
 #pragma unroll
                 for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dyh[ct][r] = fmaf(dpl, ep[ct][r], dnl * en[ct][r]);     // (element by element: the vector form is a packed multiply + in-place packed fma, the chain build.py's ISA scan refuses)
+                    for (int r = 0; r < 4; ++r) dyh[ct][r] = head_dy(hb, ep[ct][r], en[ct][r]);          // (element by element: see head_dy)
                 if (ah.hd.d_seq_emb) r_store(ah.hd.d_seq_emb, (u32)m * (u32)(4 * ah.hd.ldd), dyh, rok, dcx);
                 f32x4 hag[4], hab[4];
 #pragma unroll

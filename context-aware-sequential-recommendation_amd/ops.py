@@ -115,10 +115,19 @@ def attn_bwd(fdesc, dout, lddo, dQ, dK, dV, ldg, stats, delta=None, dQ_part=None
 
 
 def head_fwd_bwd(seq_emb, ld, table, pos, neg, M, D, state, d_seq_emb=None, ldd=0, table_grad=None,
-                 pos_logits=None, neg_logits=None):
+                 pos_logits=None, neg_logits=None, coef_out=None):
     d = L.HeadDesc(_p(seq_emb), ld, _p(table), _p(pos), _p(neg), M, D, table.shape[0], _p(state), _p(d_seq_emb), ldd,
-                   _p(table_grad), _p(pos_logits), _p(neg_logits))
+                   _p(table_grad), _p(pos_logits), _p(neg_logits), _p(coef_out))
     L.call("cr_head_fwd_bwd", C.byref(d), _stream())
+
+
+def head_fwd_bwd_ln(seq_emb, ld, table, pos, neg, M, D, state, x, ldx, gamma, dx, lddx, dgamma, dbeta, slab_stride, n_slabs,
+                    d_seq_emb=None, ldd=0, table_grad=None, pos_logits=None, neg_logits=None, coef_out=None, eps=1e-8):
+    """cr_head_fwd_bwd with the backward of the LayerNorm that made seq_emb from x (the layernorm_bwd call that would have followed)."""
+    d = L.HeadDesc(_p(seq_emb), ld, _p(table), _p(pos), _p(neg), M, D, table.shape[0], _p(state), _p(d_seq_emb), ldd,
+                   _p(table_grad), _p(pos_logits), _p(neg_logits), _p(coef_out))
+    n = L.LnBwdDesc(_p(x), ldx, _p(gamma), None, 0, _p(dx), lddx, 0, _p(dgamma), _p(dbeta), slab_stride, n_slabs, M, D, eps)
+    L.call("cr_head_fwd_bwd_ln", C.byref(d), C.byref(n), _stream())
 
 
 def test_logits(seq_emb, ld, table, cand, B, T, D, logits):
