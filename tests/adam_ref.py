@@ -33,6 +33,7 @@ import types
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
+import torch
 
 U = 2.0 ** -24
 R = 2e-4
@@ -107,7 +108,6 @@ def tg_gradient(tg):
     """(fp64 [(V + T_pos) * D] gradient, bool [V + T_pos]: the row has a unit)"""
     if "_grad" in tg:                                     # (computed once per batch: the cases of a batch share it, unchanged)
         return tg["_grad"]
-    from test_index import _table_grad_reference
     g = _table_grad_reference(tg["V"], tg["T_pos"], tg["D"], tg["seq"], tg["pos"], tg["neg"], tg["rows"], tg["rows2"], tg["scale"],
                               tg["emb"], tg["coef"])
     listed = np.zeros(tg["V"] + tg["T_pos"], bool)
@@ -280,3 +280,41 @@ def ring_copy_reference(c, dst0):
     k = c.ring.copy_elems if c.ring.copy_elems else c.ring.slot_elems
     out[:k] = c.ring.data[(c.t + 1) % c.ring.slots, :k]
     return out
+
+
+def _table_grad_reference(V, T_pos, D, seq, pos, neg, rows, rows2, scale, emb, coef):
+    """fp64: what float atomics summed in rounds 1-4"""
+    M = len(seq)
+    g = np.zeros((V + T_pos, D))
+    r = rows.astype(np.float64) + (rows2.astype(np.float64) if rows2 is not None else 0.0)
+    np.add.at(g, seq, scale * r)
+    np.add.at(g, pos, coef[0][:, None].astype(np.float64) * emb)
+    np.add.at(g, neg, coef[1][:, None].astype(np.float64) * emb)
+    g[0] = 0.0
+    if T_pos:
+        g[V:] = r.reshape(M // T_pos, T_pos, D).sum(0)
+    return g
+
+
+# ---- device buffers of the GPU tests -------------------------------------------------------------------------------------------------
+GUARD = 64          # elements on either side of a buffer (256 bytes: the buffer itself keeps the allocation's alignment)
+
+
+class Buf:
+    """A device array between two guards; shift: elements the array starts behind the aligned position."""
+
+    def __init__(self, a, fill, shift=0):
+        a = np.ascontiguousarray(a)
+        self.lo, self.n = GUARD + shift, a.size
+        self.host = np.full(a.size + 2 * GUARD + shift, fill, a.dtype)
+        self.host[self.lo:self.lo + self.n] = a.reshape(-1)
+        self.dev = torch.from_numpy(self.host).cuda()
+        self.view = self.dev[self.lo:self.lo + self.n]
+
+    def back(self):
+        """the array after the launch; the guards must hold the bits they were given"""
+        got = self.dev.cpu().numpy()
+        bits = np.int32 if got.itemsize == 4 else np.int64
+        assert np.array_equal(got[:self.lo].view(bits), self.host[:self.lo].view(bits)), "guard in front overwritten"
+        assert np.array_equal(got[self.lo + self.n:].view(bits), self.host[self.lo + self.n:].view(bits)), "guard behind overwritten"
+        return got[self.lo:self.lo + self.n]

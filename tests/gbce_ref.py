@@ -6,25 +6,20 @@ The bounds are built from fp64 quantities only.  A score carries es = u * sum_i 
   loss of a row:  beta et + sum_{live j} sigma_j es_j + 2^-20 (1 + |l|) + n_live 2^-24 l
   coefficient:    es / 4 (a negative), beta et / 4 (the target)
 and |E| / |h| carry the coefficients' bounds into dh / dE, plus 2^-14 (2^-7 plain) of sum |g| |E| and sum |g| |h| for the accumulation
-and the bf16 split of g, as test_sce_gpu._ref64.  The last loss term is the textbook bound of an fp32 sum of n_live + 1 non-negative
+and the bf16 split of g, as loss_ref.sampled_softmax_ref64.  The last loss term is the textbook bound of an fp32 sum of n_live + 1 non-negative
 terms in any order, (n - 1) 2^-24 sum |x|.  Small-e treatment: softplus(x) = max(x, 0) + log(1 + e) with e = exp(-|x|) loses e whole
 once e < 2^-24 if evaluated as written (N such terms lose N e, all of the loss of a row of very negative scores); the device and the
 emulation take the series e - e^2 / 2 below e = 2^-12 (truncation < 2^-25 e), so the bound carries no term for it: 2^-20 (1 + |l|)
 covers the few-ulp evaluation error of every term (2^-24 absolute from 1 + e above the threshold, against terms >= 2^-12.5)."""
 import numpy as np
 
-from dropout_ref import M32, fmix32, site_key
-
-CR_GBCE_SITE = 0x6BCE0000
-CR_PHI = 0x9E3779B1
+import loss_ref
+from loss_ref import GBCE_SITE as CR_GBCE_SITE
 
 
 def draw(seed, step, V, N):
-    """key = cr_site_key(seed, step, CR_GBCE_SITE); x_j = cr_fmix32(key + j * CR_PHI); s_j = 1 + ((x_j * (V - 1)) >> 32)."""
-    key = site_key(np.uint64(seed & 0xFFFFFFFF), np.uint64(step & 0xFFFFFFFF), np.uint64(CR_GBCE_SITE))
-    j = np.arange(N, dtype=np.uint64)
-    x = fmix32((key + j * np.uint64(CR_PHI)) & M32)
-    return (1 + ((x * np.uint64(V - 1)) >> np.uint64(32))).astype(np.int32)
+    """loss_ref.draw at cr_gbce's site."""
+    return loss_ref.draw(seed, step, V, N, CR_GBCE_SITE)
 
 
 def beta(N, itemnum, t):
@@ -74,19 +69,6 @@ def ref64(h, E_, pos, neg, s, b, bf16=False):
     sn = np.where(neg > 0, (h * Ed[neg]).sum(1), 0.0)
     return dict(l=l, e_l=e_l, dh=dh, e_dh=e_dh, dE=dE, e_dE=e_dE, loss=float(l.sum()), e_loss=float(e_l.sum()), n=float(ist.sum()),
                 sp=St, sn=sn, ist=ist, live=live)
-
-
-def check(got, ref, scale):
-    """Every element of loss_out, d_seq_emb and table_grad within scale x its bound; the state's loss sum and target count."""
-    r = np.abs(got["l"] - ref["l"]) / (scale * ref["e_l"] + 1e-30)
-    assert np.all(r <= 1.0), ("loss_out", float(r.max()), int(np.argmax(r)))
-    r = np.abs(got["dh"] - ref["dh"]) / (scale * ref["e_dh"] + 1e-30)
-    assert np.all(r <= 1.0), ("dh", float(r.max()), np.unravel_index(np.argmax(r), r.shape))
-    r = np.abs(got["tg"] - ref["dE"]) / (scale * ref["e_dE"] + 1e-30)
-    assert np.all(r <= 1.0), ("dE", float(r.max()), np.unravel_index(np.argmax(r), r.shape))
-    assert abs(got["state"][0] - ref["loss"]) <= scale * ref["e_loss"] + 1e-6 * abs(ref["loss"]) + 1e-5, (got["state"][0], ref["loss"])
-    assert got["state"][2] == ref["n"]
-    return float(r.max())
 
 
 # ---- the device arithmetic in numpy ----------------------------------------------------------------------------------------------
@@ -171,7 +153,7 @@ def planted_reference(steps, log=(), seed=3):
     ({step: loss}, full-ranking HR@10 of the next item after each test sequence's last one), as the GPU test measures them."""
     import torch
     from oracle import fpmodel as fm
-    from test_ce_gpu import _planted
+    from loss_ref import planted as _planted
     c = PLANTED
     B, T, D, itemnum, N = c["B"], c["T"], c["D"], c["itemnum"], c["N"]
     rs = np.random.RandomState(0)

@@ -1,17 +1,12 @@
 """Reference side of the popularity proposal of cr_sampled_ce (castrec.h): independent numpy restatements of the host builder and of the
-device draw, the fp64 results of the corrected objective with per-element bounds, and the skewed planted corpus in fp64.
-
-The bounds are test_sce_gpu._ref64's, built from fp64 quantities only, on the corrected logits z' = z - log Q.  A score carries
-es = u * sum_i |h_mi E_vi| (u = 2^-15 for the three bf16 products, 2^-7 for plain bf16) and, for the one fp32 add of the correction,
-2^-23 (|z| + |log Q|) more."""
+device draw, and the skewed planted corpus in fp64.  (The fp64 results of the corrected objective with their per-element bounds:
+loss_ref.sampled_softmax_ref64 with logq.)"""
 import math
 
 import numpy as np
 
-from dropout_ref import M32, fmix32, site_key
-
-CR_SCE_SITE = 0x5CE00000
-CR_PHI = 0x9E3779B1
+import loss_ref
+from loss_ref import SCE_SITE as CR_SCE_SITE
 
 
 def build(w):
@@ -39,9 +34,7 @@ def masses(cdf):
 
 
 def hashes(seed, step, N):
-    key = site_key(np.uint64(seed & 0xFFFFFFFF), np.uint64(step & 0xFFFFFFFF), np.uint64(CR_SCE_SITE))
-    j = np.arange(N, dtype=np.uint64)
-    return fmix32((key + j * np.uint64(CR_PHI)) & M32)
+    return loss_ref.hashes(seed, step, N, CR_SCE_SITE)
 
 
 def draw(seed, step, cdf, N):
@@ -49,50 +42,6 @@ def draw(seed, step, cdf, N):
     V = len(cdf)
     x = hashes(seed, step, N)
     return (np.searchsorted(np.asarray(cdf, np.uint64)[1:V - 1], x, side="right") + 1).astype(np.int32)
-
-
-def ref64(h, E_, pos, neg, s, logq, bf16=False):
-    """test_sce_gpu._ref64 on the corrected logits: fp64 results and per-element bounds."""
-    u = 2.0 ** -7 if bf16 else 2.0 ** -15
-    acc = 2.0 ** -7 if bf16 else 2.0 ** -14
-    h = h.astype(np.float64)
-    Ed = E_.astype(np.float64)
-    lq = np.asarray(logq, np.float64)
-    Es = Ed[s]                                           # [N, D]
-    Et = Ed[pos]                                         # [M, D] (row 0 for padded rows)
-    S0 = h @ Es.T
-    St0 = (h * Et).sum(1)
-    S = S0 - lq[s][None, :]                              # the corrected logits
-    St = St0 - lq[pos]
-    es = u * (np.abs(h) @ np.abs(Es).T) + 2.0 ** -23 * (np.abs(S0) + np.abs(lq[s])[None, :])
-    et = u * (np.abs(h) * np.abs(Et)).sum(1) + 2.0 ** -23 * (np.abs(St0) + np.abs(lq[pos]))
-    hit = s[None, :] == pos[:, None]
-    mx = np.maximum(np.where(hit, -np.inf, S).max(1), St)
-    Z = np.where(hit, 0.0, np.exp(S - mx[:, None]))
-    zt = np.exp(St - mx)
-    tot = Z.sum(1) + zt
-    lse = mx + np.log(tot)
-    P = Z / tot[:, None]
-    pt = zt / tot
-    ist = pos != 0
-    e_lse = (P * es).sum(1) + pt * et + 2.0 ** -20 * (1.0 + np.abs(lse))
-    Pm = P * ist[:, None]
-    gt = np.where(ist, pt - 1.0, 0.0)
-    dh = Pm @ Es + gt[:, None] * Et
-    dE = np.zeros_like(Ed)
-    np.add.at(dE, s, Pm.T @ h)
-    np.add.at(dE, pos[ist], gt[ist, None] * h[ist])
-    W = P * (es + e_lse[:, None]) * ist[:, None]
-    wt = np.where(ist, pt * (et + e_lse), 0.0)
-    e_dh = W @ np.abs(Es) + wt[:, None] * np.abs(Et) + acc * (Pm @ np.abs(Es) + np.abs(gt)[:, None] * np.abs(Et))
-    e_dE = np.zeros_like(dE)
-    np.add.at(e_dE, s, W.T @ np.abs(h) + acc * (Pm.T @ np.abs(h)))
-    np.add.at(e_dE, pos[ist], (wt[ist] + acc * np.abs(gt[ist]))[:, None] * np.abs(h[ist]))
-    loss = float((lse - St)[ist].sum())
-    e_loss = float((e_lse + et)[ist].sum())
-    sn = np.where(neg > 0, (h * Ed[neg]).sum(1), 0.0)
-    return dict(lse=lse, e_lse=e_lse, dh=dh, e_dh=e_dh, dE=dE, e_dE=e_dE, loss=loss, e_loss=e_loss, n=float(ist.sum()), sp=St0, sn=sn,
-                ist=ist)
 
 
 def zipf_weights(V, a=1.0):
@@ -108,7 +57,7 @@ PLANTED_LOSS, PLANTED_HR = 0.5 * math.log(65), 0.5
 
 
 def planted_skewed(rs, B, T, itemnum):
-    """test_ce_gpu._planted (item i is followed by item i + 1, left-padded to T) with the start of a sequence drawn as
+    """loss_ref.planted (item i is followed by item i + 1, left-padded to T) with the start of a sequence drawn as
     1 + int((itemnum - n - 1) u^3): low ids are frequent, high ids rare."""
     seq = np.zeros((B, T), np.int64); pos = np.zeros((B, T), np.int64); neg = np.zeros((B, T), np.int64)
     for b in range(B):

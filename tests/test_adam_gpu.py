@@ -26,10 +26,9 @@ import pytest
 import torch
 
 import adam_ref as A
+from adam_ref import Buf
 
 pytestmark = pytest.mark.gpu
-
-GUARD = 64          # elements on either side of a buffer (256 bytes: the buffer itself keeps the allocation's alignment)
 
 
 @pytest.fixture(scope="module")
@@ -38,26 +37,6 @@ def ops():
     from castrec_amd import ops as O
     assert torch.cuda.is_available()
     return O
-
-
-class Buf:
-    """A device array between two guards; shift: elements the array starts behind the aligned position."""
-
-    def __init__(self, a, fill, shift=0):
-        a = np.ascontiguousarray(a)
-        self.lo, self.n = GUARD + shift, a.size
-        self.host = np.full(a.size + 2 * GUARD + shift, fill, a.dtype)
-        self.host[self.lo:self.lo + self.n] = a.reshape(-1)
-        self.dev = torch.from_numpy(self.host).cuda()
-        self.view = self.dev[self.lo:self.lo + self.n]
-
-    def back(self):
-        """the array after the launch; the guards must hold the bits they were given"""
-        got = self.dev.cpu().numpy()
-        bits = np.int32 if got.itemsize == 4 else np.int64
-        assert np.array_equal(got[:self.lo].view(bits), self.host[:self.lo].view(bits)), "guard in front overwritten"
-        assert np.array_equal(got[self.lo + self.n:].view(bits), self.host[self.lo + self.n:].view(bits)), "guard behind overwritten"
-        return got[self.lo:self.lo + self.n]
 
 
 def geometry(D):
@@ -98,7 +77,7 @@ def run(ops, c, tg_ring=False):
     ring = c.ring
     keep = []
     if c.tg is not None:
-        from test_index import build_index
+        from index_harness import build_index
         t = c.tg
         ng, ent = geometry(t["D"])
         lay, ix = build_index(t["M"], t["V"], t["T_pos"], t["seq"], t["pos"], t["neg"], ng=ng, ent=ent)

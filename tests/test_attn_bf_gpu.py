@@ -15,7 +15,7 @@ import torch
 
 import bf16_ref as br
 import dropout_ref as dr
-from test_ops_gpu import attn_core_ref, dev, new_state, relerr
+from ops_harness import attn_core_ref, dev, new_state, relerr
 
 pytestmark = pytest.mark.gpu
 

@@ -2,13 +2,13 @@
 independent comparison under it: each parameter's gradient within (3 E_k + 2e-3) of its OWN largest entry, the forward rows within
 3 E_act + 2e-4, the loss within 3 E_loss + 2e-4, where E is what the oracle's rounding model (tests/bf16_ref.py: the operands of every
 matrix product rounded to bf16) deviates from the exact oracle at that shape, on the engine's gates and dropout masks
-(test_model_gpu._other_shapes).  tests/test_bf16_ref_host.py shows on the CPU that this bound has room for a correct kernel at these
+(model_harness._other_shapes).  tests/test_bf16_ref_host.py shows on the CPU that this bound has room for a correct kernel at these
 shapes and none for one weight-gradient tile off by 20 %.  The shapes are the smallest that reach each path; every case asserts from
 the launch plan that the kernels it names ran.  Measured values: profiles/bf16_envelope.txt (tools/probes/bf16_vs_oracle.py)."""
 import pytest
 
 import bf16_ref as br
-from test_model_gpu import E, _other_shapes  # noqa: F401  (E: the engine module, a fixture)
+from model_harness import E, _other_shapes  # noqa: F401  (E: the engine module, a fixture)
 
 pytestmark = pytest.mark.gpu
 

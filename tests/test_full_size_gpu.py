@@ -14,7 +14,7 @@ import pytest
 import torch
 
 from oracle import fpmodel as fm
-from test_model_gpu import (E, TOL, _other_shapes, engine_relu_gates, oracle_drop, oracle_with_engine_gates, rel,  # noqa: F401
+from model_harness import (E, TOL, _other_shapes, engine_relu_gates, oracle_drop, oracle_with_engine_gates, rel,  # noqa: F401
                             worst_grad_error)
 
 pytestmark = pytest.mark.gpu

@@ -1,11 +1,8 @@
 """gBCE, host side (no GPU): cr_gbce's argument checks and workspace query, the ctypes mirror of cr_gbce_desc, the --loss gbce /
 --gbce_t options, the numpy restatements of the device draw and of beta, and the error bound of the GPU test itself: a numpy
 emulation of the device arithmetic stays within 1x the bounds the GPU gets 4x of (gbce_ref)."""
-import ctypes
+import functools
 import math
-import os
-import shutil
-import subprocess
 import zlib
 
 import numpy as np
@@ -15,56 +12,20 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 
 import gbce_ref
-import sce_ref
-from test_sce_host import _fmix32_by_hand
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import loss_host
+import loss_ref
 
 
-def _valid_desc(M=40, V=100, D=50, N=16):
-    """A descriptor that passes every check but the workspace (fake pointers: nothing is launched on a check failure)."""
-    d = L.GbceDesc()
-    d.seq_emb, d.ld, d.table, d.pos, d.neg = 16, D, 16, 16, 16
-    d.M, d.D, d.V, d.N, d.precision, d.beta, d.state = M, D, V, N, L.PREC_BF16X3, 0.5, 16
-    d.samples, d.seed, d.step = None, 7, 16
-    d.d_seq_emb, d.ldd, d.table_grad = 16, D, 16
-    return d
+def _check(got, ref):
+    return loss_ref.check(got, ref, 1.0, "l")
 
 
-def _rejects(d, *words):
-    rc = L.lib.cr_gbce(ctypes.byref(d) if d is not None else None, None)
-    msg = L.lib.cr_last_error().decode()
-    assert rc == -1, (rc, msg)
-    assert "cr_gbce" in msg
-    for w in words:
-        assert w in msg, msg
-    return msg
+_valid_desc = functools.partial(loss_host.valid_desc, "gbce")
+_rejects = functools.partial(loss_host.rejects, "gbce")
 
 
 def test_gbce_validates_before_any_hip_call():
-    _rejects(None, "NULL descriptor")
-    for f in ("seq_emb", "table", "pos", "state"):
-        d = _valid_desc()
-        setattr(d, f, None)
-        _rejects(d, "NULL")
-    for D in (4, 7, 257):
-        d = _valid_desc(); d.D, d.ld, d.ldd = D, 300, 300
-        _rejects(d, "D=%d" % D)
-    for V in (1, 0, -3):
-        d = _valid_desc(); d.V = V
-        _rejects(d, "V=%d" % V)
-    for M in (0, -1):
-        d = _valid_desc(); d.M = M
-        _rejects(d, "M=%d" % M)
-    for N in (0, -2, L.CR_SCE_MAX_SAMPLES + 1):
-        d = _valid_desc(); d.N = N
-        _rejects(d, "N=%d" % N)
-    d = _valid_desc(); d.ld = 49
-    _rejects(d, "ld=49")
-    d = _valid_desc(); d.ldd = 10
-    _rejects(d, "ldd=10")
-    d = _valid_desc(); d.precision = 7
-    _rejects(d, "precision 7")
+    loss_host.refuses_the_common_arguments("gbce")
     for b in (0.0, -0.5, 1.0 + 2.0 ** -20, 2.0, float("nan"), float("inf")):
         d = _valid_desc(); d.beta = b
         _rejects(d, "beta")
@@ -83,41 +44,13 @@ def test_gbce_validates_before_any_hip_call():
 
 def test_workspace_query_is_monotone_and_rejects_unsupported_shapes():
     ws = L.lib.cr_gbce_workspace
-    assert ws(0, 16, 50) == 0 and ws(-1, 16, 50) == 0 and ws(4, 0, 50) == 0 and ws(4, -1, 50) == 0
-    assert ws(4, L.CR_SCE_MAX_SAMPLES + 1, 50) == 0 and ws(4, 16, 7) == 0 and ws(4, 16, 257) == 0 and ws(4, 16, 4) == 0
-    assert ws(1, 1, 8) > 0 and ws(1, L.CR_SCE_MAX_SAMPLES, 256) > 0
-    Ns = (1, 7, 31, 64, 256, 1000, 1024, 1025, 2048, 4096, 10000, 16384)
-    Ms = (1, 7, 64, 65, 300, 6400, 25600, 65536, 10 ** 6)
-    for D in (8, 20, 50, 64, 128, 256):
-        for N in Ns:
-            prev = 0
-            for M in Ms:
-                n = ws(M, N, D)
-                assert n > 0 and n >= prev, (D, N, M, n, prev)
-                prev = n
-        for M in Ms:
-            prev = 0
-            for N in Ns:
-                n = ws(M, N, D)
-                assert n > 0 and n >= prev, (D, M, N, n, prev)
-                prev = n
-    # independent of V, O(M + N D): the C5 shape needs well under 100 MB; no lse2 array, so never above the sampled softmax's
-    assert ws(128 * 512, 4096, 256) < 100 * 2 ** 20
+    loss_host.sampled_workspace_query_is_monotone(ws)
+    # no lse2 array, so never above the sampled softmax's
     assert ws(128 * 512, 4096, 256) <= L.lib.cr_sampled_ce_workspace(128 * 512, 4096, 256)
 
 
 def test_gbce_desc_mirror_matches_c_layout(tmp_path):
-    if shutil.which("gcc") is None:
-        pytest.skip("gcc not available")
-    probes = [("sizeof(cr_gbce_desc)", ctypes.sizeof(L.GbceDesc)), ("CR_GBCE_SITE", L.CR_GBCE_SITE)]
-    probes += [("offsetof(cr_gbce_desc, %s)" % f, getattr(L.GbceDesc, f).offset) for f, _ in L.GbceDesc._fields_]
-    src = tmp_path / "gbce.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "castrec.h"\nint main(void){' +
-                   "".join('printf("%%zu\\n", (size_t)%s);' % e for e, _ in probes) + 'return 0;}\n')
-    exe = tmp_path / "gbce"
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
-    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split()]
-    assert got == [n for _, n in probes]
+    loss_host.desc_mirror_matches_c_layout(tmp_path, "gbce", ("CR_GBCE_SITE",))
     assert L.CR_GBCE_SITE == gbce_ref.CR_GBCE_SITE == 0x6BCE0000 and L.CR_GBCE_SITE != L.CR_SCE_SITE and L.CR_GBCE_SITE >> 24
     assert "cr_gbce" in L.EXPORTS and "cr_gbce_workspace" in L.EXPORTS
 
@@ -140,12 +73,7 @@ def test_cli_takes_gbce_and_gbce_t():
 
 def test_draw_restatement_matches_a_hand_computed_case():
     seed, step, V, N = 42, 3, 3417, 5
-    inner = (step * 0x9E3779B9 + 0x6BCE0000 * 0x85EBCA77 + 0x165667B1) & 0xFFFFFFFF
-    key = _fmix32_by_hand(seed ^ _fmix32_by_hand(inner))
-    want = []
-    for j in range(N):
-        x = _fmix32_by_hand((key + j * 0x9E3779B1) & 0xFFFFFFFF)
-        want.append(1 + (x * (V - 1) >> 32))
+    want = [1 + (x * (V - 1) >> 32) for x in loss_host.hashes_by_hand(seed, step, N, 0x6BCE0000)]
     got = gbce_ref.draw(seed, step, V, N)
     assert got.dtype == np.int32 and got.tolist() == want
     for V in (2, 3, 17, 10 ** 7):
@@ -153,7 +81,7 @@ def test_draw_restatement_matches_a_hand_computed_case():
         assert s.min() >= 1 and s.max() <= V - 1
     assert not np.array_equal(gbce_ref.draw(7, 11, 10 ** 7, 64), gbce_ref.draw(7, 12, 10 ** 7, 64))
     # a site of its own: not the sampled softmax's negatives at the same (seed, step, V)
-    assert not np.array_equal(gbce_ref.draw(seed, step, 3417, 64), sce_ref.draw(seed, step, 3417, 64))
+    assert not np.array_equal(gbce_ref.draw(seed, step, 3417, 64), loss_ref.draw(seed, step, 3417, 64, loss_ref.SCE_SITE))
 
 
 def test_beta_known_answers():
@@ -175,14 +103,14 @@ BOUND_CASES = [(D, N, V) for D in (8, 50, 256) for N in (1, 7, 256) for V in (17
 @pytest.mark.parametrize("D,N,V", BOUND_CASES)
 def test_emulated_device_arithmetic_stays_within_the_bounds(D, N, V):
     """The bound the GPU test gives cr_gbce 4x of is met at 1x by bf16 hi / lo operands, fp32 sums and fp32 sigma / softplus."""
-    from test_sce_gpu import _case
+    from loss_ref import sampled_case as _case
     M = 203 if D <= 64 else 97
     h, E_, pos, neg, s = _case(D, V, M, N, zlib.crc32(b"gbce%d_%d_%d" % (D, N, V)))
     live = np.flatnonzero(pos)
     assert (N < 2 or s[1] == s[0]) and (N < 3 or (s[2] == pos[live[0]] == pos[live[1]]))       # the planted duplicate and hit
     for b in (1.0, 0.25, 1e-3):
         ref = gbce_ref.ref64(h, E_, pos, neg, s, b)
-        gbce_ref.check(gbce_ref.emulate(h, E_, pos, neg, s, b), ref, scale=1.0)
+        _check(gbce_ref.emulate(h, E_, pos, neg, s, b), ref)
         assert np.all(ref["e_l"][pos != 0] > 0) and np.all(ref["e_l"][pos == 0] == 0)
 
 
@@ -197,7 +125,7 @@ def test_small_e_series_keeps_a_row_of_very_negative_scores():
     s = np.arange(2, 2 + N).astype(np.int32)
     ref = gbce_ref.ref64(h, E_, pos, np.zeros(M, np.int32), s, 1e-3)
     got = gbce_ref.emulate(h, E_, pos, np.zeros(M, np.int32), s, 1e-3)
-    gbce_ref.check(got, ref, scale=1.0)
+    _check(got, ref)
     _sp18 = 18.0 + math.log1p(math.exp(-18.0))
     neg_part = N * math.log1p(math.exp(-18.0))
     assert ref["l"][0] == pytest.approx(1e-3 * _sp18 + neg_part, rel=1e-6)

@@ -10,17 +10,8 @@ import pytest
 import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 
-
-def build_index(M, V, T_pos, seq, pos, neg, times=1, ng=32, ent=16):
-    lay = L.IndexLayout()
-    L.check(L.lib.cr_batch_index_layout(M, V, T_pos, ng, ent, C.byref(lay)), "layout")
-    b = L.lib.cr_index_builder_create(M, V, T_pos, ng, ent)
-    assert b
-    out = np.full(lay.total_words, -7, np.int32)
-    for _ in range(times):                                # (a builder's work arrays are clean again after every build)
-        L.check(L.lib.cr_index_build(b, seq.ctypes.data, pos.ctypes.data, neg.ctypes.data, out.ctypes.data), "build")
-    L.lib.cr_index_builder_destroy(b)
-    return lay, out
+from adam_ref import _table_grad_reference
+from index_harness import build_index
 
 
 def reference_lists(M, V, T_pos, seq, pos, neg):
@@ -174,20 +165,6 @@ def test_dispatch_shape_and_geometry_agree_for_every_hidden_size(tmp_path):
 
 
 # ---- GPU: the gather against the scatter -------------------------------------------------------------------
-def _table_grad_reference(V, T_pos, D, seq, pos, neg, rows, rows2, scale, emb, coef):
-    """fp64: what float atomics summed in rounds 1-4"""
-    M = len(seq)
-    g = np.zeros((V + T_pos, D))
-    r = rows.astype(np.float64) + (rows2.astype(np.float64) if rows2 is not None else 0.0)
-    np.add.at(g, seq, scale * r)
-    np.add.at(g, pos, coef[0][:, None].astype(np.float64) * emb)
-    np.add.at(g, neg, coef[1][:, None].astype(np.float64) * emb)
-    g[0] = 0.0
-    if T_pos:
-        g[V:] = r.reshape(M // T_pos, T_pos, D).sum(0)
-    return g
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("D,V,T_pos,two", [(50, 90, 0, True), (50, 90, 25, False), (64, 3000, 0, True), (20, 12, 25, True), (33, 40, 0, False),
                                            (128, 500, 0, False), (256, 700, 25, True), (6, 9, 0, True), (24, 2, 0, False)])

@@ -8,6 +8,7 @@ import torch
 
 import bf16_ref as br
 import dropout_ref as dr
+from ops_harness import attn_core_ref, dev, new_state, relerr
 
 pytestmark = pytest.mark.gpu
 
@@ -18,22 +19,6 @@ def ops():
     from castrec_amd import ops as O
     assert torch.cuda.is_available()
     return O
-
-
-def dev(a, dtype=torch.float32):
-    return torch.as_tensor(np.asarray(a)).to(dtype).cuda().contiguous()
-
-
-def relerr(got, want):
-    want = np.asarray(want, np.float64)
-    got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
-    return float(np.abs(got - want).max() / (np.abs(want).max() + 1e-30))
-
-
-def new_state(step=0):
-    st = torch.zeros(16, dtype=torch.float32, device="cuda")          # CR_STATE_FLOATS
-    st[4:5].view(torch.int32)[0] = step
-    return st
 
 
 # ------------------------------------------------------------------------------------------------
@@ -218,30 +203,6 @@ def test_eltwise_ops(ops):
 
 
 # ------------------------------------------------------------------------------------------------
-def attn_core_ref(Q, K, V, kvalid, qvalid, resid, H, keep=None, rate=0.0, mm=None, softmax=None):
-    """modules.py:208-269 from the projected Q/K/V on (float64 torch).  mm(a, b, site) / softmax(scores): stand-ins for the two matrix
-    products ("scores", "pv") and the softmax (the rounding model of plain bf16: test_attn_bf_gpu.rounded_model); default: exact."""
-    N, T, C = Q.shape
-    d = C // H
-    mm = mm or (lambda a, b, site: a @ b)
-    softmax = softmax or (lambda s: torch.softmax(s, -1))
-    Q_ = torch.cat(torch.split(Q, d, dim=2), 0); K_ = torch.cat(torch.split(K, d, dim=2), 0); V_ = torch.cat(torch.split(V, d, dim=2), 0)
-    out = mm(Q_, K_.transpose(1, 2), "scores") / d ** 0.5
-    km = kvalid.repeat(H, 1)[:, None, :].expand(-1, T, -1)
-    pad = torch.full_like(out, float(-2 ** 32 + 1))
-    out = torch.where(km == 0, pad, out)
-    tril = torch.tril(torch.ones(T, T, dtype=out.dtype))
-    out = torch.where(tril[None] == 0, pad, out)
-    out = softmax(out)
-    out = out * qvalid.repeat(H, 1)[:, :, None]
-    if keep is not None:
-        out = out * torch.tensor(keep, dtype=out.dtype) / (1.0 - rate)
-    w = out
-    out = mm(out, V_, "pv")
-    out = torch.cat(torch.split(out, N, dim=0), 2)
-    return out + resid, w
-
-
 ATTN_CASES = [  # B, T, H, d, rate
     (3, 8, 1, 6, 0.0), (2, 50, 1, 50, 0.0), (2, 200, 1, 50, 0.2), (3, 37, 2, 32, 0.0), (2, 50, 4, 32, 0.5),
     (1, 256, 1, 64, 0.0), (2, 100, 2, 25, 0.3), (5, 16, 1, 50, 0.0), (5, 24, 1, 20, 0.0), (4, 20, 1, 50, 0.0), (4, 20, 1, 20, 0.2),

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import adam_ref as A
-from test_adam_gpu import Buf
+from adam_ref import Buf
 
 pytestmark = pytest.mark.gpu
 

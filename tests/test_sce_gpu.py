@@ -3,135 +3,33 @@ the fp64 absolute products, as test_ce_gpu.py), accidental hits and duplicates, 
 determinism, accumulation and the state block; Engine(loss="sampled_ce") against the oracle's seq_emb with the sampled loss + autograd
 in fp64, the fed multi-step path, the unchanged existing engines, the refusals, the CLI and the planted corpus."""
 import math
-import os
 import zlib
 
 import numpy as np
 import pytest
 import torch
 
-from oracle import fpmodel as fm
-
-import sce_ref
-from test_ce_gpu import _batch, _planted
+import loss_harness as H
+import loss_ref
+from loss_ref import SCE_SITE
+from loss_ref import planted as _planted
+from loss_ref import sampled_case as _case
+from loss_ref import sampled_softmax_ref64 as _ref64
+from model_harness import E  # noqa: F401  (the engine module, a fixture)
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def E():
-    import castrec_amd  # noqa: F401
-    from castrec_amd import engine
-    return engine
+def _run(h, E_, pos, neg, samples, prec, **kw):
+    return H.run("sampled_ce", h, E_, pos, neg, samples, prec, **kw)
 
 
-def _ops():
-    import castrec_amd  # noqa: F401
-    from castrec_amd import lib as L
-    from castrec_amd import ops as O
-    return L, O
+def _check(got, ref):
+    return loss_ref.check(got, ref, 4.0, "lse")
 
 
-def _case(D, V, M, N, seed):
-    """h [M, D], table [V, D], ~30 % padded rows, a repeated target, one target V-1; N samples with a duplicate and hits planted."""
-    rs = np.random.RandomState(seed)
-    h = rs.standard_normal((M, D)).astype(np.float32) * (1.5 / math.sqrt(D))
-    E_ = rs.standard_normal((V, D)).astype(np.float32) * 1.5
-    pos = rs.randint(1, V, M).astype(np.int32)
-    pos[rs.rand(M) < 0.3] = 0
-    live = np.flatnonzero(pos)
-    if len(live) > 3:
-        pos[live[1]] = pos[live[0]]
-        pos[live[2]] = V - 1
-    neg = rs.randint(1, V, M).astype(np.int32)
-    neg[pos == 0] = 0
-    s = rs.randint(1, V, N).astype(np.int32)
-    if N > 1:
-        s[1] = s[0]                                      # a duplicate
-    if N > 2 and len(live):
-        s[2] = pos[live[0]]                              # an accidental hit of two rows
-    return h, E_, pos, neg, s
-
-
-def _run(h, E_, pos, neg, samples, prec, tg0=None, state0=None, ld=None, seed=0, step=None, N=None, want_tg=True):
-    L, O = _ops()
-    M, D = h.shape
-    V = E_.shape[0]
-    N = len(samples) if samples is not None else N
-    ld = ld or D
-    hs = torch.zeros(M, ld, dtype=torch.float32, device="cuda")
-    hs[:, :D] = torch.from_numpy(h)
-    if ld > D:
-        hs[:, D:] = float("nan")
-    tab = torch.from_numpy(E_).cuda()
-    p = torch.from_numpy(pos).cuda()
-    n = torch.from_numpy(neg).cuda()
-    smp = torch.from_numpy(samples).cuda() if samples is not None else None
-    st = torch.zeros(L.CR_STATE_FLOATS, dtype=torch.float32, device="cuda") if state0 is None else state0.clone()
-    if step is not None:
-        st[4:5].view(torch.int32)[0] = step - 2 ** 32 if step >= 2 ** 31 else step          # (the uint32 word's bits)
-    dh = torch.full((M, D), float("nan"), dtype=torch.float32, device="cuda")
-    tg = (torch.zeros(V, D, dtype=torch.float32, device="cuda") if tg0 is None else tg0.clone()) if want_tg else None
-    lse = torch.full((M,), float("nan"), dtype=torch.float32, device="cuda")
-    so = torch.full((N,), -1, dtype=torch.int32, device="cuda")
-    ws = torch.empty(O.sampled_ce_workspace_bytes(M, N, D), dtype=torch.uint8, device="cuda")
-    O.sampled_ce(hs, ld, tab, p, st, ws, M, N, precision=prec, neg=n, samples=smp, seed=seed, step=st[4:5], samples_out=so,
-                 d_seq_emb=dh, ldd=D, table_grad=tg, lse_out=lse)
-    torch.cuda.synchronize()
-    return dict(dh=dh.cpu().numpy(), tg=tg.cpu().numpy() if want_tg else None, lse=lse.cpu().numpy(), state=st.cpu().numpy(), samples=so.cpu().numpy())
-
-
-def _ref64(h, E_, pos, neg, s, bf16=False):
-    """fp64 results and per-element bounds.  A score's bound es = u * sum_i |h_mi E_vi| (u = 2^-15 for bf16x3, 2^-7 for bf16),
-    carried through the p-weighted sums as in test_ce_gpu.py."""
-    u = 2.0 ** -7 if bf16 else 2.0 ** -15
-    acc = 2.0 ** -7 if bf16 else 2.0 ** -14
-    h = h.astype(np.float64)
-    Ed = E_.astype(np.float64)
-    Es = Ed[s]                                           # [N, D]
-    Et = Ed[pos]                                         # [M, D] (row 0 for padded rows)
-    S = h @ Es.T                                         # [M, N]
-    St = (h * Et).sum(1)
-    es = u * (np.abs(h) @ np.abs(Es).T)
-    et = u * (np.abs(h) * np.abs(Et)).sum(1)
-    hit = s[None, :] == pos[:, None]
-    mx = np.maximum(np.where(hit, -np.inf, S).max(1), St)
-    Z = np.where(hit, 0.0, np.exp(S - mx[:, None]))
-    zt = np.exp(St - mx)
-    tot = Z.sum(1) + zt
-    lse = mx + np.log(tot)
-    P = Z / tot[:, None]
-    pt = zt / tot
-    ist = pos != 0
-    e_lse = (P * es).sum(1) + pt * et + 2.0 ** -20 * (1.0 + np.abs(lse))
-    Pm = P * ist[:, None]
-    gt = np.where(ist, pt - 1.0, 0.0)
-    dh = Pm @ Es + gt[:, None] * Et
-    dE = np.zeros_like(Ed)
-    np.add.at(dE, s, Pm.T @ h)
-    np.add.at(dE, pos[ist], gt[ist, None] * h[ist])
-    W = P * (es + e_lse[:, None]) * ist[:, None]
-    wt = np.where(ist, pt * (et + e_lse), 0.0)
-    e_dh = W @ np.abs(Es) + wt[:, None] * np.abs(Et) + acc * (Pm @ np.abs(Es) + np.abs(gt)[:, None] * np.abs(Et))
-    e_dE = np.zeros_like(dE)
-    np.add.at(e_dE, s, W.T @ np.abs(h) + acc * (Pm.T @ np.abs(h)))
-    np.add.at(e_dE, pos[ist], (wt[ist] + acc * np.abs(gt[ist]))[:, None] * np.abs(h[ist]))
-    loss = float((lse - St)[ist].sum())
-    e_loss = float((e_lse + et)[ist].sum())
-    sn = np.where(neg > 0, (h * Ed[neg]).sum(1), 0.0)
-    return dict(lse=lse, e_lse=e_lse, dh=dh, e_dh=e_dh, dE=dE, e_dE=e_dE, loss=loss, e_loss=e_loss, n=float(ist.sum()), sp=St, sn=sn,
-                ist=ist)
-
-
-def _check(got, ref, scale=4.0):
-    r = np.abs(got["lse"] - ref["lse"]) / (scale * ref["e_lse"])
-    assert np.all(r <= 1.0), ("lse", float(r.max()))
-    r = np.abs(got["dh"] - ref["dh"]) / (scale * ref["e_dh"] + 1e-30)
-    assert np.all(r <= 1.0), ("dh", float(r.max()), np.unravel_index(np.argmax(r), r.shape))
-    r = np.abs(got["tg"] - ref["dE"]) / (scale * ref["e_dE"] + 1e-30)
-    assert np.all(r <= 1.0), ("dE", float(r.max()), np.unravel_index(np.argmax(r), r.shape))
-    assert abs(got["state"][0] - ref["loss"]) <= scale * ref["e_loss"] + 1e-6 * abs(ref["loss"]) + 1e-5, (got["state"][0], ref["loss"])
-    assert got["state"][2] == ref["n"]
+def _draw(seed, step, V, N):
+    return loss_ref.draw(seed, step, V, N, SCE_SITE)
 
 
 CASES = [(D, N, V) for D in (8, 20, 50, 64, 128, 256) for N in (1, 7, 256, 2048) for V in (17, 3417, 100003)]
@@ -139,10 +37,9 @@ CASES = [(D, N, V) for D in (8, 20, 50, 64, 128, 256) for N in (1, 7, 256, 2048)
 
 @pytest.mark.parametrize("D,N,V", CASES)
 def test_sampled_ce_against_fp64(D, N, V):
-    L, _ = _ops()
     M = 203 if D <= 64 else 97
     h, E_, pos, neg, s = _case(D, V, M, N, zlib.crc32(b"sce%d_%d_%d" % (D, N, V)))
-    got = _run(h, E_, pos, neg, s, L.PREC_BF16X3)
+    got = _run(h, E_, pos, neg, s, "bf16x3")
     ref = _ref64(h, E_, pos, neg, s)
     _check(got, ref)
     assert np.all(got["dh"][pos == 0] == 0.0)
@@ -155,20 +52,17 @@ def test_sampled_ce_against_fp64(D, N, V):
 
 @pytest.mark.parametrize("D,N,V", [(20, 256, 17), (50, 256, 3417), (128, 2048, 100003), (256, 7, 3417)])
 def test_plain_bf16_bound(D, N, V):
-    L, _ = _ops()
     h, E_, pos, neg, s = _case(D, V, 151, N, 11 + D + N)
-    _check(_run(h, E_, pos, neg, s, L.PREC_BF16), _ref64(h, E_, pos, neg, s, bf16=True))
+    _check(_run(h, E_, pos, neg, s, "bf16"), _ref64(h, E_, pos, neg, s, bf16=True))
 
 
 def test_pitch_many_rows_and_many_samples():
     """ld > D, more rows than one part of the sample sweep, N above the part budget's knee."""
-    L, _ = _ops()
     h, E_, pos, neg, s = _case(50, 3417, 1237, 4100, 5)
-    _check(_run(h, E_, pos, neg, s, L.PREC_BF16X3, ld=67), _ref64(h, E_, pos, neg, s))
+    _check(_run(h, E_, pos, neg, s, "bf16x3", ld=67), _ref64(h, E_, pos, neg, s))
 
 
 def test_accidental_hits_duplicates_and_padding():
-    L, _ = _ops()
     D, V, M = 32, 50, 96
     rs = np.random.RandomState(2)
     h = rs.standard_normal((M, D)).astype(np.float32) * 0.3
@@ -177,15 +71,15 @@ def test_accidental_hits_duplicates_and_padding():
     pos = np.full(M, 7, np.int32)
     pos[::3] = 0
     neg = np.zeros(M, np.int32)
-    got = _run(h, E_, pos, neg, np.full(8, 7, np.int32), L.PREC_BF16X3)
+    got = _run(h, E_, pos, neg, np.full(8, 7, np.int32), "bf16x3")
     assert got["state"][0] == 0.0 and got["state"][2] == float((pos != 0).sum())
     assert np.all(got["dh"] == 0.0) and np.all(got["tg"] == 0.0)
     # padding rows contribute nothing: the same call with them removed has the same loss and gradients
     s = np.array([3, 9, 9, 7, 20], np.int32)
     pos2 = pos.copy(); pos2[1::5] = 9
     live = pos2 != 0
-    a = _run(h, E_, pos2, neg, s, L.PREC_BF16X3)
-    b = _run(h[live], E_, pos2[live], neg[live], s, L.PREC_BF16X3)
+    a = _run(h, E_, pos2, neg, s, "bf16x3")
+    b = _run(h[live], E_, pos2[live], neg[live], s, "bf16x3")
     assert np.all(a["dh"][~live] == 0.0)
     np.testing.assert_allclose(a["dh"][live], b["dh"], rtol=0, atol=1e-6)
     np.testing.assert_allclose(a["tg"], b["tg"], rtol=1e-5, atol=1e-6)
@@ -203,70 +97,20 @@ def test_accidental_hits_duplicates_and_padding():
 @pytest.mark.parametrize("seed,step,V,N", [(42, 1, 3417, 256), (7, 123456, 17, 300), (0, 2 ** 31 + 5, 10 ** 7, 4096),
                                            (0xDEADBEEF, 9, 2, 7)])
 def test_device_draw_matches_the_numpy_restatement(seed, step, V, N):
-    L, _ = _ops()
-    D, M = 16, 40
-    h, E_, pos, neg, _ = _case(D, min(V, 4000), M, 1, 3)
-    if V > E_.shape[0]:                                  # (a 10^7-row table: its rows' values do not matter here)
-        E_ = np.zeros((V, D), np.float32)
-        E_[:4000] = np.random.RandomState(4).standard_normal((4000, D))
-    got = _run(h, E_, pos, neg, None, L.PREC_BF16X3, seed=seed, step=step, N=N, want_tg=False)
-    want = sce_ref.draw(seed, step, V, N)
-    assert np.array_equal(got["samples"], want)
-    assert got["samples"].min() >= 1 and got["samples"].max() <= V - 1
-    # the drawn ids give the results of the same ids supplied by the caller, bit for bit
-    sup = _run(h, E_, pos, neg, want, L.PREC_BF16X3, want_tg=False)
-    for k in ("lse", "dh"):
-        assert np.array_equal(got[k].view(np.int32), sup[k].view(np.int32)), k
-    assert np.array_equal(got["state"][:3].view(np.int32), sup["state"][:3].view(np.int32))     # ([4], [11]: the step words differ)
-    if V > 2:
-        nxt = _run(h, E_, pos, neg, None, L.PREC_BF16X3, seed=seed, step=step + 1, N=N, want_tg=False)
-        assert not np.array_equal(nxt["samples"], got["samples"])
-        assert np.array_equal(nxt["samples"], sce_ref.draw(seed, step + 1, V, N))
+    H.device_draw_matches("sampled_ce", seed, step, V, N, lambda step: _draw(seed, step, V, N))
 
 
 @pytest.mark.parametrize("D,V,M,N", [(50, 3417, 1300, 256), (128, 100003, 200, 2048), (8, 17, 77, 300)])
 def test_two_calls_give_the_same_bits(D, V, M, N):
-    L, _ = _ops()
-    h, E_, pos, neg, s = _case(D, V, M, N, 3)
-    a = _run(h, E_, pos, neg, s, L.PREC_BF16X3)
-    b = _run(h, E_, pos, neg, s, L.PREC_BF16X3)
-    for k in ("lse", "dh", "state", "samples"):
-        assert np.array_equal(a[k].view(np.int32), b[k].view(np.int32)), k
-    keep = np.ones(V, bool)
-    keep[pos] = False                                    # target rows take float atomics: rounding order may differ
-    assert np.array_equal(a["tg"][keep].view(np.int32), b["tg"][keep].view(np.int32))
-    np.testing.assert_allclose(a["tg"], b["tg"], rtol=1e-5, atol=1e-6)
+    H.two_calls_give_the_same_bits("sampled_ce", _case(D, V, M, N, 3), rtol=1e-5, atol=1e-6)
 
 
 def test_table_grad_accumulates_and_untouched_rows_stay():
-    L, _ = _ops()
-    h, E_, pos, neg, s = _case(64, 3417, 300, 256, 9)
-    rs = np.random.RandomState(1)
-    pre = torch.from_numpy(rs.standard_normal(E_.shape).astype(np.float32)).cuda()
-    got = _run(h, E_, pos, neg, s, L.PREC_BF16X3, tg0=pre)
-    base = _run(h, E_, pos, neg, s, L.PREC_BF16X3)
-    pre = pre.cpu().numpy()
-    untouched = np.setdiff1d(np.arange(E_.shape[0]), np.concatenate([s, pos[pos != 0]]))
-    assert 0 in untouched
-    assert np.array_equal(got["tg"][untouched].view(np.int32), pre[untouched].view(np.int32))
-    assert np.all(base["tg"][untouched] == 0.0)
-    np.testing.assert_allclose(got["tg"], pre + base["tg"], rtol=0, atol=1e-6)
+    H.table_grad_accumulates_and_untouched_rows_stay("sampled_ce", _case(64, 3417, 300, 256, 9), atol=1e-6)
 
 
 def test_state_block_follows_the_head_contract():
-    L, _ = _ops()
-    h, E_, pos, neg, s = _case(50, 500, 400, 64, 4)
-    st = torch.zeros(L.CR_STATE_FLOATS, dtype=torch.float32, device="cuda")
-    st[0], st[1], st[2] = 1.5, 2.0, 3.0
-    st[4:5].view(torch.int32)[0] = 7
-    got = _run(h, E_, pos, neg, s, L.PREC_BF16X3, state0=st)
-    ref = _run(h, E_, pos, neg, s, L.PREC_BF16X3)
-    g, r = got["state"], ref["state"]
-    assert g[0] == np.float32(1.5) + r[0] and g[1] == np.float32(2.0) + r[1] and g[2] == 3.0 + r[2]
-    assert np.array_equal(g[8:11], g[0:3])
-    assert g[11:12].view(np.int32)[0] == 7 and g[4:5].view(np.int32)[0] == 7
-    assert g[12:13].view(np.int32)[0] == 0
-    assert r[2] == float((pos != 0).sum())
+    H.state_block_follows_the_head_contract("sampled_ce", _case(50, 500, 400, 64, 4))
 
 
 # ---- the engine ----------------------------------------------------------------------------------------------------------------
@@ -285,105 +129,17 @@ def _sce_loss(out, pos, samples):
 
 @pytest.mark.parametrize("model", ["sasrec", "cast_1", "cast_5", "cast_9"])
 def test_engine_sampled_ce_step_matches_oracle(E, model):
-    from test_model_gpu import engine_relu_gates
-    rs = np.random.RandomState(zlib.crc32(model.encode()) % 1000)
-    B, T, D, H, itemnum, max_bins = 5, 24, 20, 1, 37, 12
-    hp = E.Hyper(maxlen=T, hidden_units=D, num_blocks=2, num_heads=H, dropout_rate=0.0, max_bins=max_bins, num_context_blocks=1,
-                 lr=1e-3, seed=7)
-    ohp = fm.Hyper(maxlen=T, hidden_units=D, num_blocks=2, num_heads=H, dropout_rate=0.0, max_bins=max_bins, num_context_blocks=1,
-                   lr=1e-3)
-    eng = E.Engine(model, 9, itemnum, hp, B, training=True, n_slabs=7, loss="sampled_ce", ce_negatives=16)
+    eng = H.engine_step_matches_oracle(E, model, dict(loss="sampled_ce", ce_negatives=16),
+                                       lambda eng, out, pos, samples: _sce_loss(out, pos, samples), rel=2e-5, grad_tol=2e-3,
+                                       adam_tol=0.02, draw=_draw)
     assert eng.loss == "sampled_ce" and not eng.use_index and not eng.bitwise_reproducible and eng.ce_negatives == 16
-    P = fm.init_params(model, 9, itemnum, ohp, seed=3)
-    P = {k: v + 0.1 * torch.tensor(rs.standard_normal(tuple(v.shape))) for k, v in P.items()}
-    eng.load_params(P)
-    P = {k: v.double().cpu() for k, v in eng.get_params().items()}
-    seq, pos, neg, time, hours, days = _batch(rs, B, T, itemnum, max_bins)
-    batch = fm.to_batch(seq, pos, neg, time, hours, days)
-    eng.set_batch(seq, pos, neg, time, hours, days)
-    eng.set_step(1)
-    eng.launch_step(apply=False)
-    torch.cuda.synchronize()
-    samples = eng.samples.cpu().numpy()
-    assert np.array_equal(samples, sce_ref.draw(7, 1, itemnum + 1, 16))
-    gates, care = engine_relu_gates(eng, B, T, None)
-
-    def oracle(smp):
-        leaves = {k: v.detach().clone().requires_grad_(True) for k, v in P.items()}
-        with fm.handed_over_gates(gates, care, check=True):
-            out = fm.forward(model, leaves, ohp, batch, None)
-        loss = _sce_loss(out, pos, smp)
-        loss.backward()
-        return loss, {k: (v.grad if v.grad is not None else torch.zeros_like(v)) for k, v in leaves.items()}
-
-    loss, G = oracle(samples)
-    st = eng.state.cpu().numpy()
-    n = float((pos != 0).sum())
-    assert st[2] == n
-    assert st[0] / n == pytest.approx(loss.item(), rel=2e-5)
-    got = eng.grads()
-    gmax = max(float(G[k].abs().max()) for k in G)
-    for k in G:
-        if k.endswith(".bk"):                            # d loss / d bk == 0 identically: rounding noise on both sides
-            continue
-        ref = G[k].numpy()
-        err = float(np.abs(got[k].cpu().double().numpy() - ref).max())
-        assert err < 2e-3 * max(float(np.abs(ref).max()), 1e-3 * gmax), (k, err, float(np.abs(ref).max()))
-    # one Adam step on both sides (the same step word: the same samples)
-    eng.Gt.zero_()
-    eng.set_step(1)
-    eng.launch_step(apply=True)
-    torch.cuda.synchronize()
-    assert np.array_equal(eng.samples.cpu().numpy(), samples)
-    lr = hp.lr
-    P1 = fm.AdamTF(P, lr=lr).step(dict(P), G)
-    now = eng.get_params()
-    for k in P:
-        if k.endswith(".bk"):
-            continue
-        d_eng = now[k].double().cpu() - P[k]
-        d_orc = P1[k] - P[k]
-        big = G[k].abs() > 1e-2 * max(float(G[k].abs().max()), 1e-3 * gmax)
-        assert float((d_eng - d_orc).abs().max()) <= 2.0 * lr + 1e-7, k
-        if bool(big.any()):
-            assert float((d_eng - d_orc)[big].abs().max()) <= 0.02 * lr, k
-    assert eng.loss_auc()[0] == pytest.approx(loss.item(), rel=2e-5)
 
 
 def test_fed_multi_step_path_matches_train_step(E):
-    B, T, D, itemnum = 16, 20, 32, 300
-    hp = E.Hyper(maxlen=T, hidden_units=D, num_blocks=2, num_heads=1, dropout_rate=0.2, seed=5, loss="sampled_ce", ce_negatives=64)
-    batches = [_planted(np.random.RandomState(100 + i), B, T, itemnum) for i in range(8)]
-    a = E.Engine("sasrec", 10, itemnum, hp, B, training=True)
+    a, _, seen, _ = H.fed_multi_step_path_matches_train_step(E, dict(loss="sampled_ce", ce_negatives=64), {}, _planted,
+                                                             quantile_bound=1e-5, max_bound_lr=8, draw=_draw)
     assert a.loss == "sampled_ce" and a.ce_negatives == 64
-    a.capture()
-    a.set_step(1)
-    a.enable_feed(n_slots=16, steps_per_graph=4)
-    assert a.graph_steps == 4
-    ran = 0
-    for bt in batches:
-        a.feed(*bt)
-    while ran < 8:
-        ran += a.train_fed()
-    torch.cuda.synchronize()
-    b = E.Engine("sasrec", 10, itemnum, hp, B, training=True)
-    b.capture()
-    b.set_step(1)
-    seen = []
-    for bt in batches:
-        b.train_step(*bt)
-        seen.append(b.samples.cpu().numpy().copy())
-    torch.cuda.synchronize()
-    assert a.step_number() == b.step_number() == 9
-    # each step drew its own samples: those of step k are the draw at step word k
-    for k, s in enumerate(seen):
-        assert np.array_equal(s, sce_ref.draw(5, k + 1, itemnum + 1, 64)), k
     assert len({s.tobytes() for s in seen}) == 8
-    assert np.array_equal(a.samples.cpu().numpy(), seen[-1])
-    pa, pb = a.get_params(), b.get_params()
-    d = np.concatenate([(pa[k] - pb[k]).abs().reshape(-1).cpu().numpy() for k in pa if not k.endswith(".bk")])
-    assert np.quantile(d, 0.999) < 1e-5 and d.max() < 8 * hp.lr, (np.quantile(d, 0.999), d.max())
-    assert a.loss_auc()[0] == pytest.approx(b.loss_auc()[0], rel=1e-4)
 
 
 def test_existing_engines_unchanged_and_refusals(E):
@@ -430,46 +186,11 @@ def test_existing_engines_unchanged_and_refusals(E):
 
 
 def test_main_cli_trains_with_sampled_ce_and_logs_finite_numbers(tmp_path, monkeypatch, caplog):
-    import json
-    import logging
-    import re
-    import main as cli
-    monkeypatch.chdir(tmp_path)
-    caplog.set_level(logging.INFO)
-    rc = cli.main(["--dataset", "synthetic:tiny", "--train_dir", "t", "--model", "cast_1", "--maxlen", "12", "--batch_size", "4",
-                   "--hidden_units", "16", "--num_epochs", "2", "--eval_every", "1", "--max_bins", "20", "--loss", "sampled_ce",
-                   "--ce_negatives", "16", "--eval_full_ranking"])
-    assert rc == 0
-    runs = os.listdir(tmp_path / "saved_models" / "synthetic_tiny")
-    d = tmp_path / "saved_models" / "synthetic_tiny" / runs[0]
-    params = json.loads((d / "params.txt").read_text())
-    assert params["loss"] == "sampled_ce" and params["ce_negatives"] == 16
-    assert not [r for r in caplog.records if r.levelno >= logging.ERROR], caplog.text[-2000:]
-    train = [float(x) for x in re.findall(r"TRAIN/loss (\S+)", caplog.text)]
-    full = re.findall(r"full ranking: valid \(NDCG@10: (\S+), HR@10: (\S+)\), test \(NDCG@10: (\S+), HR@10: (\S+)\)", caplog.text)
-    assert len(train) == 2 and len(full) == 2, caplog.text[-2000:]
-    vals = train + [float(x) for row in full for x in row] + [float(x) for x in re.findall(r"\d+\.\d+", (d / "log.txt").read_text())]
-    assert all(math.isfinite(v) for v in vals), vals
-    assert all(0 < v < 3 * math.log(17) for v in train), train      # (17 candidates per row at most)
+    H.main_cli_trains(tmp_path, monkeypatch, caplog, ["--loss", "sampled_ce", "--ce_negatives", "16"],
+                      dict(loss="sampled_ce", ce_negatives=16), full_ranking=True,
+                      loss_ceiling=3 * math.log(17))                       # (17 candidates per row at most)
 
 
 def test_sampled_ce_training_learns_a_planted_corpus(E):
-    rs = np.random.RandomState(0)
-    B, T, D, itemnum = 64, 20, 32, 400
-    hp = E.Hyper(maxlen=T, hidden_units=D, num_blocks=2, num_heads=1, dropout_rate=0.1, lr=5e-3, seed=3)
-    eng = E.Engine("sasrec", 10, itemnum, hp, B, training=True, loss="sampled_ce", ce_negatives=64)
-    eng.capture()
-    eng.set_step(1)
-    for _ in range(250):
-        eng.train_step(*_planted(rs, B, T, itemnum))
-    torch.cuda.synchronize()
-    loss, _ = eng.loss_auc()
-    assert loss < 0.5 * math.log(65), loss
-    # full-ranking HR@10 of the next item after each test sequence's last one (chance: 10 / 400)
-    ev = E.Engine("sasrec", 10, itemnum, hp, B, training=False, share=eng)
-    seq, pos, _ = _planted(np.random.RandomState(99), B, T, itemnum)
-    ev.forward_eval(seq)
-    ids, _, rank = ev.topk(10, targets=pos[:, -1])
-    torch.cuda.synchronize()
-    hr = float((rank.cpu().numpy() < 10).mean())
-    assert hr > 0.5, hr
+    H.training_learns_a_planted_corpus(E, dict(B=64, T=20, D=32, itemnum=400, lr=5e-3), 250, _planted,
+                                       dict(loss="sampled_ce", ce_negatives=64), loss_ceiling=0.5 * math.log(65), hr_floor=0.5)

@@ -1,6 +1,7 @@
 """The popularity proposal of the sampled softmax, host side (no GPU): the proposal builder against known answers and an independent
 restatement, what it refuses, the restated draw by hand and by its frequencies, cr_sampled_ce's two new argument checks, the
 --ce_proposal / --ce_pop_power options, and the fp64 reference of the skewed planted corpus on the GPU test's schedule."""
+import functools
 import math
 
 import numpy as np
@@ -10,8 +11,11 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 from castrec_amd.proposal import build_proposal, effective_items
 
+import loss_host
 import sce_pop_ref
-from test_sce_host import _fmix32_by_hand, _rejects, _valid_desc
+
+_valid_desc = functools.partial(loss_host.valid_desc, "sampled_ce")
+_rejects = functools.partial(loss_host.rejects, "sampled_ce")
 
 
 def test_builder_known_answers():
@@ -74,12 +78,8 @@ def test_builder_refusals_name_the_first_offending_id():
 def test_draw_restatement_matches_a_hand_computed_case():
     seed, step, N = 42, 3, 6
     cdf = [0, 2 ** 30, 2 ** 31, 2 ** 31 + 5, 2 ** 32 - 1]        # masses 2^30, 2^30, 5, 2^31 - 5 (the last entry reads as 2^32)
-    inner = (step * 0x9E3779B9 + sce_pop_ref.CR_SCE_SITE * 0x85EBCA77 + 0x165667B1) & 0xFFFFFFFF
-    key = _fmix32_by_hand(seed ^ _fmix32_by_hand(inner))
-    want = []
-    for j in range(N):
-        x = _fmix32_by_hand((key + j * 0x9E3779B1) & 0xFFFFFFFF)
-        want.append(next(s for s in range(1, 5) if x < (cdf[s] if s < 4 else 2 ** 32)))
+    want = [next(s for s in range(1, 5) if x < (cdf[s] if s < 4 else 2 ** 32))
+            for x in loss_host.hashes_by_hand(seed, step, N, sce_pop_ref.CR_SCE_SITE)]
     got = sce_pop_ref.draw(seed, step, np.array(cdf, np.uint32), N)
     assert got.dtype == np.int32 and got.tolist() == want
     # the edges: x = cdf[s] belongs to item s + 1, x = 2^32 - 1 to the last item even though cdf[V-1] = 2^32 - 1 is not above it

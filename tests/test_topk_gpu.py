@@ -10,9 +10,10 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 from castrec_amd import ops as O
 
+from topk_index_ref import REL, _excl_lists, _inputs, _model
+
 pytestmark = pytest.mark.gpu
 KMAX = L.CR_TOPK_MAX
-REL = 1e-5                       # bf16x3 against the fp64 dot, relative to sum_i |q_i t_i| (the scale of a dot product's rounding)
 
 
 def _run(Q, T, K, excl=None, targets=None, precision=L.PREC_BF16X3, ld=None):
@@ -65,22 +66,6 @@ def _check(Q, T, K, excl, ids, scores, rel=REL):
         assert sure <= set(gi.tolist()), (b, sure - set(gi.tolist()))
         for i in gi:                                                         # anything else is within the tolerance of the K-th
             assert S[b, i] >= kth - 2 * tol, (b, i, S[b, i], kth)
-
-
-def _excl_lists(rs, B, V, n_max):
-    out = []
-    for b in range(B):
-        kind = b % 4
-        if kind == 0:
-            out.append([])
-        elif kind == 1:
-            r = rs.randint(0, V + 3, rs.randint(1, n_max + 1)).tolist()         # ids past the table, 0
-            out.append(r + r[:2] + [0])                                      # duplicates
-        elif kind == 2:
-            out.append(rs.randint(1, max(2, V), rs.randint(1, n_max + 1)).tolist())
-        else:
-            out.append(list(range(1, V))[: max(0, V - 3)])                   # fewer than K eligible when K > 2
-    return out
 
 
 @pytest.mark.parametrize("D", [20, 50, 64, 128, 256])
@@ -200,27 +185,6 @@ def test_deterministic():
 
 
 # ---- the public surface ----------------------------------------------------------------------------------------------------------------
-def _model(name, itemnum=500, D=50, T=20, seed=0):
-    from castrec_amd.models import build_model
-    args = types.SimpleNamespace(maxlen=T, hidden_units=D, num_blocks=2, num_heads=1, dropout_rate=0.0, l2_emb=0.0, lr=1e-3,
-                                 max_bins=20, bin_in_hours=24, num_context_blocks=2, log_scale=False, input_context=False)
-    m = build_model(name, 20, itemnum, 5.0, args)
-    rs = np.random.RandomState(seed)
-    P = m.get_params()
-    m.load_params({k: v.cpu().numpy() + 0.1 * rs.standard_normal(tuple(v.shape)).astype(np.float32) for k, v in P.items()})
-    return m
-
-
-def _inputs(rs, B, T, itemnum, max_bins=20):
-    seq = rs.randint(1, itemnum + 1, (B, T)).astype(np.int32)
-    for b in range(B):
-        seq[b, : rs.randint(0, T - 2)] = 0
-    ts = (rs.randint(0, max_bins + 1, (B, T)) * (seq != 0)).astype(np.int32)
-    hrs = (rs.randint(1, 25, (B, T)) * (seq != 0)).astype(np.int32)
-    dys = (rs.randint(1, 8, (B, T)) * (seq != 0)).astype(np.int32)
-    return seq, ts, hrs, dys
-
-
 @pytest.mark.parametrize("name", ["sasrec", "cast_1", "cast_9"])
 def test_recommend_matches_predict_over_all_items(name):
     itemnum, B, T, k = 500, 9, 20, 25

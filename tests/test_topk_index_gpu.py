@@ -12,7 +12,7 @@ from castrec_amd import lib as L
 from castrec_amd import ops as O
 from castrec_amd.index import ItemIndex
 import topk_index_ref as R
-from test_topk_gpu import REL, _excl_lists, _inputs, _model
+from topk_index_ref import REL, _excl_lists, _inputs, _model
 
 pytestmark = pytest.mark.gpu
 SPLIT, PLAIN = L.PREC_BF16X3, L.PREC_BF16
