@@ -22,6 +22,9 @@
 // (tile of 16 rows, k-step) are 1 KB contiguous, the lo halves a second plane.  The IDX instantiations of both kernels load those
 // fragments (whole tiles in the sweep, one row per lane for the targets and the excluded rows) where the others load, mask and split
 // table rows; everything after the A operand is the same code, so a score has the same bits either way.
+//
+// Gathered sub-index (castrec.h cr_topk_index_gather): a row's fragments depend on that row alone, so the index of a subset of the rows
+// is made by copying them (k_topk_index_gather, from an index or from the table); a search of it is the two launches above on fewer rows.
 #include <algorithm>
 
 #include "cr_bf16.hpp"
@@ -448,6 +451,40 @@ __global__ __launch_bounds__(256) void k_topk_index_build(const float* table, in
     }
 }
 
+// The index of the table {0; source row ids[0]; ...; source row ids[n - 1]} (castrec.h cr_topk_index_gather): a wave per destination
+// tile, lane (li, lg) holds destination row 16 tile + li = source row ids[16 tile + li - 1].  A lane without a source row (destination
+// row 0, rows > n of the last tile, an id outside 1 .. V-1) stores +0.  From an index (IDX) the row's 16-byte groups are copied as
+// tk_idx_row reads them; from the table the row is masked and split as the build does it.  Either way the build's store, so the bytes
+// are the build's on the gathered table.
+template <int NK, bool SPLIT, bool IDX>
+__global__ __launch_bounds__(256) void k_topk_index_gather(const float* table, const bf8* src, int64_t src_plane, int V, int D,
+                                                           const int32_t* ids, int n, bf8* idx, int64_t plane, int n_tiles) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15;
+    const int tile = blockIdx.x * 4 + wave;
+    if (tile >= n_tiles) return;                           // wave-uniform
+    const int j = tile * 16 + li - 1;
+    const int id = (j >= 0 && j < n) ? ids[j] : 0;
+    const bool rok = id >= 1 && id < V;
+    const int row = rok ? id : 0;
+    bf8 h[NK], lo[NK];
+    if constexpr (IDX) {
+        TkIdxArgs a;
+        a.idx = src;
+        a.plane = src_plane;
+        tk_idx_row<NK, SPLIT>(a, row, rok, h, lo);
+    } else {
+        float v[NK][8];
+        tk_row_issue<NK>(v, table, D, row, rok, row == V - 1, D);
+        tk_row_finish<NK, SPLIT>(v, table, D, row, rok, row == V - 1, D, h, lo);
+    }
+    bf8* p = idx + (int64_t)tile * (NK * 64) + lane;
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        p[ks * 64] = h[ks];
+        if (SPLIT) p[plane + ks * 64] = lo[ks];
+    }
+}
+
 // planes of an index of `precision`: 2 (hi + lo; CR_PREC_F32 as CR_PREC_BF16X3), 1 (plain bf16), 0 for anything else
 int tk_index_planes(int precision) {
     return (precision == CR_PREC_BF16X3 || precision == CR_PREC_F32) ? 2 : precision == CR_PREC_BF16 ? 1 : 0;
@@ -513,6 +550,42 @@ extern "C" int cr_topk_index_build(const float* table, int V, int D, int precisi
         hipLaunchKernelGGL((k_topk_index_build<nk, sp>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, V, D, idx, plane, n_tiles);
     });
     return cr_check_launch("cr_topk_index_build");
+}
+
+extern "C" int cr_topk_index_gather(const float* table, const void* index, int index_precision, int V, int D, const int32_t* ids,
+                                    int n, int precision, void* out_index, size_t out_bytes, void* stream) {
+    CR_REQUIRE((table != nullptr) != (index != nullptr), "cr_topk_index_gather: exactly one source, table or index, must be non-NULL (%s)",
+               table ? "both given" : "both NULL");
+    CR_REQUIRE(ids && out_index, "cr_topk_index_gather: NULL ids or out_index");
+    CR_REQUIRE(D >= 8 && D <= 256, "cr_topk_index_gather: D=%d outside 8 .. 256", D);
+    CR_REQUIRE(V >= 1, "cr_topk_index_gather: V=%d must be >= 1", V);
+    CR_REQUIRE(n >= 1 && n < 0x7fffffff, "cr_topk_index_gather: n=%d must be >= 1 (and n + 1 an int)", n);
+    const int planes = tk_index_planes(precision);
+    CR_REQUIRE(planes != 0, "cr_topk_index_gather: unknown precision %d", precision);
+    int64_t src_plane = 0;
+    if (index) {
+        const int sp = tk_index_planes(index_precision);
+        CR_REQUIRE(sp != 0, "cr_topk_index_gather: unknown index_precision %d", index_precision);
+        CR_REQUIRE(planes <= sp, "cr_topk_index_gather: a plain bf16 index has no lo plane for a sub-index of precision %d", precision);
+        src_plane = (((int64_t)V + 15) / 16) * tk_nk(D) * 64;
+    }
+    const size_t need = cr_topk_index_bytes(n + 1, D, precision);
+    CR_REQUIRE(out_bytes >= need, "cr_topk_index_gather: out_index of %zu bytes, cr_topk_index_bytes(n + 1 = %d) says %zu", out_bytes,
+               n + 1, need);
+    const int NK = tk_nk(D), n_tiles = (int)(((int64_t)n + 1 + 15) / 16);
+    const int64_t plane = (int64_t)n_tiles * NK * 64;
+    bf8* idx = static_cast<bf8*>(out_index);
+    const bf8* src = static_cast<const bf8*>(index);
+    hipStream_t st = cr_stream(stream);
+    tk_dispatch(NK, planes == 2, [&](auto nk, auto sp) {
+        if (index)
+            hipLaunchKernelGGL((k_topk_index_gather<nk, sp, true>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, src, src_plane, V, D,
+                               ids, n, idx, plane, n_tiles);
+        else
+            hipLaunchKernelGGL((k_topk_index_gather<nk, sp, false>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, src, src_plane, V, D,
+                               ids, n, idx, plane, n_tiles);
+    });
+    return cr_check_launch("cr_topk_index_gather");
 }
 
 extern "C" size_t cr_score_topk_workspace(int B, int V, int D, int K) {

@@ -1670,8 +1670,21 @@ class Engine:
         the items each row must not return nor count in its target's rank; targets: [B] ids whose rank among the eligible items is
         wanted (-1: excluded).  Scores come from bf16x3 products (fp32-grade; plain bf16 on an engine at attn_precision 'bf16');
         test_logits keeps its exact fp32 form.  index: an ItemIndex of this engine's item table (castrec_amd.index): the scores come
-        from it instead of the table, with the same bits.  castrec.h cr_score_topk."""
+        from it instead of the table, with the same bits.  castrec.h cr_score_topk.  index may also be an ItemSubset of the table:
+        the best k among its items only -- ids, exclusions and targets stay global ids, a target outside the subset has rank -1 and
+        ranks count the subset's eligible items."""
         B, V, D = self.B, self.itemnum + 1, self.D
+        from .index import ItemSubset, excl_to_local, to_local
+        subset = index if isinstance(index, ItemSubset) else None
+        if subset is not None:
+            if (subset.parent_V, subset.D) != (V, D):
+                raise ValueError("subset of a [%d, %d] table, the engine's item table is [%d, %d]" % (subset.parent_V, subset.D, V, D))
+            m = subset._map                                   # the host copy of subset.ids
+            if excl_ids is not None and excl_off is not None:
+                excl_off, excl_ids = excl_to_local(m, excl_off, excl_ids.cpu().numpy() if torch.is_tensor(excl_ids) else excl_ids)
+            if targets is not None:
+                targets = to_local(m, targets.cpu().numpy() if torch.is_tensor(targets) else targets)
+            index, V = subset.index, subset.index.V
         need = O.topk_workspace_bytes(B, V, D, int(k))
         ws = getattr(self, "_topk_ws", None)
         if ws is None or ws.numel() < need:
@@ -1697,6 +1710,8 @@ class Engine:
                 raise ValueError("index of a [%d, %d] table, the engine's item table is [%d, %d]" % (index.V, index.D, V, D))
             O.score_topk(query, self.T * ld, (V, D), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank,
                          index=index.blob, index_precision=index.prec)
+            if subset is not None:
+                ids = subset.ids.to(self.dev)[ids.long()]     # local -> global; local 0 (fewer than k eligible) stays 0
             return ids, scores, rank
         O.score_topk(query, self.T * ld, self.p("item_emb"), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank)
         return ids, scores, rank

@@ -5,6 +5,11 @@ engine needed -- and saved / loaded as one file.  A search returns the bits of t
     ix = ItemIndex.build(table)                    # table: float32 CUDA tensor [V, D]; or model.build_item_index()
     ids, scores = ix.search(queries, k=10)         # queries [B, D] float32, numpy or CUDA
     ix.save("items.npz"); ix = ItemIndex.load("items.npz")
+
+ItemSubset: "the best k among these items" for a whole batch -- the allowed rows gathered once into a compact sub-index (castrec.h
+cr_topk_index_gather) that the same search runs over; global ids in and out, the score bits of the full search.
+
+    ids, scores = ix.search(queries, k=10, allow=in_stock)      # or: sub = ix.subset(in_stock); sub.search(queries, k=10)
 """
 import numpy as np
 import torch
@@ -43,6 +48,43 @@ def excl_csr(rows, B):
     return off, ids
 
 
+# ---- shared candidate subsets: global ids <-> the local ids of a gathered sub-index (pure numpy; ItemSubset and Engine.topk) --------
+def subset_ids(ids, V):
+    """Any iterable of item ids -> the subset's id map: int32 [n + 1], ascending without duplicates, [0] == 0 (local row 0 is the zero
+    padding row, local row 1 + j is item map[1 + j]).  ValueError for an empty set or an id outside 1 .. V-1."""
+    a = np.unique(np.asarray(ids if isinstance(ids, np.ndarray) else list(ids), np.int64).ravel())
+    if a.size == 0:
+        raise ValueError("a subset needs at least one item id")
+    if a[0] < 1 or a[-1] > V - 1:
+        raise ValueError("subset ids must be item ids in 1 .. %d, got %d .. %d" % (V - 1, a[0], a[-1]))
+    return np.concatenate([np.zeros(1, np.int64), a]).astype(np.int32)
+
+
+def to_local(sorted_ids, ids):
+    """Global ids -> local ids of the subset whose id map is sorted_ids (subset_ids): same shape, int32; id 0 stays 0 and an id that
+    is not in the subset becomes -1 (as a target that reads "rank -1"; excl_to_local drops it)."""
+    sorted_ids = np.asarray(sorted_ids, np.int64)
+    ids = np.asarray(ids, np.int64)
+    pos = np.minimum(np.searchsorted(sorted_ids, ids), sorted_ids.size - 1)
+    return np.where(sorted_ids[pos] == ids, pos, -1).astype(np.int32)
+
+
+def to_global(sorted_ids, local):
+    """Local ids of a search of the subset -> global ids: local 0, the "fewer than k eligible" filler, stays 0."""
+    return np.asarray(sorted_ids)[np.asarray(local, np.int64)]
+
+
+def excl_to_local(sorted_ids, off, ids):
+    """An exclusion CSR (excl_csr) on global ids -> the same on local ids; ids outside the subset (and 0) are dropped."""
+    if off is None or ids is None:
+        return None, None
+    off = np.asarray(off, np.int64)
+    loc = to_local(sorted_ids, np.asarray(ids, np.int64)[off[0]:off[-1]])
+    keep = loc > 0
+    kept = np.concatenate([np.zeros(1, np.int64), np.cumsum(keep, dtype=np.int64)])       # kept[i]: survivors among the first i ids
+    return kept[off - off[0]], loc[keep].astype(np.int32)
+
+
 class ItemIndex(object):
     """V, D: the table's shape; precision: "bf16x3" (hi + lo planes: serves every search precision) or "bf16" (hi only, half the bytes:
     plain-bf16 searches only); blob: the uint8 tensor of castrec.h's layout; version: the parameter version of the model that built it
@@ -68,10 +110,23 @@ class ItemIndex(object):
         p = _prec(precision)
         return cls(table.shape[0], table.shape[1], p, O.topk_index_build(table, p), version)
 
-    def search(self, queries, k, exclude=None, targets=None, precision=None):
+    def subset(self, ids):
+        """An ItemSubset of the items `ids` (any iterable of ids in 1 .. V-1), gathered out of this index: no table needed.  The
+        subset inherits precision and version."""
+        if not self.blob.is_cuda:
+            raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to gather a subset")
+        m = torch.from_numpy(subset_ids(ids, self.V)).to(self.blob.device)
+        with torch.cuda.device(self.blob.device):
+            blob = O.topk_index_gather(m[1:], self.prec, index=self.blob, index_precision=self.prec, V=self.V, D=self.D)
+        return ItemSubset(ItemIndex(m.numel(), self.D, self.prec, blob, self.version), m, self.V, self.version)
+
+    def search(self, queries, k, exclude=None, targets=None, precision=None, allow=None):
         """The k best items for each query row (dot product), as Model.recommend returns them: numpy (ids [B, k], scores [B, k]) and,
         with targets, each target's rank.  exclude: None or one iterable of ids per row.  precision: the search arithmetic, by
-        default the index's own."""
+        default the index's own.  allow: an iterable of ids -- the best k among those items only, for every row: shorthand for
+        self.subset(allow).search(...) (keep the ItemSubset to search the same set again)."""
+        if allow is not None:
+            return self.subset(allow).search(queries, k, exclude=exclude, targets=targets, precision=precision)
         if not self.blob.is_cuda:
             raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to search")
         dev = self.blob.device
@@ -119,3 +174,83 @@ class ItemIndex(object):
                 raise ValueError("%s: blob of %d bytes does not fit its meta V=%d D=%d precision=%d (%d bytes)"
                                  % (path, blob.size, V, D, p, need))
         return cls(V, D, p, torch.from_numpy(np.ascontiguousarray(blob)).to(device), None)
+
+
+SUBSET_FORMAT = 1
+
+
+class ItemSubset(object):
+    """A candidate subset shared by every query of a search: "the best k among these items".  index: an ItemIndex of the gathered
+    [n + 1, D] table {0; item ids[1]; ...; item ids[n]} (castrec.h cr_topk_index_gather: the bytes cr_topk_index_build gives on that
+    table, so a score has the bits of the full search); ids: int32 [n + 1] on the index's device, ascending, ids[0] == 0 -- local
+    row -> global id; parent_V: the rows of the table the ids refer to; version: as ItemIndex.version.  Ascending ids make the local
+    order the global order, so ties break as in the full search.  Everything public takes and returns global ids; ranks are ranks
+    among the eligible items of the subset.  One subset per call: per-query masks are not supported.
+
+        sub = ix.subset(ids)                           # out of an ItemIndex; or ItemSubset.build(table, ids) from the fp32 table
+        top, scores = sub.search(queries, k=10)        # == ix.search(queries, 10, allow=ids)
+        sub.save("instock.npz"); sub = ItemSubset.load("instock.npz")
+    """
+
+    def __init__(self, index, ids, parent_V, version=None):
+        self.index, self.ids, self.parent_V, self.version = index, ids, int(parent_V), version
+        self._map = ids.cpu().numpy()
+        m = self._map
+        if (ids.dtype != torch.int32 or m.ndim != 1 or m.size != index.V or m.size < 2 or m[0] != 0 or np.any(np.diff(m.astype(np.int64)) <= 0)
+                or m[-1] > self.parent_V - 1):
+            raise ValueError("subset ids must be int32 [%d]: 0, then ascending item ids below %d" % (index.V, self.parent_V))
+
+    D = property(lambda self: self.index.D)
+    precision = property(lambda self: self.index.precision)
+    prec = property(lambda self: self.index.prec)
+
+    @classmethod
+    def build(cls, table, ids, precision="bf16x3", version=None):
+        """From the fp32 table itself (a float32 CUDA tensor [V, D]): only the subset's rows are read, no full index is needed."""
+        if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2:
+            raise TypeError("ItemSubset.build takes a float32 CUDA tensor [V, D]")
+        table = table.contiguous()
+        p = _prec(precision)
+        V, D = table.shape
+        m = torch.from_numpy(subset_ids(ids, V)).to(table.device)
+        with torch.cuda.device(table.device):
+            blob = O.topk_index_gather(m[1:], p, table=table)
+        return cls(ItemIndex(m.numel(), D, p, blob, version), m, V, version)
+
+    def search(self, queries, k, exclude=None, targets=None, precision=None):
+        """ItemIndex.search among the subset's items: global ids in, global ids out.  An excluded id outside the subset is ignored; a
+        target outside it (or excluded) has rank -1; a row with fewer than k eligible items ends in id 0, score -inf."""
+        rows = None
+        if exclude is not None:
+            off, ids = excl_to_local(self._map, *excl_csr(exclude, len(queries)))
+            rows = [ids[off[b]:off[b + 1]] for b in range(len(off) - 1)]
+        if targets is not None:
+            targets = to_local(self._map, targets.cpu().numpy() if torch.is_tensor(targets) else targets)
+        out = self.index.search(queries, k, exclude=rows, targets=targets, precision=precision)
+        return (to_global(self._map, out[0]),) + tuple(out[1:])
+
+    def save(self, path):
+        """One uncompressed .npz: blob (uint8), ids (int32 [n + 1]) and meta = [format, n + 1, D, precision, parent_V]."""
+        with open(path, "wb") as f:
+            np.savez(f, blob=self.index.blob.cpu().numpy(), ids=self._map,
+                     meta=np.array([SUBSET_FORMAT, self.index.V, self.D, self.prec, self.parent_V], np.int64))
+        return path
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        """device="cpu" only inspects the file; such a subset does not search.  version is None."""
+        with np.load(path) as z:
+            meta = [int(x) for x in z["meta"]]
+            if len(meta) != 5 or meta[0] != SUBSET_FORMAT or "ids" not in z.files:
+                raise ValueError("%s: not an item subset file of format %d (meta %s; an ItemIndex file loads with ItemIndex.load)"
+                                 % (path, SUBSET_FORMAT, meta))
+            _, V, D, p, parent_V = meta
+            need = L.lib.cr_topk_index_bytes(V, D, p) if p in _NAMES else 0
+            blob, ids = z["blob"], z["ids"]
+            if need == 0 or blob.dtype != np.uint8 or blob.size != need:
+                raise ValueError("%s: blob of %d bytes does not fit its meta n + 1=%d D=%d precision=%d (%d bytes)"
+                                 % (path, blob.size, V, D, p, need))
+            if ids.dtype != np.int32:
+                raise ValueError("%s: ids of type %s, int32 expected" % (path, ids.dtype))
+        index = ItemIndex(V, D, p, torch.from_numpy(np.ascontiguousarray(blob)).to(device), None)
+        return cls(index, torch.from_numpy(np.ascontiguousarray(ids)).to(device), parent_V, None)

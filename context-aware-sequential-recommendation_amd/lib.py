@@ -246,6 +246,7 @@ _sig("cr_score_topk_workspace", C.c_size_t, [c_i, c_i, c_i, c_i])
 _sig("cr_score_topk", c_i, [C.POINTER(TopkDesc), c_p])
 _sig("cr_topk_index_bytes", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_topk_index_build", c_i, [c_p, c_i, c_i, c_i, c_p, C.c_size_t, c_p])
+_sig("cr_topk_index_gather", c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, C.c_size_t, c_p])
 _sig("cr_softmax_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_softmax_ce", c_i, [C.POINTER(SoftmaxCeDesc), c_p])
 _sig("cr_sampled_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
@@ -260,7 +261,7 @@ EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "
            "cr_head_fwd_bwd", "cr_head_fwd_bwd_ln", "cr_stack_fwd_head_supported", "cr_stack_fwd_head", "cr_test_logits", "cr_adam_step", "cr_reduce_slabs", "cr_l2_penalty", "cr_graph_begin", "cr_graph_end", "cr_graph_launch",
            "cr_graph_destroy", "cr_sampler_create", "cr_sampler_next", "cr_sampler_destroy",
            "cr_tgrad_geometry", "cr_batch_index_layout", "cr_index_builder_create", "cr_index_build", "cr_index_builder_destroy", "cr_table_grad",
-           "cr_score_topk_workspace", "cr_score_topk", "cr_topk_index_bytes", "cr_topk_index_build", "cr_softmax_ce_workspace", "cr_softmax_ce",
+           "cr_score_topk_workspace", "cr_score_topk", "cr_topk_index_bytes", "cr_topk_index_build", "cr_topk_index_gather", "cr_softmax_ce_workspace", "cr_softmax_ce",
            "cr_sampled_ce_workspace", "cr_sampled_ce", "cr_gbce_workspace", "cr_gbce"]
 
 lib = _lib

@@ -238,24 +238,44 @@ class _Model(object):
         return ItemIndex.build(self._owner.p("item_emb"), precision, version=self._param_version)
 
     def _check_index(self, index):
+        """index: None, an ItemIndex or an ItemSubset (its parent_V is the table it refers to)."""
         if index is None:
             return
-        if (index.V, index.D) != (self.itemnum + 1, self._owner.D):
+        V = getattr(index, "parent_V", None) or index.V
+        if (V, index.D) != (self.itemnum + 1, self._owner.D):
             raise ValueError("index of a [%d, %d] table, the model's item table is [%d, %d]"
-                             % (index.V, index.D, self.itemnum + 1, self._owner.D))
+                             % (V, index.D, self.itemnum + 1, self._owner.D))
         if index.version is not None and index.version != self._param_version:
             raise RuntimeError("stale index: built at parameter version %d, the model is at %d (build_item_index() again)"
                                % (index.version, self._param_version))
 
-    def similar_items(self, ids, k=10, index=None):
+    def _allowed(self, allow, index):
+        """What recommend / similar_items search: `index` itself without allow; with allow (an ItemSubset, or an iterable of item ids)
+        the ItemSubset -- gathered out of `index` when there is one, else from the item table's rows."""
+        from .index import ItemSubset
+        self._check_index(index)
+        if allow is None:
+            return index
+        if isinstance(allow, ItemSubset):
+            self._check_index(allow)
+            return allow
+        if index is not None:
+            if isinstance(index, ItemSubset):
+                raise ValueError("allow= with index= an ItemSubset: pass one subset")
+            return index.subset(allow)
+        return ItemSubset.build(self._owner.p("item_emb"), allow, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3",
+                                version=self._param_version)
+
+    def similar_items(self, ids, k=10, index=None, allow=None):
         """The k items whose table rows have the largest dot product with each given item's own row (the model's geometry: the scores
         of recommend with the item's vector as the query), the item itself left out.  Returns numpy (ids [n, k], scores [n, k]).
-        index: an ItemIndex of the table to search instead of one built for this call."""
+        index: an ItemIndex of the table to search instead of one built for this call.  allow: an iterable of item ids or an
+        ItemSubset -- the k most similar among those items only (one set for every row)."""
         from .index import ItemIndex
         ids = np.asarray(ids, np.int64).ravel()
         if ids.size == 0 or ids.min() < 1 or ids.max() > self.itemnum:
             raise ValueError("ids must be item ids in 1 .. %d" % self.itemnum)
-        self._check_index(index)
+        index = self._allowed(allow, index)
         table = self._owner.p("item_emb")
         if index is None:
             index = ItemIndex.build(table, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3")
@@ -263,14 +283,17 @@ class _Model(object):
         return index.search(q, int(k), exclude=[[int(i)] for i in ids])
 
     def recommend(self, u, seq, k=10, timeseq=None, hours_seq=None, days_seq=None, exclude="history", return_scores=True,
-                  targets=None, index=None):
+                  targets=None, index=None, allow=None):
         """The k best items of the whole catalogue for each row of a batch (the last position's scores against every item row,
         sasrec.py:93-97 extended from a candidate list to the table; castrec.h cr_score_topk).  exclude: "history" (the nonzero ids
         of each row of seq), None, or one iterable of ids per row.  Returns numpy (ids [B, k], scores [B, k]) -- ids only when
         return_scores is False -- and, with targets ([B] ids), a third array: each target's 0-based rank among the eligible items
         (-1 for an excluded target).  Rows with fewer than k eligible items end in id 0, score -inf.  index: an ItemIndex of the item
-        table (build_item_index): same results, the table's rows are not converted again."""
-        self._check_index(index)
+        table (build_item_index): same results, the table's rows are not converted again.  allow: an iterable of item ids or an
+        ItemSubset (castrec_amd.index) -- the best k among those items only, one set shared by every row (per-row masks are not
+        supported); it combines with exclude, a target outside it has rank -1 and ranks count the set's eligible items.  With an
+        iterable the subset is gathered for this call (out of index when given): keep an ItemSubset to reuse it."""
+        index = self._allowed(allow, index)
         seq = np.asarray(seq)
         if seq.ndim == 1:
             seq = seq[None]

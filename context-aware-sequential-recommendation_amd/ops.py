@@ -189,6 +189,36 @@ def topk_index_build(table, precision=L.PREC_BF16X3, out=None):
     return out
 
 
+def topk_index_gather(ids, precision=L.PREC_BF16X3, table=None, index=None, index_precision=None, V=None, D=None, out=None):
+    """cr_topk_index_gather: the index of {0; source row ids[0]; ...} as a uint8 CUDA tensor.  ids: an int32 CUDA tensor [n] of ids in
+    1 .. V-1.  The source is `table` (a contiguous float32 CUDA tensor [V, D]) or `index` (a uint8 CUDA tensor from topk_index_build
+    of a [V, D] table, built with index_precision) -- exactly one."""
+    _i32(ids, "ids")
+    if (table is None) == (index is None):
+        raise ValueError("topk_index_gather takes exactly one source: table or index")
+    if table is not None:
+        _f32(table, "table")
+        if table.dim() != 2 or not table.is_contiguous():
+            raise ValueError("table must be a contiguous [V, D] tensor")
+        V, D = table.shape
+        index_precision = 0
+    else:
+        if index.dtype != torch.uint8 or not index.is_cuda or not index.is_contiguous():
+            raise TypeError("index must be a contiguous uint8 CUDA tensor")
+        index_precision = int(precision if index_precision is None else index_precision)
+        if index.numel() != topk_index_bytes(V, D, index_precision):
+            raise ValueError("index of %d bytes is not an index of V=%d D=%d precision=%d" % (index.numel(), V, D, index_precision))
+    if ids.dim() != 1 or not ids.is_contiguous() or ids.numel() < 1:
+        raise ValueError("ids must be a contiguous [n] tensor, n >= 1")
+    n = ids.numel()
+    nb = topk_index_bytes(n + 1, D, precision)
+    if out is None:
+        out = torch.empty(nb, dtype=torch.uint8, device=ids.device)
+    L.call("cr_topk_index_gather", _p(table), _p(index), index_precision, V, D, ids.data_ptr(), n, precision, out.data_ptr(), out.numel(),
+           _stream())
+    return out
+
+
 def softmax_ce_workspace_bytes(M, V, D):
     n = L.lib.cr_softmax_ce_workspace(M, V, D)
     if n == 0:

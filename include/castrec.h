@@ -490,6 +490,18 @@ int cr_score_topk(const cr_topk_desc* d, void* stream);
 size_t cr_topk_index_bytes(int V, int D, int precision);
 int cr_topk_index_build(const float* table, int V, int D, int precision, void* index, size_t index_bytes, void* stream);
 
+/* ---- gathered sub-index: a shared candidate subset as an index of its own (csrc/cr_topk.hip) ---------------------------
+ * "The best K among these items" for a whole batch: gather the allowed rows once into a compact index, search that with
+ * cr_score_topk (V = n + 1) and map the returned local ids back through ids.  A row's fragments depend on that row alone, so
+ * out_index: the index of the [n + 1, D] table {0; src row ids[0]; ...; src row ids[n-1]}, with the bytes cr_topk_index_build
+ * gives on that table.  Source: `table` ([V, D] fp32) or `index` (an index of it, of index_precision) -- exactly one non-NULL.
+ * ids: device int32 [n], each in 1 .. V-1 (an id outside is read as row 0: a zero row; callers validate).
+ * out_bytes >= cr_topk_index_bytes(n + 1, D, precision).  From an index: precision == index_precision, or CR_PREC_BF16 out of a
+ * bf16x3 index (its hi plane alone).  One asynchronous launch, a wave per destination tile; ascending ids keep the order of the
+ * global ids, so the tie rule of a search carries over.  Checked before any device call, as everything else. */
+int cr_topk_index_gather(const float* table, const void* index, int index_precision, int V, int D,
+                         const int32_t* ids, int n, int precision, void* out_index, size_t out_bytes, void* stream);
+
 /* ---- full-catalogue softmax cross-entropy (csrc/cr_ce.hip) ----------------------------------------------------------
  * The training objective over the whole item table, an alternative to cr_head_fwd_bwd's one-negative BCE.  Rows m = 0 .. M-1,
  * h_m = seq_emb row m, E = table [V, D], istarget_m = (pos[m] != 0):
