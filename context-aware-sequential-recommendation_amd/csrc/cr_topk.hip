@@ -17,14 +17,15 @@
 // order in which candidates reached the buffer; the chunk partition is fixed by the shape; counts are integers.
 // One MFMA shape in this file (build.py ISA_CHECKED): v_mfma_f32_16x16x32_bf16.
 //
-// Item index (castrec.h cr_topk_index_build, cr_topk_desc.index): the catalogue as the A fragments the sweep forms from the table, made
-// once by k_topk_index_build with the same tk_row_issue / tk_row_finish and stored in fragment order -- a wave's 64 lanes of one
-// (tile of 16 rows, k-step) are 1 KB contiguous, the lo halves a second plane.  The IDX instantiations of both kernels load those
-// fragments (whole tiles in the sweep, one row per lane for the targets and the excluded rows) where the others load, mask and split
-// table rows; everything after the A operand is the same code, so a score has the same bits either way.
-//
-// Gathered sub-index (castrec.h cr_topk_index_gather): a row's fragments depend on that row alone, so the index of a subset of the rows
-// is made by copying them (k_topk_index_gather, from an index or from the table); a search of it is the two launches above on fewer rows.
+// Row source (TkSrc, tk_source): where an item row's A fragments come from.  Either the fp32 table -- rows loaded, masked past D and
+// split by cr_bf16.hpp's tk_row_issue / tk_row_finish -- or (IDX) an item index (castrec.h cr_topk_index_build, cr_topk_desc.index):
+// those same fragments made once and stored in fragment order, a wave's 64 lanes of one (tile of 16 rows, k-step) 1 KB contiguous, the
+// lo halves a second plane.  One row per lane -- targets, excluded rows, the rows an index is written from -- comes from tk_src_row;
+// the sweep's tile, one round ahead, is spelled out in its round loop (issue / finish of table rows, or tk_idx_tile): that keeps the
+// loop's instruction sequence what it was measured with; as a pair of functions it is scheduled differently, not measurably slower
+// (DESIGN.md section 10).  Everything after the A operand is the same code, so a score has the same bits from either source.  A
+// row's fragments depend on that row alone: k_topk_index_write makes the index of a table from rows 16 tile + li and a gathered
+// sub-index (castrec.h cr_topk_index_gather) from rows ids[]; a search of it is the two launches above on fewer rows.
 #include <algorithm>
 
 #include "cr_bf16.hpp"
@@ -35,10 +36,20 @@ constexpr int TK_CAP = 128;                 // candidate buffer per query; a rou
 constexpr int TK_PAD = 0x7fffffff;          // id of an empty list entry (score -inf): worse than every item
 constexpr int TK_MAX_CHUNKS = 256;
 
+// The row source: the fp32 table [V, D], or (IDX kernels) its index in 16-byte groups, the lo plane `plane` groups after the hi plane
+// (unread by a plain search).  Made by tk_source alone, which leaves no member unset for either kind of kernel.
+struct TkSrc {
+    const float* table;
+    const bf8* idx;
+    int64_t plane;
+    int n_tiles;
+    int V, D;
+};
+
 struct TkArgs {
     const float* q; int64_t ldq;
-    const float* table;
-    int V, D, B, K;
+    TkSrc src;
+    int B, K;
     const int64_t* off;                     // device copy of the CSR offsets, or null
     const int32_t* excl;
     const int32_t* tgt;
@@ -49,15 +60,6 @@ struct TkArgs {
     int chunk, n_chunks;
 };
 
-// the index forms: the blob in 16-byte groups, the lo plane `plane` groups after the hi plane (unused by a plain index)
-struct TkIdxArgs : TkArgs {
-    const bf8* idx;
-    int64_t plane;
-    int n_tiles;
-};
-template <bool IDX>
-using TkA = std::conditional_t<IDX, TkIdxArgs, TkArgs>;
-
 // a better than b: higher score, equal scores -> smaller id (empty entries carry TK_PAD, the largest id)
 __device__ __forceinline__ bool tk_better(float as, int ai, float bs, int bi) { return as > bs || (as == bs && ai < bi); }
 
@@ -66,28 +68,46 @@ __device__ __forceinline__ bool tk_better(float as, int ai, float bs, int bi) { 
 // A fragments of the 16 rows of tile `tile` from the index: group ((h n_tiles + tile) NK + ks) 64 + lane.  A tile past the table (the
 // idle waves of a chunk's last round) reads tile 0: its ids are not eligible, its scores are dropped.
 template <int NK, bool SPLIT>
-__device__ __forceinline__ void tk_idx_tile(const TkIdxArgs& a, int tile, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
-    const bf8* p = a.idx + (int64_t)(tile < a.n_tiles ? tile : 0) * (NK * 64) + (threadIdx.x & 63);
+__device__ __forceinline__ void tk_idx_tile(const TkSrc& s, int tile, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
+    const bf8* p = s.idx + (int64_t)(tile < s.n_tiles ? tile : 0) * (NK * 64) + (threadIdx.x & 63);
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks) {
         hi[ks] = p[ks * 64];
-        if (SPLIT) lo[ks] = p[a.plane + ks * 64];
+        if (SPLIT) lo[ks] = p[s.plane + ks * 64];
     }
 }
-// One row per lane (li), as tk_row_issue / tk_row_finish give it: 16-byte gathers; a lane without a row gets zeros.
+// ... and the wave's store of tile `tile` of an index whose lo plane lies `plane` groups after the hi plane
 template <int NK, bool SPLIT>
-__device__ __forceinline__ void tk_idx_row(const TkIdxArgs& a, int row, bool rok, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
-    const int lg = (threadIdx.x & 63) >> 4, r = rok ? row : 0;
-    const bf8* p = a.idx + (int64_t)(r >> 4) * (NK * 64) + (lg * 16 + (r & 15));
-    const bf8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+__device__ __forceinline__ void tk_idx_store(bf8* idx, int64_t plane, int tile, const bf8 (&hi)[NK], const bf8 (&lo)[NK]) {
+    bf8* p = idx + (int64_t)tile * (NK * 64) + (threadIdx.x & 63);
 #pragma unroll
     for (int ks = 0; ks < NK; ++ks) {
-        const bf8 h = p[ks * 64];
-        hi[ks] = rok ? h : z;
-        if (SPLIT) {
-            const bf8 l = p[a.plane + ks * 64];
-            lo[ks] = rok ? l : z;
+        p[ks * 64] = hi[ks];
+        if (SPLIT) p[plane + ks * 64] = lo[ks];
+    }
+}
+
+// The fragments of one row per lane (li): from the table as tk_row_issue / tk_row_finish give them, from the index by 16-byte gathers
+// of the same groups; a lane without a row (!rok) gets zeros.
+template <int NK, bool SPLIT, bool IDX>
+__device__ __forceinline__ void tk_src_row(const TkSrc& s, int row, bool rok, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
+    if constexpr (IDX) {
+        const int lg = (threadIdx.x & 63) >> 4, r = rok ? row : 0;
+        const bf8* p = s.idx + (int64_t)(r >> 4) * (NK * 64) + (lg * 16 + (r & 15));
+        const bf8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+        for (int ks = 0; ks < NK; ++ks) {
+            const bf8 h = p[ks * 64];
+            hi[ks] = rok ? h : z;
+            if (SPLIT) {
+                const bf8 l = p[s.plane + ks * 64];
+                lo[ks] = rok ? l : z;
+            }
         }
+    } else {
+        float v[NK][8];
+        tk_row_issue<NK>(v, s.table, s.D, row, rok, row == s.V - 1, s.D);
+        tk_row_finish<NK, SPLIT>(v, s.table, s.D, row, rok, row == s.V - 1, s.D, hi, lo);
     }
 }
 
@@ -180,7 +200,7 @@ __device__ void tk_fold(const TkLds& l, int qi, int n, int K, const TkArgs& a, i
 }
 
 template <int NK, int QB, bool SPLIT, bool IDX>
-__global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
+__global__ __launch_bounds__(256) void k_topk_sweep(TkArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int QT = 16 * QB;
     const int K = a.K;
@@ -188,7 +208,7 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int q0 = blockIdx.x * QT;
     const int nq = min(QT, a.B - q0);
-    const int c0 = blockIdx.y * a.chunk, c1 = min(a.V, c0 + a.chunk);
+    const int c0 = blockIdx.y * a.chunk, c1 = min(a.src.V, c0 + a.chunk);
 
     // the query tile as B fragments, once
     for (int qb = wave; qb < QB; qb += 4) {
@@ -196,8 +216,8 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
         const bool rok = row < a.B;
         float v[NK][8];
         bf8 h[NK], lo[NK];
-        tk_row_issue<NK>(v, a.q, a.ldq, row, rok, row == a.B - 1, a.D);
-        tk_row_finish<NK, SPLIT>(v, a.q, a.ldq, row, rok, row == a.B - 1, a.D, h, lo);
+        tk_row_issue<NK>(v, a.q, a.ldq, row, rok, row == a.B - 1, a.src.D);
+        tk_row_finish<NK, SPLIT>(v, a.q, a.ldq, row, rok, row == a.B - 1, a.src.D, h, lo);
 #pragma unroll
         for (int ks = 0; ks < NK; ++ks) {
             l.img_hi[(qb * NK + ks) * 64 + lane] = h[ks];
@@ -208,7 +228,7 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
     for (int i = threadIdx.x; i < QT; i += 256) {
         int t = -1;
         if (a.tgt && i < nq) t = a.tgt[q0 + i];
-        l.tq[i] = (t >= 1 && t < a.V) ? t : -1;
+        l.tq[i] = (t >= 1 && t < a.src.V) ? t : -1;
         l.cnt[i] = 0;
         l.thr[i] = i < nq ? -INFINITY : INFINITY;          // a query row past B takes no candidates
         l.st[i] = 0.0f;
@@ -220,13 +240,7 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
         for (int qb = wave; qb < QB; qb += 4) {
             const int t = l.tq[qb * 16 + li];
             bf8 ah[NK], al[NK], bh[NK], bl[NK];
-            if constexpr (IDX) {
-                tk_idx_row<NK, SPLIT>(a, t, t > 0, ah, al);
-            } else {
-                float v[NK][8];
-                tk_row_issue<NK>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D);
-                tk_row_finish<NK, SPLIT>(v, a.table, a.D, t, t > 0, t == a.V - 1, a.D, ah, al);
-            }
+            tk_src_row<NK, SPLIT, IDX>(a.src, t, t > 0, ah, al);
 #pragma unroll
             for (int ks = 0; ks < NK; ++ks) {
                 bh[ks] = l.img_hi[(qb * NK + ks) * 64 + lane];
@@ -249,10 +263,10 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
     float v[NK][8];                                        // the round ahead: table rows in flight, or (IDX) the fragments themselves
     bf8 nh[NK], nl[NK];
     if constexpr (IDX) {
-        tk_idx_tile<NK, SPLIT>(a, (c0 + wave * 16) >> 4, nh, nl);           // chunks start at multiples of 64 rows
+        tk_idx_tile<NK, SPLIT>(a.src, (c0 + wave * 16) >> 4, nh, nl);       // chunks start at multiples of 64 rows
     } else {
         const int row = c0 + wave * 16 + li;
-        tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
+        tk_row_issue<NK>(v, a.src.table, a.src.D, row, row < c1, row == a.src.V - 1, a.src.D);
     }
     for (int round = 0; round < n_rounds; ++round) {
         const int it0 = c0 + round * 64 + wave * 16;
@@ -263,15 +277,15 @@ __global__ __launch_bounds__(256) void k_topk_sweep(TkA<IDX> a) {
                 ah[ks] = nh[ks];
                 if (SPLIT) al[ks] = nl[ks];
             }
-            if (round + 1 < n_rounds) tk_idx_tile<NK, SPLIT>(a, (it0 + 64) >> 4, nh, nl);
+            if (round + 1 < n_rounds) tk_idx_tile<NK, SPLIT>(a.src, (it0 + 64) >> 4, nh, nl);
         } else {
             {
                 const int row = it0 + li;
-                tk_row_finish<NK, SPLIT>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D, ah, al);
+                tk_row_finish<NK, SPLIT>(v, a.src.table, a.src.D, row, row < c1, row == a.src.V - 1, a.src.D, ah, al);
             }
             if (round + 1 < n_rounds) {
                 const int row = it0 + 64 + li;
-                tk_row_issue<NK>(v, a.table, a.D, row, row < c1, row == a.V - 1, a.D);
+                tk_row_issue<NK>(v, a.src.table, a.src.D, row, row < c1, row == a.src.V - 1, a.src.D);
             }
         }
 #pragma unroll
@@ -337,7 +351,7 @@ __device__ __forceinline__ void tk_wave_best(float& s, int& id) {
 }
 
 template <int NK, bool SPLIT, bool IDX>
-__global__ __launch_bounds__(256) void k_topk_merge(TkA<IDX> a) {
+__global__ __launch_bounds__(256) void k_topk_merge(TkArgs a) {
     __shared__ float sc[4][16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
     const int b = blockIdx.x * 4 + wave;
@@ -385,7 +399,7 @@ __global__ __launch_bounds__(256) void k_topk_merge(TkA<IDX> a) {
     for (int o = 32; o > 0; o >>= 1) raw += __shfl_xor(raw, o, 64);
     bool hit_t = false;
     for (int64_t j = e0 + lane; j < e1; j += 64) hit_t |= a.excl[j] == t;
-    const bool bad = !(t >= 1 && t < a.V) || __any(hit_t);
+    const bool bad = !(t >= 1 && t < a.src.V) || __any(hit_t);
     if (bad) {
         if (lane == 0) a.rank[b] = -1;
         return;
@@ -396,20 +410,14 @@ __global__ __launch_bounds__(256) void k_topk_merge(TkA<IDX> a) {
     if (e1 > e0) {
         float qv[NK][8];
         bf8 bh[NK], bl[NK];
-        tk_row_issue<NK>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.D);
-        tk_row_finish<NK, SPLIT>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.D, bh, bl);
+        tk_row_issue<NK>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.src.D);
+        tk_row_finish<NK, SPLIT>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.src.D, bh, bl);
         for (int64_t p0 = e0; p0 < e1; p0 += 16) {
             const int64_t p = p0 + li;
             const int e = p < e1 ? a.excl[p] : 0;
-            const bool rok = e >= 1 && e < a.V;
+            const bool rok = e >= 1 && e < a.src.V;
             bf8 ah[NK], al[NK];
-            if constexpr (IDX) {
-                tk_idx_row<NK, SPLIT>(a, e, rok, ah, al);
-            } else {
-                float v[NK][8];
-                tk_row_issue<NK>(v, a.table, a.D, e, rok, e == a.V - 1, a.D);
-                tk_row_finish<NK, SPLIT>(v, a.table, a.D, e, rok, e == a.V - 1, a.D, ah, al);
-            }
+            tk_src_row<NK, SPLIT, IDX>(a.src, e, rok, ah, al);
             const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
             if (li == 0) {
 #pragma unroll
@@ -432,62 +440,51 @@ __global__ __launch_bounds__(256) void k_topk_merge(TkA<IDX> a) {
     if (lane == 0) a.rank[b] = raw - sub;
 }
 
-// The index of a table: a wave per tile of 16 rows, the fragments exactly as the sweep forms them (rows >= V and columns >= D: +0).
-template <int NK, bool SPLIT>
-__global__ __launch_bounds__(256) void k_topk_index_build(const float* table, int V, int D, bf8* idx, int64_t plane, int n_tiles) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15;
-    const int tile = blockIdx.x * 4 + wave;
-    if (tile >= n_tiles) return;                           // wave-uniform
-    const int row = tile * 16 + li;
-    float v[NK][8];
-    bf8 h[NK], lo[NK];
-    tk_row_issue<NK>(v, table, D, row, row < V, row == V - 1, D);
-    tk_row_finish<NK, SPLIT>(v, table, D, row, row < V, row == V - 1, D, h, lo);
-    bf8* p = idx + (int64_t)tile * (NK * 64) + lane;
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-        p[ks * 64] = h[ks];
-        if (SPLIT) p[plane + ks * 64] = lo[ks];
-    }
-}
-
-// The index of the table {0; source row ids[0]; ...; source row ids[n - 1]} (castrec.h cr_topk_index_gather): a wave per destination
-// tile, lane (li, lg) holds destination row 16 tile + li = source row ids[16 tile + li - 1].  A lane without a source row (destination
-// row 0, rows > n of the last tile, an id outside 1 .. V-1) stores +0.  From an index (IDX) the row's 16-byte groups are copied as
-// tk_idx_row reads them; from the table the row is masked and split as the build does it.  Either way the build's store, so the bytes
-// are the build's on the gathered table.
+// Writing an index (castrec.h cr_topk_index_build, cr_topk_index_gather): a wave per destination tile, lane (li, lg) stores the
+// fragments of its source row where the sweep's lane reads destination row r = 16 tile + li.  Without ids the source row is r itself
+// (the build: rows >= V and columns >= D are +0); with ids it is ids[r - 1], the index of the table {0; row ids[0]; ...; row
+// ids[n - 1]} -- no source row, so +0, for r = 0, r > n and an id outside 1 .. V-1.  A row's fragments depend on that row alone, so
+// the gathered bytes are the build's on the gathered table, whether they come from the table or (IDX) from an index of it.
 template <int NK, bool SPLIT, bool IDX>
-__global__ __launch_bounds__(256) void k_topk_index_gather(const float* table, const bf8* src, int64_t src_plane, int V, int D,
-                                                           const int32_t* ids, int n, bf8* idx, int64_t plane, int n_tiles) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15;
-    const int tile = blockIdx.x * 4 + wave;
+__global__ __launch_bounds__(256) void k_topk_index_write(TkSrc s, const int32_t* ids, int n, bf8* idx, int64_t plane, int n_tiles) {
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= n_tiles) return;                           // wave-uniform
-    const int j = tile * 16 + li - 1;
-    const int id = (j >= 0 && j < n) ? ids[j] : 0;
-    const bool rok = id >= 1 && id < V;
-    const int row = rok ? id : 0;
+    const int r = tile * 16 + (threadIdx.x & 15);
+    const int row = !ids ? r : (r >= 1 && r <= n) ? ids[r - 1] : 0;
+    const bool rok = row < s.V && (!ids || row >= 1);
     bf8 h[NK], lo[NK];
-    if constexpr (IDX) {
-        TkIdxArgs a;
-        a.idx = src;
-        a.plane = src_plane;
-        tk_idx_row<NK, SPLIT>(a, row, rok, h, lo);
-    } else {
-        float v[NK][8];
-        tk_row_issue<NK>(v, table, D, row, rok, row == V - 1, D);
-        tk_row_finish<NK, SPLIT>(v, table, D, row, rok, row == V - 1, D, h, lo);
-    }
-    bf8* p = idx + (int64_t)tile * (NK * 64) + lane;
-#pragma unroll
-    for (int ks = 0; ks < NK; ++ks) {
-        p[ks * 64] = h[ks];
-        if (SPLIT) p[plane + ks * 64] = lo[ks];
-    }
+    tk_src_row<NK, SPLIT, IDX>(s, row, rok, h, lo);        // (a lane without a row reads nothing at `row`)
+    tk_idx_store<NK, SPLIT>(idx, plane, tile, h, lo);
 }
 
 // planes of an index of `precision`: 2 (hi + lo; CR_PREC_F32 as CR_PREC_BF16X3), 1 (plain bf16), 0 for anything else
 int tk_index_planes(int precision) {
     return (precision == CR_PREC_BF16X3 || precision == CR_PREC_F32) ? 2 : precision == CR_PREC_BF16 ? 1 : 0;
+}
+
+// an index of a [V, D] table: k-steps, tiles of 16 rows, and the 16-byte groups of one plane
+struct TkIdxGeom {
+    int NK, n_tiles;
+    int64_t plane;
+};
+TkIdxGeom tk_index_geom(int V, int D) {
+    TkIdxGeom g;
+    g.NK = tk_nk(D);
+    g.n_tiles = (int)(((int64_t)V + 15) / 16);
+    g.plane = (int64_t)g.n_tiles * g.NK * 64;
+    return g;
+}
+TkSrc tk_source(const float* table, const void* index, int V, int D) {
+    const TkIdxGeom g = tk_index_geom(V, D);
+    return TkSrc{table, static_cast<const bf8*>(index), g.plane, g.n_tiles, V, D};
+}
+
+// what every entry point `who` asks of a table's shape and of a precision
+int tk_check_shape(const char* who, int V, int D, int precision) {
+    CR_REQUIRE(D >= 8 && D <= 256, "%s: D=%d outside 8 .. 256", who, D);
+    CR_REQUIRE(V >= 1, "%s: V=%d must be >= 1", who, V);
+    CR_REQUIRE(tk_index_planes(precision) != 0, "%s: unknown precision %d", who, precision);
+    return CR_OK;
 }
 
 struct TkGeom {
@@ -519,7 +516,7 @@ size_t tk_workspace(int B, const TkGeom& g, int K) {
 }
 
 template <int NK, bool SPLIT, bool IDX>
-void tk_launch(const TkA<IDX>& a, const TkGeom& g, hipStream_t st) {
+void tk_launch(const TkArgs& a, const TkGeom& g, hipStream_t st) {
     const dim3 grid(g.n_qt, g.n_chunks);
     if (g.QB == 4) hipLaunchKernelGGL((k_topk_sweep<NK, 4, SPLIT, IDX>), grid, dim3(256), g.lds, st, a);
     else if (g.QB == 2) hipLaunchKernelGGL((k_topk_sweep<NK, 2, SPLIT, IDX>), grid, dim3(256), g.lds, st, a);
@@ -527,28 +524,31 @@ void tk_launch(const TkA<IDX>& a, const TkGeom& g, hipStream_t st) {
     hipLaunchKernelGGL((k_topk_merge<NK, SPLIT, IDX>), dim3((a.B + 3) / 4), dim3(256), 0, st, a);
 }
 
+// the index of `rows` rows in `planes` planes, written from src: row for row (ids NULL) or from rows ids[0 .. n-1] behind a zero row
+void tk_index_write(const TkSrc& src, const int32_t* ids, int n, void* out, int rows, int planes, hipStream_t st) {
+    const TkIdxGeom g = tk_index_geom(rows, src.D);
+    const dim3 grid((g.n_tiles + 3) / 4);
+    bf8* idx = static_cast<bf8*>(out);
+    tk_dispatch(g.NK, planes == 2, [&](auto nk, auto sp) {
+        if (src.idx) hipLaunchKernelGGL((k_topk_index_write<nk, sp, true>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
+        else hipLaunchKernelGGL((k_topk_index_write<nk, sp, false>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
+    });
+}
+
 }  // namespace
 
 extern "C" size_t cr_topk_index_bytes(int V, int D, int precision) {
     const int planes = tk_index_planes(precision);
     if (V < 1 || D < 8 || D > 256 || planes == 0) return 0;
-    return (size_t)planes * (((size_t)V + 15) / 16) * (size_t)tk_nk(D) * 1024;
+    return (size_t)planes * (size_t)tk_index_geom(V, D).plane * 16;
 }
 
 extern "C" int cr_topk_index_build(const float* table, int V, int D, int precision, void* index, size_t index_bytes, void* stream) {
     CR_REQUIRE(table && index, "cr_topk_index_build: NULL table or index");
-    CR_REQUIRE(D >= 8 && D <= 256, "cr_topk_index_build: D=%d outside 8 .. 256", D);
-    CR_REQUIRE(V >= 1, "cr_topk_index_build: V=%d must be >= 1", V);
-    CR_REQUIRE(tk_index_planes(precision) != 0, "cr_topk_index_build: unknown precision %d", precision);
+    if (const int rc = tk_check_shape("cr_topk_index_build", V, D, precision)) return rc;
     const size_t need = cr_topk_index_bytes(V, D, precision);
     CR_REQUIRE(index_bytes >= need, "cr_topk_index_build: index of %zu bytes, cr_topk_index_bytes says %zu", index_bytes, need);
-    const int NK = tk_nk(D), n_tiles = (int)(((int64_t)V + 15) / 16);
-    const int64_t plane = (int64_t)n_tiles * NK * 64;
-    bf8* idx = static_cast<bf8*>(index);
-    hipStream_t st = cr_stream(stream);
-    tk_dispatch(NK, tk_index_planes(precision) == 2, [&](auto nk, auto sp) {
-        hipLaunchKernelGGL((k_topk_index_build<nk, sp>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, V, D, idx, plane, n_tiles);
-    });
+    tk_index_write(tk_source(table, nullptr, V, D), nullptr, 0, index, V, tk_index_planes(precision), cr_stream(stream));
     return cr_check_launch("cr_topk_index_build");
 }
 
@@ -557,34 +557,18 @@ extern "C" int cr_topk_index_gather(const float* table, const void* index, int i
     CR_REQUIRE((table != nullptr) != (index != nullptr), "cr_topk_index_gather: exactly one source, table or index, must be non-NULL (%s)",
                table ? "both given" : "both NULL");
     CR_REQUIRE(ids && out_index, "cr_topk_index_gather: NULL ids or out_index");
-    CR_REQUIRE(D >= 8 && D <= 256, "cr_topk_index_gather: D=%d outside 8 .. 256", D);
-    CR_REQUIRE(V >= 1, "cr_topk_index_gather: V=%d must be >= 1", V);
+    if (const int rc = tk_check_shape("cr_topk_index_gather", V, D, precision)) return rc;
     CR_REQUIRE(n >= 1 && n < 0x7fffffff, "cr_topk_index_gather: n=%d must be >= 1 (and n + 1 an int)", n);
     const int planes = tk_index_planes(precision);
-    CR_REQUIRE(planes != 0, "cr_topk_index_gather: unknown precision %d", precision);
-    int64_t src_plane = 0;
     if (index) {
         const int sp = tk_index_planes(index_precision);
         CR_REQUIRE(sp != 0, "cr_topk_index_gather: unknown index_precision %d", index_precision);
         CR_REQUIRE(planes <= sp, "cr_topk_index_gather: a plain bf16 index has no lo plane for a sub-index of precision %d", precision);
-        src_plane = (((int64_t)V + 15) / 16) * tk_nk(D) * 64;
     }
     const size_t need = cr_topk_index_bytes(n + 1, D, precision);
     CR_REQUIRE(out_bytes >= need, "cr_topk_index_gather: out_index of %zu bytes, cr_topk_index_bytes(n + 1 = %d) says %zu", out_bytes,
                n + 1, need);
-    const int NK = tk_nk(D), n_tiles = (int)(((int64_t)n + 1 + 15) / 16);
-    const int64_t plane = (int64_t)n_tiles * NK * 64;
-    bf8* idx = static_cast<bf8*>(out_index);
-    const bf8* src = static_cast<const bf8*>(index);
-    hipStream_t st = cr_stream(stream);
-    tk_dispatch(NK, planes == 2, [&](auto nk, auto sp) {
-        if (index)
-            hipLaunchKernelGGL((k_topk_index_gather<nk, sp, true>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, src, src_plane, V, D,
-                               ids, n, idx, plane, n_tiles);
-        else
-            hipLaunchKernelGGL((k_topk_index_gather<nk, sp, false>), dim3((n_tiles + 3) / 4), dim3(256), 0, st, table, src, src_plane, V, D,
-                               ids, n, idx, plane, n_tiles);
-    });
+    tk_index_write(tk_source(table, index, V, D), ids, n, out_index, n + 1, planes, cr_stream(stream));
     return cr_check_launch("cr_topk_index_gather");
 }
 
@@ -597,15 +581,13 @@ extern "C" size_t cr_score_topk_workspace(int B, int V, int D, int K) {
 extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
     CR_REQUIRE(d, "cr_score_topk: NULL descriptor");
     CR_REQUIRE(d->K >= 1 && d->K <= CR_TOPK_MAX, "cr_score_topk: K=%d outside 1 .. CR_TOPK_MAX (%d)", d->K, CR_TOPK_MAX);
-    CR_REQUIRE(d->D >= 8 && d->D <= 256, "cr_score_topk: D=%d outside 8 .. 256", d->D);
     CR_REQUIRE(d->B >= 1 && d->V >= 1, "cr_score_topk: B=%d, V=%d must be >= 1", d->B, d->V);
+    if (const int rc = tk_check_shape("cr_score_topk", d->V, d->D, d->precision)) return rc;
     CR_REQUIRE(d->ld >= d->D, "cr_score_topk: ld=%d < D=%d", d->ld, d->D);
     if (d->index) CR_REQUIRE(d->query, "cr_score_topk: NULL query");
     else CR_REQUIRE(d->query && d->table, "cr_score_topk: NULL query or table");
     CR_REQUIRE(d->top_ids && d->top_scores, "cr_score_topk: NULL output (top_ids / top_scores)");
     CR_REQUIRE(!d->targets || d->rank, "cr_score_topk: targets given but rank is NULL");
-    CR_REQUIRE(d->precision == CR_PREC_F32 || d->precision == CR_PREC_BF16X3 || d->precision == CR_PREC_BF16,
-               "cr_score_topk: unknown precision %d", d->precision);
     if (d->index) {
         const int planes = tk_index_planes(d->index_precision);
         CR_REQUIRE(planes != 0, "cr_score_topk: unknown index_precision %d", d->index_precision);
@@ -632,8 +614,8 @@ extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
     unsigned char* w = static_cast<unsigned char*>(d->workspace);
     const size_t nb = (size_t)g.n_chunks * d->B;
     TkArgs a;
-    a.q = d->query; a.ldq = d->ld; a.table = d->table;
-    a.V = d->V; a.D = d->D; a.B = d->B; a.K = d->K;
+    a.q = d->query; a.ldq = d->ld; a.src = tk_source(d->table, d->index, d->V, d->D);
+    a.B = d->B; a.K = d->K;
     a.off = nullptr;
     if (d->excl_off && d->excl_off[d->B] > d->excl_off[0]) {
         int64_t* off = reinterpret_cast<int64_t*>(w);
@@ -650,15 +632,9 @@ extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
     a.top_ids = d->top_ids; a.top_scores = d->top_scores; a.rank = d->rank;
     a.chunk = g.chunk; a.n_chunks = g.n_chunks;
     const bool split = d->precision != CR_PREC_BF16;       // CR_PREC_F32: the bf16x3 products (fp32-grade)
-    if (d->index) {
-        TkIdxArgs ia;
-        static_cast<TkArgs&>(ia) = a;
-        ia.idx = static_cast<const bf8*>(d->index);
-        ia.n_tiles = (int)(((int64_t)d->V + 15) / 16);
-        ia.plane = (int64_t)ia.n_tiles * g.NK * 64;
-        tk_dispatch(g.NK, split, [&](auto nk, auto sp) { tk_launch<nk, sp, true>(ia, g, st); });
-    } else {
-        tk_dispatch(g.NK, split, [&](auto nk, auto sp) { tk_launch<nk, sp, false>(a, g, st); });
-    }
+    tk_dispatch(g.NK, split, [&](auto nk, auto sp) {
+        if (d->index) tk_launch<nk, sp, true>(a, g, st);
+        else tk_launch<nk, sp, false>(a, g, st);
+    });
     return cr_check_launch("cr_score_topk");
 }

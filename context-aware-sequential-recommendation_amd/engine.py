@@ -1673,48 +1673,16 @@ class Engine:
         from it instead of the table, with the same bits.  castrec.h cr_score_topk.  index may also be an ItemSubset of the table:
         the best k among its items only -- ids, exclusions and targets stay global ids, a target outside the subset has rank -1 and
         ranks count the subset's eligible items."""
-        B, V, D = self.B, self.itemnum + 1, self.D
-        from .index import ItemSubset, excl_to_local, to_local
-        subset = index if isinstance(index, ItemSubset) else None
-        if subset is not None:
-            if (subset.parent_V, subset.D) != (V, D):
-                raise ValueError("subset of a [%d, %d] table, the engine's item table is [%d, %d]" % (subset.parent_V, subset.D, V, D))
-            m = subset._map                                   # the host copy of subset.ids
-            if excl_ids is not None and excl_off is not None:
-                excl_off, excl_ids = excl_to_local(m, excl_off, excl_ids.cpu().numpy() if torch.is_tensor(excl_ids) else excl_ids)
-            if targets is not None:
-                targets = to_local(m, targets.cpu().numpy() if torch.is_tensor(targets) else targets)
-            index, V = subset.index, subset.index.V
-        need = O.topk_workspace_bytes(B, V, D, int(k))
-        ws = getattr(self, "_topk_ws", None)
-        if ws is None or ws.numel() < need:
-            ws = self._topk_ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
-        if excl_ids is not None and not torch.is_tensor(excl_ids):
-            excl_ids = torch.from_numpy(np.ascontiguousarray(excl_ids, np.int32))
-        if excl_ids is not None:
-            excl_ids = excl_ids.to(self.dev, torch.int32).contiguous()
-            if excl_ids.numel() == 0:
-                excl_ids = None
-                excl_off = None
-        if targets is not None:
-            targets = torch.as_tensor(np.asarray(targets, np.int32) if not torch.is_tensor(targets) else targets).to(self.dev, torch.int32).contiguous()
-        ids = torch.empty(B, int(k), dtype=torch.int32, device=self.dev)
-        scores = torch.empty(B, int(k), dtype=torch.float32, device=self.dev)
-        rank = torch.empty(B, dtype=torch.int32, device=self.dev) if targets is not None else None
-        prec = L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3
-        se = self.seq_emb
-        ld = se.shape[1]
-        query = se[self.T - 1:]                           # row b of the queries: seq_emb row b * T + T - 1
-        if index is not None:
-            if (index.V, index.D) != (V, D):
-                raise ValueError("index of a [%d, %d] table, the engine's item table is [%d, %d]" % (index.V, index.D, V, D))
-            O.score_topk(query, self.T * ld, (V, D), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank,
-                         index=index.blob, index_precision=index.prec)
-            if subset is not None:
-                ids = subset.ids.to(self.dev)[ids.long()]     # local -> global; local 0 (fewer than k eligible) stays 0
-            return ids, scores, rank
-        O.score_topk(query, self.T * ld, self.p("item_emb"), B, int(k), prec, excl_off, excl_ids, targets, ws, ids, scores, rank)
-        return ids, scores, rank
+        from . import index as X
+        V, D = self.itemnum + 1, self.D
+        if isinstance(index, X.ItemSubset) and (index.parent_V, index.D) != (V, D):
+            raise ValueError("subset of a [%d, %d] table, the engine's item table is [%d, %d]" % (index.parent_V, index.D, V, D))
+        if isinstance(index, X.ItemIndex) and (index.V, index.D) != (V, D):
+            raise ValueError("index of a [%d, %d] table, the engine's item table is [%d, %d]" % (index.V, index.D, V, D))
+        ld = self.seq_emb.shape[1]
+        query = self.seq_emb[self.T - 1:]                 # row b of the queries: seq_emb row b * T + T - 1
+        return X.search(query, self.T * ld, self.B, k, self.p("item_emb") if index is None else index,
+                        L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3, self, excl_off, excl_ids, targets)
 
     # ---- parameter / gradient access (tests, checkpoints) ----------------------------------------
     def get_params(self):

@@ -85,6 +85,70 @@ def excl_to_local(sorted_ids, off, ids):
     return kept[off - off[0]], loc[keep].astype(np.int32)
 
 
+# ---- the one search path (ItemIndex.search, ItemSubset.search, Engine.topk) ---------------------------------------------------------
+def _host(x):
+    return x.cpu().numpy() if torch.is_tensor(x) else x
+
+
+def _dev_i32(x, dev):
+    return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, np.int32))).to(dev, torch.int32).contiguous()
+
+
+def search(query, ld, B, k, source, precision, owner, excl_off=None, excl_ids=None, targets=None):
+    """cr_score_topk, marshalled once: the k best items for the B fp32 query rows query + b * ld (a CUDA tensor's storage) out of
+    `source` -- the fp32 item table (a CUDA tensor [V, D]), an ItemIndex of it, or an ItemSubset (the best k among its items).
+    precision: the search arithmetic (L.PREC_*).  excl_off / excl_ids: an exclusion CSR (excl_csr) and targets: [B] ids, host or
+    device, all on global ids -- a subset's translation to its local ids and back happens here and nowhere else.  owner: the object
+    that keeps the workspace between calls (its _topk_ws).  Returns device tensors (ids [B, k] int32, scores [B, k] fp32, rank [B]
+    int32 or None for no targets)."""
+    dev, k = query.device, int(k)
+    subset = source if isinstance(source, ItemSubset) else None
+    if subset is not None:
+        excl_off, excl_ids = excl_to_local(subset._map, excl_off, _host(excl_ids))
+        if targets is not None:
+            targets = to_local(subset._map, _host(targets))
+        source = subset.index
+    if excl_ids is not None:
+        excl_ids = _dev_i32(excl_ids, dev)
+        if excl_ids.numel() == 0:                           # an empty exclusion list is no exclusion list
+            excl_off = excl_ids = None
+    if targets is not None:
+        targets = _dev_i32(targets, dev)
+    if torch.is_tensor(source):
+        (V, D), table, kw = source.shape, source, {}
+    else:
+        (V, D), kw = (source.V, source.D), dict(index=source.blob, index_precision=source.prec)
+        table = (V, D)
+    need = O.topk_workspace_bytes(B, V, D, k)
+    ws = getattr(owner, "_topk_ws", None)
+    if ws is None or ws.numel() < need:
+        ws = owner._topk_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ids = torch.empty(B, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev) if targets is not None else None
+    with torch.cuda.device(dev):
+        O.score_topk(query, ld, table, B, k, precision, excl_off, excl_ids, targets, ws, ids, scores, rank, **kw)
+        if subset is not None:
+            ids = subset.ids.to(dev)[ids.long()]            # local -> global; local 0 (fewer than k eligible) stays 0
+    return ids, scores, rank
+
+
+def _search_numpy(source, queries, k, exclude, targets, precision):
+    """ItemIndex.search and ItemSubset.search: queries (numpy or CUDA) and per-row exclusion lists in, numpy out."""
+    index = source.index if isinstance(source, ItemSubset) else source
+    if not index.blob.is_cuda:
+        raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to search")
+    q = queries if torch.is_tensor(queries) else torch.from_numpy(np.ascontiguousarray(queries, np.float32))
+    q = q.to(index.blob.device, torch.float32).contiguous()
+    if q.dim() != 2 or q.shape[1] != index.D:
+        raise ValueError("queries must be [B, %d], got %s" % (index.D, tuple(q.shape)))
+    B = q.shape[0]
+    top, sc, rk = search(q, index.D, B, k, source, index.prec if precision is None else _prec(precision), index, *excl_csr(exclude, B),
+                         targets=targets)
+    out = (top.cpu().numpy(), sc.cpu().numpy())
+    return out + (rk.cpu().numpy(),) if rk is not None else out
+
+
 class ItemIndex(object):
     """V, D: the table's shape; precision: "bf16x3" (hi + lo planes: serves every search precision) or "bf16" (hi only, half the bytes:
     plain-bf16 searches only); blob: the uint8 tensor of castrec.h's layout; version: the parameter version of the model that built it
@@ -96,7 +160,6 @@ class ItemIndex(object):
         if need == 0 or blob.numel() != need or blob.dtype != torch.uint8:
             raise ValueError("index blob of %d bytes (%s) does not fit V=%d D=%d precision=%s (%d bytes)"
                              % (blob.numel(), blob.dtype, self.V, self.D, self.precision, need))
-        self._ws = None
 
     @property
     def prec(self):
@@ -127,32 +190,7 @@ class ItemIndex(object):
         self.subset(allow).search(...) (keep the ItemSubset to search the same set again)."""
         if allow is not None:
             return self.subset(allow).search(queries, k, exclude=exclude, targets=targets, precision=precision)
-        if not self.blob.is_cuda:
-            raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to search")
-        dev = self.blob.device
-        q = queries if torch.is_tensor(queries) else torch.from_numpy(np.ascontiguousarray(queries, np.float32))
-        q = q.to(dev, torch.float32).contiguous()
-        if q.dim() != 2 or q.shape[1] != self.D:
-            raise ValueError("queries must be [B, %d], got %s" % (self.D, tuple(q.shape)))
-        B, k = q.shape[0], int(k)
-        off, ids = excl_csr(exclude, B)
-        if ids is not None and ids.size == 0:
-            off = ids = None
-        if ids is not None:
-            ids = torch.from_numpy(ids).to(dev)
-        if targets is not None:
-            targets = (targets if torch.is_tensor(targets) else torch.from_numpy(np.asarray(targets, np.int32))).to(dev, torch.int32).contiguous()
-        need = O.topk_workspace_bytes(B, self.V, self.D, k)
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        top = torch.empty(B, k, dtype=torch.int32, device=dev)
-        sc = torch.empty(B, k, dtype=torch.float32, device=dev)
-        rk = torch.empty(B, dtype=torch.int32, device=dev) if targets is not None else None
-        with torch.cuda.device(dev):
-            O.score_topk(q, self.D, (self.V, self.D), B, k, self.prec if precision is None else _prec(precision), off, ids, targets,
-                         self._ws, top, sc, rk, index=self.blob, index_precision=self.prec)
-        out = (top.cpu().numpy(), sc.cpu().numpy())
-        return out + (rk.cpu().numpy(),) if targets is not None else out
+        return _search_numpy(self, queries, k, exclude, targets, precision)
 
     def save(self, path):
         """One uncompressed .npz: blob (uint8) and meta = [format, V, D, precision]."""
@@ -220,14 +258,7 @@ class ItemSubset(object):
     def search(self, queries, k, exclude=None, targets=None, precision=None):
         """ItemIndex.search among the subset's items: global ids in, global ids out.  An excluded id outside the subset is ignored; a
         target outside it (or excluded) has rank -1; a row with fewer than k eligible items ends in id 0, score -inf."""
-        rows = None
-        if exclude is not None:
-            off, ids = excl_to_local(self._map, *excl_csr(exclude, len(queries)))
-            rows = [ids[off[b]:off[b + 1]] for b in range(len(off) - 1)]
-        if targets is not None:
-            targets = to_local(self._map, targets.cpu().numpy() if torch.is_tensor(targets) else targets)
-        out = self.index.search(queries, k, exclude=rows, targets=targets, precision=precision)
-        return (to_global(self._map, out[0]),) + tuple(out[1:])
+        return _search_numpy(self, queries, k, exclude, targets, precision)
 
     def save(self, path):
         """One uncompressed .npz: blob (uint8), ids (int32 [n + 1]) and meta = [format, n + 1, D, precision, parent_V]."""

@@ -293,6 +293,7 @@ class _Model(object):
         ItemSubset (castrec_amd.index) -- the best k among those items only, one set shared by every row (per-row masks are not
         supported); it combines with exclude, a target outside it has rank -1 and ranks count the set's eligible items.  With an
         iterable the subset is gathered for this call (out of index when given): keep an ItemSubset to reuse it."""
+        from .index import excl_csr
         index = self._allowed(allow, index)
         seq = np.asarray(seq)
         if seq.ndim == 1:
@@ -305,19 +306,8 @@ class _Model(object):
         if isinstance(exclude, str):
             if exclude != "history":
                 raise ValueError("exclude must be 'history', None or a list of per-row id iterables")
-            rows = [r[r != 0] for r in seq.astype(np.int64)]
-        elif exclude is None:
-            rows = None
-        else:
-            rows = [np.asarray(list(r), np.int64).ravel() for r in exclude]
-            if len(rows) != B:
-                raise ValueError("exclude has %d rows for a batch of %d" % (len(rows), B))
-        off = ids = None
-        if rows is not None:
-            off = np.zeros(B + 1, np.int64)
-            off[1:] = np.cumsum([len(r) for r in rows])
-            ids = np.concatenate(rows).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
-        top, sc, rk = eng.topk(int(k), off, ids, targets, index=index)
+            exclude = [r[r != 0] for r in seq.astype(np.int64)]
+        top, sc, rk = eng.topk(int(k), *excl_csr(exclude, B), targets, index=index)
         out = (top.cpu().numpy(),) + ((sc.cpu().numpy(),) if return_scores else ())
         if targets is not None:
             out = out + (rk.cpu().numpy(),)

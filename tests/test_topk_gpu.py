@@ -4,68 +4,15 @@ import types
 
 import numpy as np
 import pytest
-import torch
 
 import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
-from castrec_amd import ops as O
 
-from topk_index_ref import REL, _excl_lists, _inputs, _model
+import topk_harness as H
+from topk_harness import REL
 
 pytestmark = pytest.mark.gpu
 KMAX = L.CR_TOPK_MAX
-
-
-def _run(Q, T, K, excl=None, targets=None, precision=L.PREC_BF16X3, ld=None):
-    """Q [B, D], T [V, D] float32 numpy; excl: list of per-row id lists.  Returns numpy ids, scores, rank."""
-    B, D = Q.shape
-    V = T.shape[0]
-    ld = ld or D
-    qbuf = np.zeros((B, ld), np.float32)
-    qbuf[:, :D] = Q
-    q = torch.from_numpy(qbuf).cuda()
-    t = torch.from_numpy(np.ascontiguousarray(T, np.float32)).cuda()
-    off = ids = None
-    if excl is not None:
-        off = np.zeros(B + 1, np.int64)
-        off[1:] = np.cumsum([len(r) for r in excl])
-        flat = np.concatenate([np.asarray(r, np.int32) for r in excl]) if off[-1] else np.zeros(1, np.int32)
-        ids = torch.from_numpy(flat.astype(np.int32)).cuda()
-    tg = torch.from_numpy(np.asarray(targets, np.int32)).cuda() if targets is not None else None
-    ws = torch.empty(O.topk_workspace_bytes(B, V, D, K), dtype=torch.uint8, device="cuda")
-    out_i = torch.empty(B, K, dtype=torch.int32, device="cuda")
-    out_s = torch.empty(B, K, dtype=torch.float32, device="cuda")
-    rk = torch.empty(B, dtype=torch.int32, device="cuda") if targets is not None else None
-    O.score_topk(q, ld, t, B, K, precision, off, ids, tg, ws, out_i, out_s, rk)
-    torch.cuda.synchronize()
-    return out_i.cpu().numpy(), out_s.cpu().numpy(), (rk.cpu().numpy() if rk is not None else None)
-
-
-def _check(Q, T, K, excl, ids, scores, rel=REL):
-    S = Q.astype(np.float64) @ T.astype(np.float64).T                      # [B, V]
-    A = np.abs(Q.astype(np.float64)) @ np.abs(T.astype(np.float64)).T      # sum_i |q_i t_i|
-    B, V = S.shape
-    for b in range(B):
-        ex = set(int(e) for e in (excl[b] if excl is not None else ())) | {0}
-        mask = np.ones(V, bool)
-        mask[[e for e in ex if 0 <= e < V]] = False
-        elig = np.nonzero(mask)[0]
-        tol = rel * max(1e-30, float(A[b, 1:].max()) if V > 1 else 1.0)
-        n_real = min(K, len(elig))
-        got_i, got_s = ids[b], scores[b]
-        assert np.all(got_i[n_real:] == 0) and np.all(np.isneginf(got_s[n_real:])), (b, got_i, got_s)
-        gi = got_i[:n_real].astype(np.int64)
-        assert len(set(gi.tolist())) == n_real and not (set(gi.tolist()) & ex) and np.all(gi < V)
-        assert np.all(np.diff(got_s[:n_real]) <= 0)
-        assert np.all(np.abs(got_s[:n_real] - S[b, gi]) <= rel * A[b, gi]), (b, np.abs(got_s[:n_real] - S[b, gi]) / A[b, gi])
-        if n_real == 0:
-            continue
-        order = elig[np.lexsort((elig, -S[b, elig]))]
-        kth = S[b, order[n_real - 1]]
-        sure = set(order[:n_real][S[b, order[:n_real]] > kth + 2 * tol].tolist())
-        assert sure <= set(gi.tolist()), (b, sure - set(gi.tolist()))
-        for i in gi:                                                         # anything else is within the tolerance of the K-th
-            assert S[b, i] >= kth - 2 * tol, (b, i, S[b, i], kth)
 
 
 @pytest.mark.parametrize("D", [20, 50, 64, 128, 256])
@@ -77,9 +24,9 @@ def test_topk_against_fp64(D, V):
             B = 33                                                           # (host reference time)
         Q = rs.standard_normal((B, D)).astype(np.float32)
         T = (0.1 * rs.standard_normal((V, D))).astype(np.float32)
-        excl = _excl_lists(rs, B, V, 40) if V <= 3416 else [rs.randint(0, V, rs.randint(0, 60)).tolist() for _ in range(B)]
-        ids, sc, _ = _run(Q, T, K, excl)
-        _check(Q, T, K, excl, ids, sc)
+        excl = H.excl_lists(rs, B, V, 40) if V <= 3416 else [rs.randint(0, V, rs.randint(0, 60)).tolist() for _ in range(B)]
+        ids, sc, _ = H.search(Q, K, excl, None, L.PREC_BF16X3, table=T)
+        H.check_fp64(Q, T, K, excl, ids, sc)
 
 
 def test_topk_large_table_and_pitch():
@@ -88,8 +35,8 @@ def test_topk_large_table_and_pitch():
     T = (0.05 * rs.standard_normal((V, D))).astype(np.float32)
     Q = rs.standard_normal((B, D)).astype(np.float32)
     excl = [rs.randint(1, V, 30).tolist() for _ in range(B)]
-    ids, sc, _ = _run(Q, T, K, excl, ld=300)
-    _check(Q, T, K, excl, ids, sc)
+    ids, sc, _ = H.search(Q, K, excl, None, L.PREC_BF16X3, table=T, ld=300)
+    H.check_fp64(Q, T, K, excl, ids, sc)
 
 
 def test_plain_bf16_bound():
@@ -97,11 +44,11 @@ def test_plain_bf16_bound():
     for D in (50, 128):
         Q = rs.standard_normal((33, D)).astype(np.float32)
         T = (0.1 * rs.standard_normal((5000, D))).astype(np.float32)
-        ids, sc, _ = _run(Q, T, 10, None, precision=L.PREC_BF16)
+        ids, sc, _ = H.search(Q, 10, None, None, L.PREC_BF16, table=T)
         # bf16 operands: |err| <= 2 * 2^-8 * sum |q_i t_i| per score; checked against that bound, relative to the score scale
-        _check(Q, T, 10, None, ids, sc, rel=2 ** -6)
-        i2, s2, _ = _run(Q, T, 10, None, precision=L.PREC_F32)              # CR_PREC_F32 takes the bf16x3 products
-        i3, s3, _ = _run(Q, T, 10, None, precision=L.PREC_BF16X3)
+        H.check_fp64(Q, T, 10, None, ids, sc, rel=2 ** -6)
+        i2, s2, _ = H.search(Q, 10, None, None, L.PREC_F32, table=T)              # CR_PREC_F32 takes the bf16x3 products
+        i3, s3, _ = H.search(Q, 10, None, None, L.PREC_BF16X3, table=T)
         np.testing.assert_array_equal(i2, i3); np.testing.assert_array_equal(s2, s3)
 
 
@@ -111,7 +58,7 @@ def test_ties_go_to_the_smaller_id():
     base = rs.standard_normal((V // 3, D)).astype(np.float32)
     T = np.repeat(base, 3, axis=0)[:V]                                     # rows 3j, 3j+1, 3j+2 equal
     Q = rs.standard_normal((5, D)).astype(np.float32)
-    ids, sc, _ = _run(Q, T, 30, None)
+    ids, sc, _ = H.search(Q, 30, None, None, L.PREC_BF16X3, table=T)
     for b in range(5):
         for k in range(29):
             assert sc[b, k] > sc[b, k + 1] or (sc[b, k] == sc[b, k + 1] and ids[b, k] < ids[b, k + 1]), (b, k)
@@ -140,12 +87,12 @@ def test_ranks_exact_on_small_tables_and_bounded_on_large():
         T = (0.1 * rs.standard_normal((V, D))).astype(np.float32)
         T[7] = T[3]; T[8] = T[3]                                            # ties
         Q = rs.standard_normal((B, D)).astype(np.float32)
-        excl = _excl_lists(rs, B, V, 20)
+        excl = H.excl_lists(rs, B, V, 20)
         excl = [r if b % 4 != 3 else r[:10] for b, r in enumerate(excl)]
         tg = rs.randint(1, V, B)
         tg[0] = 3; tg[1] = 8
         excl[2] = excl[2] + [int(tg[2])]                                     # an excluded target
-        ids, sc, rk = _run(Q, T, KMAX, excl, tg)
+        ids, sc, rk = H.search(Q, KMAX, excl, tg, L.PREC_BF16X3, table=T)
         for b in range(B):
             ex = set(excl[b])
             if tg[b] in ex:
@@ -157,7 +104,7 @@ def test_ranks_exact_on_small_tables_and_bounded_on_large():
     Q = rs.standard_normal((B, D)).astype(np.float32)
     excl = [rs.randint(1, V, 50).tolist() for _ in range(B)]
     tg = rs.randint(1, V, B)
-    _, _, rk = _run(Q, T, 10, excl, tg)
+    _, _, rk = H.search(Q, 10, excl, tg, L.PREC_BF16X3, table=T)
     S = Q.astype(np.float64) @ T.astype(np.float64).T
     for b in range(B):
         ex = set(excl[b]) | {0}
@@ -178,8 +125,8 @@ def test_deterministic():
     Q = rs.standard_normal((B, D)).astype(np.float32)
     excl = [rs.randint(1, V, 30).tolist() for _ in range(B)]
     tg = rs.randint(1, V, B)
-    a = _run(Q, T, 100, excl, tg)
-    b = _run(Q, T, 100, excl, tg)
+    a = H.search(Q, 100, excl, tg, L.PREC_BF16X3, table=T)
+    b = H.search(Q, 100, excl, tg, L.PREC_BF16X3, table=T)
     for x, y in zip(a, b):
         np.testing.assert_array_equal(x, y)
 
@@ -188,9 +135,9 @@ def test_deterministic():
 @pytest.mark.parametrize("name", ["sasrec", "cast_1", "cast_9"])
 def test_recommend_matches_predict_over_all_items(name):
     itemnum, B, T, k = 500, 9, 20, 25
-    m = _model(name)
+    m = H.model(name)
     rs = np.random.RandomState(1)
-    seq, ts, hrs, dys = _inputs(rs, B, T, itemnum)
+    seq, ts, hrs, dys = H.inputs(rs, B, T, itemnum)
     ids, sc = m.recommend(list(range(B)), seq, k=k, timeseq=ts, hours_seq=hrs, days_seq=dys)
     allc = np.arange(1, itemnum + 1, dtype=np.int32)
     lg, _ = m.predict(None, list(range(B)), seq, allc, timeseq=ts, hours_seq=hrs, days_seq=dys, want_attention=False)
@@ -223,7 +170,7 @@ def test_evaluate_full_equals_a_host_full_ranking_evaluator():
         ts = 1_000_000_000 + 3600 * np.cumsum(rs.randint(1, 50, n))
         User[u] = [(int(rs.randint(1, itemnum + 1)), 4.0, int(ts[j])) for j in range(n)]
     dataset = U.partition(User, usernum, itemnum)
-    m = _model("cast_1", itemnum=itemnum)
+    m = H.model("cast_1", itemnum=itemnum)
     args = types.SimpleNamespace(maxlen=20, bin_in_hours=24, max_bins=20, log_scale=False, test_model=None, test_seq_len=None)
     for fn, mode in ((U.evaluate_full, "test"), (U.evaluate_valid_full, "valid")):
         np.random.seed(7)

@@ -14,6 +14,7 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 from castrec_amd import util as U
 from helpers import load_sampler_golden
+from topk_harness import rejects
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -27,13 +28,7 @@ def _valid_desc(B=4, V=100, D=50, K=10):
 
 
 def _rejects(d, *words):
-    rc = L.lib.cr_score_topk(ctypes.byref(d) if d is not None else None, None)
-    msg = L.lib.cr_last_error().decode()
-    assert rc == -1, (rc, msg)
-    assert "cr_score_topk" in msg
-    for w in words:
-        assert w in msg, msg
-    return msg
+    return rejects(("cr_score_topk", ctypes.byref(d) if d is not None else None, None), *words)
 
 
 def test_score_topk_validates_before_any_hip_call():

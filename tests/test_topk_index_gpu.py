@@ -11,20 +11,13 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 from castrec_amd import ops as O
 from castrec_amd.index import ItemIndex
+import topk_harness as H
 import topk_index_ref as R
-from topk_index_ref import REL, _excl_lists, _inputs, _model
+from topk_harness import REL, same_bits as _same, search as _search
 
 pytestmark = pytest.mark.gpu
 SPLIT, PLAIN = L.PREC_BF16X3, L.PREC_BF16
 DS = [8, 20, 50, 64, 128, 256]
-
-
-def _table_in_nan_buffer(T):
-    """The table on the device, followed directly by NaNs: anything read past its end shows."""
-    V, D = T.shape
-    buf = torch.full((V * D + 1024,), float("nan"), dtype=torch.float32, device="cuda")
-    buf[:V * D] = torch.from_numpy(T.reshape(-1)).cuda()
-    return buf[:V * D].view(V, D)
 
 
 @pytest.mark.parametrize("D", DS)
@@ -33,7 +26,7 @@ def test_built_blob_equals_the_numpy_layout(D):
     for V in (1, 2, 17, 65):
         T = rs.standard_normal((V, D)).astype(np.float32)
         T[0, 0] = -0.0
-        t = _table_in_nan_buffer(T)
+        t = H.table_in_nan_buffer(T)
         for prec in (SPLIT, PLAIN):
             want = R.build_blob(T, prec)
             n = O.topk_index_bytes(V, D, prec)
@@ -48,48 +41,6 @@ def test_built_blob_equals_the_numpy_layout(D):
             assert np.array_equal(again.cpu().numpy(), want)
         if V == 17:                                                                      # CR_PREC_F32 names the split index
             assert torch.equal(O.topk_index_build(t, L.PREC_F32), O.topk_index_build(t, SPLIT))
-
-
-def _search(Q, K, excl, tg, prec, table=None, index=None, iprec=None, V=None):
-    """cr_score_topk on the table or on an index of it: (ids, score bits as uint32, rank) as numpy."""
-    B, D = Q.shape
-    q = torch.from_numpy(Q).cuda() if not torch.is_tensor(Q) else Q
-    V = table.shape[0] if table is not None else V
-    off = ids = None
-    if excl is not None:
-        off = np.zeros(B + 1, np.int64)
-        off[1:] = np.cumsum([len(r) for r in excl])
-        flat = np.concatenate([np.asarray(r, np.int32) for r in excl]) if off[-1] else np.zeros(1, np.int32)
-        ids = torch.from_numpy(flat.astype(np.int32)).cuda()
-    tgt = torch.from_numpy(np.asarray(tg, np.int32)).cuda() if tg is not None else None
-    ws = torch.empty(O.topk_workspace_bytes(B, V, D, K), dtype=torch.uint8, device="cuda")
-    out_i = torch.full((B, K), -7, dtype=torch.int32, device="cuda")
-    out_s = torch.full((B, K), 123.0, dtype=torch.float32, device="cuda")
-    rk = torch.full((B,), -7, dtype=torch.int32, device="cuda") if tg is not None else None
-    if index is None:
-        O.score_topk(q, D, table, B, K, prec, off, ids, tgt, ws, out_i, out_s, rk)
-    else:
-        O.score_topk(q, D, (V, D), B, K, prec, off, ids, tgt, ws, out_i, out_s, rk, index=index, index_precision=iprec)
-    torch.cuda.synchronize()
-    return out_i.cpu().numpy(), out_s.cpu().numpy().view(np.uint32), (rk.cpu().numpy() if rk is not None else None)
-
-
-def _same(a, b, what):
-    for x, y, name in zip(a, b, ("ids", "scores", "rank")):
-        if x is None:
-            assert y is None
-            continue
-        assert np.array_equal(x, y), (what, name, np.argwhere(x != y)[:5])
-
-
-def _targets(rs, B, V, excl):
-    tg = rs.randint(1, max(2, V), B).astype(np.int32)
-    tg[0] = V - 1
-    if B > 4:
-        tg[1], tg[3], tg[4] = 0, V + 2, V
-        tg[2] = max(1, V - 2)
-        excl[2] = list(excl[2]) + [int(tg[2])]                                           # an excluded target
-    return tg
 
 
 def _compare_all(T, Q, K, excl, tg, what):
@@ -113,8 +64,8 @@ def test_indexed_search_is_bit_identical(D, V):
     T = (0.1 * rs.standard_normal((V, D))).astype(np.float32)
     for B, K in ((1, 1), (17, 10), (70, 128)):
         Q = rs.standard_normal((B, D)).astype(np.float32)
-        excl = _excl_lists(rs, B, V, 40)                   # empty, duplicates, 0, ids >= V, nearly everything
-        tg = _targets(rs, B, V, excl)
+        excl = H.excl_lists(rs, B, V, 40)                   # empty, duplicates, 0, ids >= V, nearly everything
+        tg = H.targets(rs, B, V, excl)
         ids, _, rk = _compare_all(T, Q, K, excl, tg, (D, V, B, K))
         assert np.all(ids[:, 0] != -7) and np.all(rk != -7)
         if B > 4:
@@ -131,7 +82,8 @@ def test_indexed_search_is_bit_identical_on_ties():
     Q = rs.standard_normal((B, D)).astype(np.float32)
     excl = [rs.randint(1, V, 20).tolist() for _ in range(B)]
     ids, sc, rk = _compare_all(T, Q, K, excl, rs.randint(1, V, B), ("ties",))
-    assert np.any(sc[:, :-1] == sc[:, 1:])                                               # the run did meet ties
+    bits = sc.view(np.uint32)
+    assert np.any(bits[:, :-1] == bits[:, 1:])                                           # the run did meet ties
 
 
 def test_indexed_search_is_bit_identical_on_many_chunks():
@@ -170,7 +122,7 @@ def test_item_index_search_save_load(tmp_path):
     V, D, B, K = 517, 50, 9, 20
     T = (0.1 * rs.standard_normal((V, D))).astype(np.float32)
     Q = rs.standard_normal((B, D)).astype(np.float32)
-    excl = _excl_lists(rs, B, V, 30)
+    excl = H.excl_lists(rs, B, V, 30)
     tg = rs.randint(1, V, B).astype(np.int32)
     t = torch.from_numpy(T).cuda()
     ix = ItemIndex.build(t)
@@ -178,19 +130,17 @@ def test_item_index_search_save_load(tmp_path):
     assert np.array_equal(ix.blob.cpu().numpy(), R.build_blob(T, SPLIT))
     ids, sc, rk = ix.search(Q, K, exclude=excl, targets=tg)
     ref = _search(Q, K, excl, tg, SPLIT, table=t)
-    _same(ref, (ids, sc.view(np.uint32), rk), ("ItemIndex.search",))
+    _same(ref, (ids, sc, rk), ("ItemIndex.search",))
     ids2, sc2 = ix.search(torch.from_numpy(Q).cuda(), K)                                 # device queries, no exclusions, no targets
-    _same(_search(Q, K, None, None, SPLIT, table=t)[:2], (ids2, sc2.view(np.uint32)), ("device queries",))
+    _same(_search(Q, K, None, None, SPLIT, table=t)[:2], (ids2, sc2), ("device queries",))
     p = ix.save(str(tmp_path / "items.npz"))
     back = ItemIndex.load(p)
     assert back.blob.is_cuda and back.version is None and torch.equal(back.blob, ix.blob)
-    _same(ref, (lambda r: (r[0], r[1].view(np.uint32), r[2]))(back.search(Q, K, exclude=excl, targets=tg)), ("loaded",))
+    _same(ref, back.search(Q, K, exclude=excl, targets=tg), ("loaded",))
     plain = ItemIndex.build(t, "bf16")
     assert plain.blob.numel() * 2 == ix.blob.numel()
-    _same(_search(Q, K, excl, tg, PLAIN, table=t), (lambda r: (r[0], r[1].view(np.uint32), r[2]))(plain.search(Q, K, exclude=excl, targets=tg)),
-          ("plain ItemIndex",))
-    _same(_search(Q, K, excl, tg, PLAIN, table=t),
-          (lambda r: (r[0], r[1].view(np.uint32), r[2]))(ix.search(Q, K, exclude=excl, targets=tg, precision="bf16")), ("plain search of split",))
+    _same(_search(Q, K, excl, tg, PLAIN, table=t), plain.search(Q, K, exclude=excl, targets=tg), ("plain ItemIndex",))
+    _same(_search(Q, K, excl, tg, PLAIN, table=t), ix.search(Q, K, exclude=excl, targets=tg, precision="bf16"), ("plain search of split",))
     with pytest.raises(RuntimeError, match="plain"):
         plain.search(Q, K, precision="bf16x3")
     with pytest.raises(ValueError):
@@ -199,9 +149,9 @@ def test_item_index_search_save_load(tmp_path):
 
 def test_model_recommend_similar_items_and_staleness():
     itemnum, B, T, k = 300, 9, 20, 25
-    m = _model("cast_1", itemnum=itemnum)
+    m = H.model("cast_1", itemnum=itemnum)
     rs = np.random.RandomState(1)
-    seq, ts, hrs, dys = _inputs(rs, B, T, itemnum)
+    seq, ts, hrs, dys = H.inputs(rs, B, T, itemnum)
     tg = rs.randint(1, itemnum + 1, B).astype(np.int32)
     kw = dict(k=k, timeseq=ts, hours_seq=hrs, days_seq=dys, targets=tg)
     ix = m.build_item_index()
@@ -233,7 +183,7 @@ def test_model_recommend_similar_items_and_staleness():
         m.similar_items([0])
 
     # a training step makes the index stale; a rebuilt one works; a loaded one (version None) is the caller's responsibility
-    other = _model("cast_1", itemnum=itemnum + 1)
+    other = H.model("cast_1", itemnum=itemnum + 1)
     with pytest.raises(ValueError):
         other.recommend(None, seq, index=ix, **kw)
     pos = rs.randint(1, itemnum + 1, seq.shape).astype(np.int32) * (seq != 0)
@@ -266,7 +216,7 @@ def test_evaluate_full_with_an_index_returns_the_same_pair():
         ts = 1_000_000_000 + 3600 * np.cumsum(rs.randint(1, 50, n))
         User[u] = [(int(rs.randint(1, itemnum + 1)), 4.0, int(ts[j])) for j in range(n)]
     dataset = U.partition(User, usernum, itemnum)
-    m = _model("cast_1", itemnum=itemnum)
+    m = H.model("cast_1", itemnum=itemnum)
     args = types.SimpleNamespace(maxlen=20, bin_in_hours=24, max_bins=20, log_scale=False, test_model=None, test_seq_len=None)
     for fn in (U.evaluate_full, U.evaluate_valid_full):
         a = fn(m, dataset, args)

@@ -8,6 +8,7 @@ import pytest
 import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 import topk_index_ref as R
+from topk_harness import rejects
 
 SPLIT, PLAIN = L.PREC_BF16X3, L.PREC_BF16
 
@@ -26,12 +27,7 @@ def test_index_bytes_is_the_layout_formula():
 
 
 def _build_rejects(table, V, D, prec, index, nbytes, *words):
-    rc = L.lib.cr_topk_index_build(table, V, D, prec, index, nbytes, None)
-    msg = L.lib.cr_last_error().decode()
-    assert rc == -1, (rc, msg)
-    assert msg.startswith("cr_topk_index_build:"), msg
-    for w in words:
-        assert w in msg, msg
+    rejects(("cr_topk_index_build", table, V, D, prec, index, nbytes, None), *words)
 
 
 def test_index_build_validates_before_any_hip_call():
@@ -57,13 +53,7 @@ def _desc(B=4, V=100, D=50, K=10, precision=SPLIT, index_precision=SPLIT):
 
 
 def _rejects(d, *words):
-    rc = L.lib.cr_score_topk(ctypes.byref(d), None)
-    msg = L.lib.cr_last_error().decode()
-    assert rc == -1, (rc, msg)
-    assert msg.startswith("cr_score_topk:"), msg
-    for w in words:
-        assert w in msg, msg
-    return msg
+    return rejects(("cr_score_topk", ctypes.byref(d), None), *words)
 
 
 def test_score_topk_index_fields_validate_before_any_hip_call():

@@ -10,8 +10,9 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 from castrec_amd import ops as O
 from castrec_amd.index import ItemIndex, ItemSubset, subset_ids
+import topk_harness as H
 import topk_index_ref as R
-from topk_index_ref import REL, _inputs, _model
+from topk_harness import same_bits as _same
 
 pytestmark = pytest.mark.gpu
 SPLIT, PLAIN = L.PREC_BF16X3, L.PREC_BF16
@@ -28,14 +29,6 @@ def _pick(rs, V, n):
     must = [1, 15, 16, 17, V - 1]
     rest = rs.choice([i for i in range(2, V - 1) if i not in must], n - len(must), replace=False)
     return rs.permutation(must + rest.tolist()).tolist()
-
-
-def _table_in_nan_buffer(T):
-    """The table on the device, followed directly by NaNs: anything read past its end shows."""
-    V, D = T.shape
-    buf = torch.full((V * D + 1024,), float("nan"), dtype=torch.float32, device="cuda")
-    buf[:V * D] = torch.from_numpy(T.reshape(-1)).cuda()
-    return buf[:V * D].view(V, D)
 
 
 def _gather_checked(ids_dev, prec, want, what, **src):
@@ -57,7 +50,7 @@ def test_gathered_sub_index_has_the_bytes_of_a_build_on_the_gathered_table(D):
     for V in VS:
         T = rs.standard_normal((V, D)).astype(np.float32)                   # row 0 is NOT zero: local row 0 must be written as +0
         T[1, 0] = -0.0
-        t = _table_in_nan_buffer(T)
+        t = H.table_in_nan_buffer(T)
         ix = {p: O.topk_index_build(t, p) for p in (SPLIT, PLAIN)}
         for n in NS:
             for ids in ([_pick(rs, V, n)] + ([[1], [16]] if n == 1 else [])):
@@ -78,7 +71,7 @@ def test_gathered_sub_index_has_the_bytes_of_a_build_on_the_gathered_table(D):
         # every item: the full index (of a table whose padding row is zero, as an item table's is)
         T0 = T.copy()
         T0[0] = 0.0
-        t0 = _table_in_nan_buffer(T0)
+        t0 = H.table_in_nan_buffer(T0)
         every = torch.arange(1, V, dtype=torch.int32, device="cuda")
         for prec in (SPLIT, PLAIN):
             full = O.topk_index_build(t0, prec)
@@ -86,16 +79,6 @@ def test_gathered_sub_index_has_the_bytes_of_a_build_on_the_gathered_table(D):
             assert np.array_equal(want, R.build_blob(T0, prec))
             _gather_checked(every, prec, want, (D, V, "every item, table"), table=t0)
             _gather_checked(every, prec, want, (D, V, "every item, index"), index=full, index_precision=prec, V=V, D=D)
-
-
-def _bits(r):
-    return (r[0], r[1].view(np.uint32)) + ((r[2],) if len(r) > 2 else ())
-
-
-def _same(a, b, what):
-    assert len(a) == len(b)
-    for x, y, name in zip(_bits(a), _bits(b), ("ids", "scores", "rank")):
-        assert x.dtype == y.dtype and np.array_equal(x, y), (what, name, np.argwhere(x != y)[:5], x, y)
 
 
 def _case(rs, V, ids, B):
@@ -203,39 +186,18 @@ def test_subset_search_against_fp64_brute_force():
     ids = _pick(rs, V, 37)
     excl = [[], ids[:5], [3, 0, 200], ids[:30], ids[5:9]]
     t = torch.from_numpy(T).cuda()
-    S = Q.astype(np.float64) @ T.astype(np.float64).T
-    A = np.abs(Q.astype(np.float64)) @ np.abs(T.astype(np.float64)).T
+    outside = set(range(1, V)) - set(ids)                                   # eligible: the subset's items the row does not exclude
     for sub in (ItemIndex.build(t).subset(ids), ItemSubset.build(t, ids)):
         got_i, got_s = sub.search(Q, K, exclude=excl)
-        for b in range(B):
-            elig = np.array(sorted(set(ids) - set(excl[b])))
-            n_real = min(K, len(elig))
-            assert np.all(got_i[b, n_real:] == 0) and np.all(np.isneginf(got_s[b, n_real:]))
-            gi = got_i[b, :n_real].astype(np.int64)
-            assert len(set(gi.tolist())) == n_real and set(gi.tolist()) <= set(elig.tolist())
-            assert np.all(np.diff(got_s[b, :n_real]) <= 0)
-            assert np.all(np.abs(got_s[b, :n_real] - S[b, gi]) <= REL * A[b, gi])
-            tol = REL * float(A[b, 1:].max())
-            order = elig[np.lexsort((elig, -S[b, elig]))]
-            kth = S[b, order[n_real - 1]]
-            sure = set(order[:n_real][S[b, order[:n_real]] > kth + 2 * tol].tolist())
-            assert sure <= set(gi.tolist()), (b, sure - set(gi.tolist()))
-            assert np.all(S[b, gi] >= kth - 2 * tol)
+        H.check_fp64(Q, T, K, [set(r) | outside for r in excl], got_i, got_s)
 
 
 # ---- the public surface ----------------------------------------------------------------------------------------------------------------
-def _eq(a, b, what):
-    assert len(a) == len(b), what
-    for x, y in zip(a, b):
-        assert x.dtype == y.dtype and np.array_equal(x.view(np.uint32) if x.dtype == np.float32 else x,
-                                                     y.view(np.uint32) if y.dtype == np.float32 else y), (what, x, y)
-
-
 def test_model_recommend_and_similar_items_with_allow(tmp_path):
     itemnum, B, T, k = 500, 9, 20, 12
-    m = _model("cast_1", itemnum=itemnum)
+    m = H.model("cast_1", itemnum=itemnum)
     rs = np.random.RandomState(5)
-    seq, ts, hrs, dys = _inputs(rs, B, T, itemnum)
+    seq, ts, hrs, dys = H.inputs(rs, B, T, itemnum)
     allow = rs.choice(np.arange(1, itemnum + 1), 120, replace=False).tolist() + [1, itemnum, 15, 16, 17]
     allow[7] = int(seq[0][seq[0] != 0][0])                                  # an allowed item of row 0's history
     inside = set(allow)
@@ -251,17 +213,17 @@ def test_model_recommend_and_similar_items_with_allow(tmp_path):
     # the full search with (history united with the complement) excluded: existing code
     want = m.recommend(None, seq, exclude=[sorted(h | set(outside)) for h in hist], **kw)
     a = m.recommend(None, seq, allow=allow, **kw)
-    _eq(want, a, "allow=ids, no index")
-    _eq(a, m.recommend(None, seq, allow=allow, index=ix, **kw), "allow=ids, index=ix")
-    _eq(a, m.recommend(None, seq, allow=sub, **kw), "allow=ItemSubset")
-    _eq(a, m.recommend(None, seq, allow=iter(allow), exclude="history", **kw), "an iterator; exclude='history' spelled out")
-    _eq(a, m.recommend(None, seq, index=sub, **kw), "index=ItemSubset")
+    _same(want, a, "allow=ids, no index")
+    _same(a, m.recommend(None, seq, allow=allow, index=ix, **kw), "allow=ids, index=ix")
+    _same(a, m.recommend(None, seq, allow=sub, **kw), "allow=ItemSubset")
+    _same(a, m.recommend(None, seq, allow=iter(allow), exclude="history", **kw), "an iterator; exclude='history' spelled out")
+    _same(a, m.recommend(None, seq, index=sub, **kw), "index=ItemSubset")
     assert a[2][0] == a[2][1] == -1 and np.all(a[2][2:] >= 0)
     for b in range(B):
         got = set(a[0][b].tolist())
         assert got <= inside and not (got & hist[b]) and 0 not in got
     none = m.recommend(None, seq, allow=allow, exclude=None, **kw)          # without the history exclusion
-    _eq(m.recommend(None, seq, exclude=[outside] * B, **kw), none, "allow=ids, exclude=None")
+    _same(m.recommend(None, seq, exclude=[outside] * B, **kw), none, "allow=ids, exclude=None")
     assert none[2][0] >= 0
     ids_only = m.recommend(None, seq, k=k, timeseq=ts, hours_seq=hrs, days_seq=dys, allow=sub, return_scores=False)
     assert np.array_equal(ids_only, a[0])
@@ -275,9 +237,9 @@ def test_model_recommend_and_similar_items_with_allow(tmp_path):
         for r, it in enumerate(items):
             assert it not in sid[r] and set(sid[r].tolist()) <= inside and len(set(sid[r].tolist())) == 10
         ref = ref or (sid, ssc)
-        _eq(ref, (sid, ssc), "similar_items(allow=)")
-    _eq(ref, ix.search(m.get_params()["item_emb"].cpu()[torch.from_numpy(items)], 10,
-                       exclude=[sorted(set(outside) | {int(i)}) for i in items]), "similar_items against the full search")
+        _same(ref, (sid, ssc), "similar_items(allow=)")
+    _same(ref, ix.search(m.get_params()["item_emb"].cpu()[torch.from_numpy(items)], 10,
+                         exclude=[sorted(set(outside) | {int(i)}) for i in items]), "similar_items against the full search")
 
     # save / load on the device: equal arrays; version None after a load
     p = sub.save(str(tmp_path / "allowed.npz"))
@@ -286,14 +248,14 @@ def test_model_recommend_and_similar_items_with_allow(tmp_path):
     assert torch.equal(back.index.blob, sub.index.blob) and torch.equal(back.ids, sub.ids)
     Q = rs.standard_normal((B, 50)).astype(np.float32)
     _same(sub.search(Q, k, exclude=[list(h) for h in hist], targets=tg), back.search(Q, k, exclude=[list(h) for h in hist], targets=tg), "loaded")
-    _eq(a, m.recommend(None, seq, allow=back, **kw), "allow=a loaded ItemSubset")
+    _same(a, m.recommend(None, seq, allow=back, **kw), "allow=a loaded ItemSubset")
     with pytest.raises(ValueError, match="format"):
         ItemIndex.load(p)
     with pytest.raises(ValueError):
         m.recommend(None, seq, allow=[0, 5], **kw)
     with pytest.raises(ValueError):
         m.recommend(None, seq, allow=[itemnum + 1], **kw)
-    other = _model("cast_1", itemnum=itemnum + 1)
+    other = H.model("cast_1", itemnum=itemnum + 1)
     with pytest.raises(ValueError):
         other.recommend(None, seq, allow=sub, **kw)
 
@@ -306,23 +268,23 @@ def test_model_recommend_and_similar_items_with_allow(tmp_path):
         with pytest.raises(RuntimeError, match="stale index"):
             call()
     fresh = m.recommend(None, seq, allow=allow, **kw)                       # gathered from the current table
-    _eq(fresh, m.recommend(None, seq, allow=m.build_item_index().subset(allow), **kw), "after the step")
+    _same(fresh, m.recommend(None, seq, allow=m.build_item_index().subset(allow), **kw), "after the step")
     assert not np.array_equal(fresh[1], a[1])
 
 
 def test_allow_none_is_the_existing_code_path():
     itemnum, B, T, k = 500, 6, 20, 10
-    m = _model("cast_1", itemnum=itemnum)
+    m = H.model("cast_1", itemnum=itemnum)
     rs = np.random.RandomState(6)
-    seq, ts, hrs, dys = _inputs(rs, B, T, itemnum)
+    seq, ts, hrs, dys = H.inputs(rs, B, T, itemnum)
     tg = rs.randint(1, itemnum + 1, B).astype(np.int32)
     kw = dict(k=k, timeseq=ts, hours_seq=hrs, days_seq=dys, targets=tg)
     ix = m.build_item_index()
-    _eq(m.recommend(None, seq, **kw), m.recommend(None, seq, allow=None, **kw), "recommend")
-    _eq(m.recommend(None, seq, index=ix, **kw), m.recommend(None, seq, index=ix, allow=None, **kw), "recommend(index=)")
+    _same(m.recommend(None, seq, **kw), m.recommend(None, seq, allow=None, **kw), "recommend")
+    _same(m.recommend(None, seq, index=ix, **kw), m.recommend(None, seq, index=ix, allow=None, **kw), "recommend(index=)")
     items = [1, 7, itemnum]
-    _eq(m.similar_items(items, 10), m.similar_items(items, 10, allow=None), "similar_items")
-    _eq(m.similar_items(items, 10, index=ix), m.similar_items(items, 10, index=ix, allow=None), "similar_items(index=)")
+    _same(m.similar_items(items, 10), m.similar_items(items, 10, allow=None), "similar_items")
+    _same(m.similar_items(items, 10, index=ix), m.similar_items(items, 10, index=ix, allow=None), "similar_items(index=)")
     Q = rs.standard_normal((B, 50)).astype(np.float32)
     excl = [rs.randint(0, itemnum + 3, 10).tolist() for _ in range(B)]
     _same(ix.search(Q, k, exclude=excl, targets=tg), ix.search(Q, k, exclude=excl, targets=tg, allow=None), "ItemIndex.search")

@@ -12,6 +12,7 @@ import castrec_amd  # noqa: F401
 from castrec_amd import lib as L
 from castrec_amd.index import excl_csr, excl_to_local, subset_ids, to_global, to_local
 import topk_index_ref as R
+from topk_harness import rejects
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SPLIT, PLAIN = L.PREC_BF16X3, L.PREC_BF16
@@ -55,12 +56,7 @@ def test_exclusion_rows_are_translated_and_absent_ids_dropped():
 
 
 def _gather_rejects(table, index, iprec, V, D, ids, n, prec, out, nbytes, *words):
-    rc = L.lib.cr_topk_index_gather(table, index, iprec, V, D, ids, n, prec, out, nbytes, None)
-    msg = L.lib.cr_last_error().decode()
-    assert rc == -1, (rc, msg)
-    assert msg.startswith("cr_topk_index_gather:"), msg
-    for w in words:
-        assert w in msg, msg
+    rejects(("cr_topk_index_gather", table, index, iprec, V, D, ids, n, prec, out, nbytes, None), *words)
 
 
 def test_index_gather_validates_before_any_hip_call():

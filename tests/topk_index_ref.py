@@ -3,8 +3,6 @@
 NK = tk_nk(D) k-steps, n_tiles = ceil(V / 16), planes = 2 (split: hi, lo) or 1 (plain: hi).  The blob is an array of 16-byte groups of
 eight bf16; group (plane h, tile t, k-step ks, lane l) sits at byte (((h n_tiles + t) NK + ks) 64 + l) 16 and its element j is column
 32 ks + 8 (l >> 4) + j of row 16 t + (l & 15): hi = bf16(x), lo = bf16(x - hi); +0 where the row is >= V or the column >= D."""
-import types
-
 import numpy as np
 
 from gbce_ref import _split
@@ -55,43 +53,3 @@ def group(blob, V, D, h, t, ks, lane):
     o = group_offset(V, D, h, t, ks, lane)
     return (blob[o:o + 16].view(np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
 
-
-# ---- what test_topk_gpu and test_topk_index_gpu share ------------------------------------------------------------------------------
-REL = 1e-5                       # bf16x3 against the fp64 dot, relative to sum_i |q_i t_i| (the scale of a dot product's rounding)
-
-
-def _excl_lists(rs, B, V, n_max):
-    out = []
-    for b in range(B):
-        kind = b % 4
-        if kind == 0:
-            out.append([])
-        elif kind == 1:
-            r = rs.randint(0, V + 3, rs.randint(1, n_max + 1)).tolist()         # ids past the table, 0
-            out.append(r + r[:2] + [0])                                      # duplicates
-        elif kind == 2:
-            out.append(rs.randint(1, max(2, V), rs.randint(1, n_max + 1)).tolist())
-        else:
-            out.append(list(range(1, V))[: max(0, V - 3)])                   # fewer than K eligible when K > 2
-    return out
-
-
-def _model(name, itemnum=500, D=50, T=20, seed=0):
-    from castrec_amd.models import build_model
-    args = types.SimpleNamespace(maxlen=T, hidden_units=D, num_blocks=2, num_heads=1, dropout_rate=0.0, l2_emb=0.0, lr=1e-3,
-                                 max_bins=20, bin_in_hours=24, num_context_blocks=2, log_scale=False, input_context=False)
-    m = build_model(name, 20, itemnum, 5.0, args)
-    rs = np.random.RandomState(seed)
-    P = m.get_params()
-    m.load_params({k: v.cpu().numpy() + 0.1 * rs.standard_normal(tuple(v.shape)).astype(np.float32) for k, v in P.items()})
-    return m
-
-
-def _inputs(rs, B, T, itemnum, max_bins=20):
-    seq = rs.randint(1, itemnum + 1, (B, T)).astype(np.int32)
-    for b in range(B):
-        seq[b, : rs.randint(0, T - 2)] = 0
-    ts = (rs.randint(0, max_bins + 1, (B, T)) * (seq != 0)).astype(np.int32)
-    hrs = (rs.randint(1, 25, (B, T)) * (seq != 0)).astype(np.int32)
-    dys = (rs.randint(1, 8, (B, T)) * (seq != 0)).astype(np.int32)
-    return seq, ts, hrs, dys
