@@ -1,6 +1,7 @@
 // Helpers of the register-layout backward kernels (cr_stack_bwd.hip: one launch per row phase; cr_stack_bwd1.hip: one launch
 // per block): permuted weight images for out^T = W g^T, the wave's tile -> bf16 image, weight gradients a^T g from images
-// through transposed reads, LayerNorm backward of the lane's row and the fixed-order fold of its column sums.
+// through transposed reads, LayerNorm backward of the lane's row and the fixed-order fold of its column sums; the small pieces both
+// files share (tile rows, zeroing, the feed-forward wgrad pair, the embedding backward) and the host's argument checks.
 #pragma once
 #include "cr_rlayout.hpp"
 
@@ -275,3 +276,93 @@ __device__ __forceinline__ void ln_grads_store(float* part /* [2][SB_WAVES][64] 
     }
 }
 
+// =====================================================================================================
+// What the three-launch kernels (cr_stack_bwd.hip) and the one-launch kernel (cr_stack_bwd1.hip) share beyond the products above.
+// The one-launch kernel takes from here only what leaves its instruction stream as it was ("One row chain, two
+// kernels": its row chain itself stays written out in b1_phase1).
+// =====================================================================================================
+// accumulator sets of one size (weight-gradient tiles [2], LayerNorm column sums [4]) to zero
+template <int N, class... A>
+__device__ __forceinline__ void r_zero(f32x4 (&x)[N], A&... more) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        x[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        ((more[i] = x[i]), ...);
+    }
+}
+
+// the lane's row of 16-row tile `tile` of sequence n: m = its row of [M, D] (clamped into the sequence), rok = it exists
+__device__ __forceinline__ void r_tile_rows(int n, int tile, int T, int& m, bool& rok) {
+    const int q = 16 * tile + (lane_now() & 15);
+    rok = q < T;
+    m = n * T + min(q, T - 1);
+}
+
+// dW2 (+ db2) += hid^T g2, dW1 (+ db1) += f_in^T g1 over the `ntr` tiles of a round; image slots of IST elements: 0 hid (+ ones),
+// 1 g2, 2 f_in (+ ones), 3 g1
+template <bool SPLIT, bool BIAS>
+__device__ __forceinline__ void ffn_wgrad_accum(f32x4 (&aw2)[2], f32x4 (&ab2)[2], f32x4 (&aw1)[2], f32x4 (&ab1)[2], const __bf16* Im, int ntr, int it, int jt0) {
+    constexpr int IST = SPLIT ? 2 * SB_IMG : SB_IMG;
+    wgrad_accum<SPLIT, BIAS>(aw2, ab2, Im, Im + SB_IMG, Im + IST, Im + IST + SB_IMG, ntr, it, jt0);
+    wgrad_accum<SPLIT, BIAS>(aw1, ab1, Im + 2 * IST, Im + 2 * IST + SB_IMG, Im + 3 * IST, Im + 3 * IST + SB_IMG, ntr, it, jt0);
+}
+
+// ---- the embedding backward of the lane's row of dx (cr_embed_bwd's recipe): g = dx * mask * keep / (1 - rate) ----
+// stepv: the step word of the gather's dropout site (cr_step_request(e.drop), however the kernel obtained it)
+__device__ __forceinline__ void r_embed_bwd(f32x4 (&dxl)[4], const cr_embed_desc& e, uint32_t stepv, int m, bool rok, int D) {
+    const DropCtx dce = drop_ctx(e.drop, stepv);
+    const int lg = lane_now() >> 4;
+    const int mk = e.mask_ids ? e.mask_ids[m] : 1;
+    const float kf = (rok && mk != 0) ? 1.0f : 0.0f;
+    const uint32_t eb = ((e.drop.row_offset + (uint32_t)m) * (uint32_t)D + (uint32_t)(4 * lg)) * CR_PHI + dce.key;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            float v = dxl[ct][r] * kf;
+            v *= drop_factor_x(dce, eb + (uint32_t)(16 * ct + r) * CR_PHI);
+            dxl[ct][r] = v;
+        }
+}
+// lane = column `col` (< D) of row m with id `id`: its element of the float-atomic burst into the item and positional tables
+__device__ __forceinline__ void embed_row_atomics(const cr_embed_bwd_desc& sc, int id, int m, int col, int D, float g) {
+    const cr_embed_desc& e = sc.f;
+    if (sc.table_grad && !(e.zero_pad && id == 0)) atomicAdd(sc.table_grad + (size_t)id * D + col, g * e.scale);
+    if (sc.pos_grad) atomicAdd(sc.pos_grad + (size_t)(m % e.T) * D + col, g);
+}
+
+// =====================================================================================================
+// host side: argument checks of both files' entry points (`who`: the entry point's name, for the message)
+// =====================================================================================================
+// the pointer sets of a block: the feed-forward half (LN2, W1, W2) and / or the projection half (LN1, Wqkv)
+static int rb_check_pointers(const cr_block_bwd_desc* bd, bool ffn, bool qkv, const char* who) {
+    const cr_block_desc* d = &bd->f;
+    if (ffn) {
+        CR_REQUIRE(bd->d_o && d->hid && d->f_in && d->o && d->mask_ids && d->w1 && d->w2 && d->ln2_g, "%s: NULL pointer", who);
+        CR_REQUIRE(bd->g_w1 && bd->g_b1 && bd->g_w2 && bd->g_b2 && bd->g_ln2_g && bd->g_ln2_b, "%s: NULL gradient pointer", who);
+    }
+    if (qkv) {
+        CR_REQUIRE(bd->dqkv && bd->d_o && d->q_in && d->x && d->wqkv && d->ln1_g, "%s: NULL pointer", who);
+        CR_REQUIRE(bd->g_wqkv && bd->g_bqkv && bd->g_ln1_g && bd->g_ln1_b, "%s: NULL gradient pointer", who);
+        CR_REQUIRE(bd->dq_part == nullptr, "%s: dq_part (single-pass fp32 attention backward) is not taken", who);
+    }
+    return CR_OK;
+}
+// the stack's final LayerNorm, fused in front of the feed-forward chain
+static int rb_check_final_ln(const cr_ln_bwd_desc* n, const cr_block_bwd_desc* bd, const char* who) {
+    const cr_block_desc* d = &bd->f;
+    CR_REQUIRE(n->x == d->y && n->ldx == d->D && n->M == d->M && n->D == d->D, "%s: the LayerNorm's input must be this block's y", who);
+    CR_REQUIRE(n->gamma && n->dy && n->dgamma && n->dbeta && n->accumulate == 0, "%s: LayerNorm backward arguments", who);
+    CR_REQUIRE(n->slab_stride == bd->slab_stride && n->n_slabs == bd->n_slabs, "%s: the LayerNorm's slabs must be the block's", who);
+    CR_REQUIRE((size_t)n->M * n->lddy * 4 < ((size_t)1 << 32), "%s: dy of 4 GiB or more", who);
+    return CR_OK;
+}
+// the embedding recipe whose backward is applied to dx (what both forms ask of it; each adds its own on the destinations)
+static int rb_check_embed_recipe(const cr_embed_bwd_desc* sc, const cr_block_bwd_desc* bd, const char* who) {
+    const cr_embed_desc* e = &sc->f;
+    const cr_block_desc* d = &bd->f;
+    CR_REQUIRE(e->ids && e->M == d->M && e->D == d->D && e->ld_out == d->D && e->col_off == 0 && e->T > 0 && e->V > 0,
+               "%s: the embedding recipe must describe the block's dense input x", who);
+    CR_REQUIRE(!bd->dx_accumulate, "%s: dx_accumulate with a scatter (this kernel must be the only producer of dx)", who);
+    return CR_OK;
+}

@@ -20,9 +20,15 @@
 // Same inputs, outputs and slab layout as the cr_block_* entry points (castrec.h); results differ from them by the
 // rounding of the split products (~1e-5 relative).  Shapes: D <= 64 (D < 64: bias gradients from the ones column; D = 64:
 // from an all-ones product), T <= 224 (two rounds of 7 tiles).
+//
+// cr_rbwd.hpp holds what these kernels share with each other and with the one-launch kernel (cr_stack_bwd1.hip): the products and images,
+// r_tile_rows, r_zero, ffn_wgrad_accum, the embedding-backward recipe and its atomic burst, and the host's argument checks.  The row
+// chains themselves are written out here AND in b1_phase1 / b1_q_side / b1_k_side: a fix to one is a fix to both (DESIGN.md section 4,
+// "One row chain, two kernels", says why they are not one function, and which statement -- delta at one head -- differs on purpose).
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
+#include <type_traits>
 
 #include "cr_rbwd.hpp"
 
@@ -70,28 +76,19 @@ __global__ __launch_bounds__(SB_NT) void k_stack_ffn_bwd(SbArgs a) {
     const float scale1 = (d.drop_ffn1.rate > 0.0f) ? 1.0f / (1.0f - d.drop_ffn1.rate) : 1.0f;
     constexpr bool BIAS = DS == 64;                       // no spare column: bias gradients by an all-ones product
     f32x4 aw1[2], aw2[2], ab1[2], ab2[2], ag[4], ab[4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { aw1[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; aw2[j] = aw1[j]; ab1[j] = aw1[j]; ab2[j] = aw1[j]; }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) { ag[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; ab[ct] = ag[ct]; }
+    f32x4 agF[4], abF[4];                                 // final-LayerNorm gradient partials (has_ln)
+    r_zero(aw1, aw2, ab1, ab2);
+    r_zero(ag, ab, agF, abF);
     const int it = wave >> 1, jt0 = 2 * (wave & 1);       // this wave's tiles of the weight gradients
     // work items of this workgroup: (sequence n, round rd), n = blockIdx.x, + gridDim.x, ...; the inputs of the NEXT
     // item's tile are requested before the weight-gradient phase of the current one (and the first before the weights
     // are staged): a tile's five row blocks come from HBM, 2-3 us that nothing else would cover
     constexpr bool PF = DS == 50;                        // look-ahead loads only where the register budget allows
     RRaw rdy, rhid, rfin, ro, rq, ry;
-    f32x4 agF[4], abF[4];                                 // final-LayerNorm gradient partials (has_ln)
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) { agF[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; abF[ct] = agF[ct]; }
-    auto tile_rows = [&](int n, int rd, int& m, bool& rok) {
-        const int q = 16 * (rd * SB_TPR + wave) + (lane_now() & 15);
-        rok = q < T;
-        m = n * T + min(q, T - 1);
-    };
     auto issue = [&](int n, int rd) {
         if (n < a.B && wave < min(SB_TPR, a.nkt - rd * SB_TPR)) {
             int m; bool rok;
-            tile_rows(n, rd, m, rok);
+            r_tile_rows(n, rd * SB_TPR + wave, T, m, rok);
             const u32 mo = (u32)m * (u32)(4 * D);
             if (a.has_ln) {                                          // rows beyond T: zero gradient (they must not reach the LayerNorm sums)
                 r_issue(rdy, a.ln.dy, (u32)m * (u32)(4 * a.ln.lddy), dcx, rok);
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(SB_NT) void k_stack_ffn_bwd(SbArgs a) {
             if (wave < ntr) {
                 const int lg = lane_now() >> 4;
                 int m; bool rok;
-                tile_rows(n, rd, m, rok);
+                r_tile_rows(n, rd * SB_TPR + wave, T, m, rok);
                 const u32 mo = (u32)m * (u32)(4 * D);
                 const float msk = (rok && d.mask_ids[m] != 0) ? 1.0f : 0.0f;    // rows beyond T contribute nothing
                 f32x4 dy[4], g2[4], hid[4];
@@ -216,8 +213,7 @@ __global__ __launch_bounds__(SB_NT) void k_stack_ffn_bwd(SbArgs a) {
             SB_TS(3);
             __syncthreads();
             SB_TS(4);
-            wgrad_accum<SPLIT, BIAS>(aw2, ab2, Im, Im + SB_IMG, Im + IST, Im + IST + SB_IMG, ntr, it, jt0);                          // dW2 (+ db2) += hid^T g2
-            wgrad_accum<SPLIT, BIAS>(aw1, ab1, Im + 2 * IST, Im + 2 * IST + SB_IMG, Im + 3 * IST, Im + 3 * IST + SB_IMG, ntr, it, jt0);  // dW1 (+ db1) += f_in^T g1
+            ffn_wgrad_accum<SPLIT, BIAS>(aw2, ab2, aw1, ab1, Im, ntr, it, jt0);
             SB_TS(5);
             __syncthreads();
             SB_TS(6);
@@ -258,15 +254,10 @@ __global__ __launch_bounds__(SB_NT) void k_stack_qkv_bwd(SbArgs a) {
     // column-tile predicates are live values too, and the look-ahead registers on top of them spilled 270.)
     constexpr bool PF = DS == 50;
     RRaw rdq, rqin, rdo, rdk;
-    auto tile_rows = [&](int n, int rd, int& m, bool& rok) {
-        const int q = 16 * (rd * SB_TPR + wave) + (lane_now() & 15);
-        rok = q < T;
-        m = n * T + min(q, T - 1);
-    };
     auto issue = [&](int n, int rd) {
         if (n < a.B && wave < min(SB_TPR, a.nkt - rd * SB_TPR)) {
             int m; bool rok;
-            tile_rows(n, rd, m, rok);
+            r_tile_rows(n, rd * SB_TPR + wave, T, m, rok);
             const u32 mo = (u32)m * (u32)(4 * D);
             r_issue(rdq, bd.dqkv, mo, dcx, rok);                     // rows beyond T: zero gradients
             r_issue(rqin, d.q_in, mo, dcx);
@@ -286,10 +277,8 @@ __global__ __launch_bounds__(SB_NT) void k_stack_qkv_bwd(SbArgs a) {
     }
     constexpr bool BIAS = DS == 64;
     f32x4 awq[2], awk[2], awv[2], abq[2], abk[2], abv[2], ag[4], ab[4];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { awq[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; awk[j] = awq[j]; awv[j] = awq[j]; abq[j] = awq[j]; abk[j] = awq[j]; abv[j] = awq[j]; }
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct) { ag[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; ab[ct] = ag[ct]; }
+    r_zero(awq, awk, awv, abq, abk, abv);
+    r_zero(ag, ab);
     const int it = wave >> 1, jt0 = 2 * (wave & 1);
     __syncthreads();
 #pragma unroll 1
@@ -302,7 +291,7 @@ __global__ __launch_bounds__(SB_NT) void k_stack_qkv_bwd(SbArgs a) {
             if (!PF) issue(n, rd);
             if (active) {
                 int m; bool rok;
-                tile_rows(n, rd, m, rok);
+                r_tile_rows(n, rd * SB_TPR + wave, T, m, rok);
                 const u32 mo = (u32)m * (u32)(4 * D);
                 RRaw rdv, rx, rdx;
                 r_issue(rdv, bd.dqkv + 2 * MD, mo, dcx, rok);
@@ -354,19 +343,8 @@ __global__ __launch_bounds__(SB_NT) void k_stack_qkv_bwd(SbArgs a) {
                     // d_addend straight from the registers; for the table rows the tile goes through a wave-private fp32
                     // scratch (the image slot the second phase fills later) so that one row = one contiguous float-atomic burst.
                     const cr_embed_desc& e = a.sc.f;
-                    const DropCtx dce = drop_ctx(e.drop);
                     const int ln = lane_now(), li = ln & 15, lg = ln >> 4;
-                    const int mk = e.mask_ids ? e.mask_ids[m] : 1;
-                    const float kf = (rok && mk != 0) ? 1.0f : 0.0f;
-                    const uint32_t eb = ((e.drop.row_offset + (uint32_t)m) * (uint32_t)D + (uint32_t)(4 * lg)) * CR_PHI + dce.key;
-#pragma unroll
-                    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float v = dxl[ct][r] * kf;
-                            if (dce.on) v *= drop_factor_x(dce, eb + (uint32_t)(16 * ct + r) * CR_PHI);
-                            dxl[ct][r] = v;
-                        }
+                    r_embed_bwd(dxl, e, cr_step_request(e.drop), m, rok, D);
                     if (a.sc.d_addend) r_store(a.sc.d_addend, mo, dxl, rok, dcx);
                     if (a.sc.table_grad || a.sc.pos_grad) {
                         float* scr = scat + wave * (16 * 64);
@@ -382,10 +360,7 @@ __global__ __launch_bounds__(SB_NT) void k_stack_qkv_bwd(SbArgs a) {
                         for (int r = 0; r < nr; ++r) {
                             const int id = __shfl(my_id, r, 64);
                             const float g = scr[r * 64 + 4 * ((col >> 2) ^ r) + (col & 3)];
-                            if (col < D) {
-                                if (a.sc.table_grad && !(e.zero_pad && id == 0)) atomicAdd(a.sc.table_grad + (size_t)id * D + col, g * e.scale);
-                                if (a.sc.pos_grad) atomicAdd(a.sc.pos_grad + (size_t)((n * T + 16 * (rd * SB_TPR + wave) + r) % e.T) * D + col, g);
-                            }
+                            if (col < D) embed_row_atomics(a.sc, id, n * T + 16 * (rd * SB_TPR + wave) + r, col, D, g);
                         }
                     }
                 }
@@ -452,6 +427,17 @@ static int launch_qkv_bwd(const SbArgs& a, hipStream_t s) {
     return cr_check_launch("cr_stack_qkv_bwd");
 }
 
+// the instantiation of a hidden size and precision: D = 50 and 64 as constants, any other size at run time
+template <class F>
+static int sb_dispatch(int D, int precision, F&& launch) {
+    auto sized = [&](auto split) {
+        if (D == 50) return launch(split, std::integral_constant<int, 50>{});
+        if (D == 64) return launch(split, std::integral_constant<int, 64>{});
+        return launch(split, std::integral_constant<int, 0>{});
+    };
+    return precision == CR_PREC_BF16X3 ? sized(std::true_type{}) : sized(std::false_type{});
+}
+
 static int sb_args(SbArgs* a, const cr_block_bwd_desc* bd, int B, int T, int precision, const char* who) {
     const char* why = sb_unsupported(bd, B, T, precision);
     CR_REQUIRE(why == nullptr, "%s: unsupported (%s)", who, why ? why : "");
@@ -469,25 +455,18 @@ static int stack_ffn_bwd_any(const cr_block_bwd_desc* bd, const cr_ln_bwd_desc* 
     const cr_block_desc* d = &bd->f;
     CR_REQUIRE(heads == 1 || (heads == 2 && d->D == 64), "%s: attn_delta per head is formed for one head, or two heads at D = 64", who);
     a.heads = heads;
-    CR_REQUIRE(bd->d_o && d->hid && d->f_in && d->o && d->mask_ids && d->w1 && d->w2 && d->ln2_g, "%s: NULL pointer", who);
-    CR_REQUIRE(bd->g_w1 && bd->g_b1 && bd->g_w2 && bd->g_b2 && bd->g_ln2_g && bd->g_ln2_b, "%s: NULL gradient pointer", who);
+    if ((rc = rb_check_pointers(bd, true, false, who))) return rc;
     CR_REQUIRE(bd->attn_delta == nullptr || d->q_in != nullptr, "%s: attn_delta needs q_in", who);
     if (n) {
-        CR_REQUIRE(n->x == d->y && n->ldx == d->D && n->M == d->M && n->D == d->D, "%s: the LayerNorm's input must be this block's y", who);
-        CR_REQUIRE(n->gamma && n->dy && n->dgamma && n->dbeta && n->accumulate == 0, "%s: LayerNorm backward arguments", who);
-        CR_REQUIRE(n->slab_stride == bd->slab_stride && n->n_slabs == bd->n_slabs, "%s: the LayerNorm's slabs must be the block's", who);
-        CR_REQUIRE((size_t)n->M * n->lddy * 4 < ((size_t)1 << 32), "%s: dy of 4 GiB or more", who);
+        if ((rc = rb_check_final_ln(n, bd, who))) return rc;
         a.ln = *n;
         a.has_ln = 1;
     } else {
         CR_REQUIRE(bd->dy, "%s: dy is NULL", who);
     }
     a.ts = g_attn_ts_which == 8 ? g_attn_ts : nullptr;
-    const bool split = precision == CR_PREC_BF16X3;
     hipStream_t s = cr_stream(stream);
-    if (d->D == 50) return split ? launch_ffn_bwd<true, 50>(a, s) : launch_ffn_bwd<false, 50>(a, s);
-    if (d->D == 64) return split ? launch_ffn_bwd<true, 64>(a, s) : launch_ffn_bwd<false, 64>(a, s);
-    return split ? launch_ffn_bwd<true, 0>(a, s) : launch_ffn_bwd<false, 0>(a, s);
+    return sb_dispatch(d->D, precision, [&](auto split, auto ds) { return launch_ffn_bwd<decltype(split)::value, decltype(ds)::value>(a, s); });
 }
 extern "C" int cr_stack_ffn_bwd(const cr_block_bwd_desc* bd, int B, int T, int precision, void* stream) {
     return stack_ffn_bwd_any(bd, nullptr, B, T, 1, precision, stream, "cr_stack_ffn_bwd");
@@ -505,15 +484,11 @@ static int stack_qkv_bwd_any(const cr_block_bwd_desc* bd, const cr_embed_bwd_des
     int rc = sb_args(&a, bd, B, T, precision, who);
     if (rc) return rc;
     const cr_block_desc* d = &bd->f;
-    CR_REQUIRE(bd->dqkv && bd->d_o && d->q_in && d->x && d->wqkv && d->ln1_g, "%s: NULL pointer", who);
-    CR_REQUIRE(bd->g_wqkv && bd->g_bqkv && bd->g_ln1_g && bd->g_ln1_b, "%s: NULL gradient pointer", who);
-    CR_REQUIRE(bd->dq_part == nullptr, "%s: dq_part (single-pass fp32 attention backward) is not taken", who);
+    if ((rc = rb_check_pointers(bd, false, true, who))) return rc;
     if (sc) {
         const cr_embed_desc* e = &sc->f;
-        CR_REQUIRE(e->ids && e->M == d->M && e->D == d->D && e->ld_out == d->D && e->col_off == 0 && e->T > 0 && e->V > 0,
-                   "%s: the embedding recipe must describe the block's dense input x", who);
+        if ((rc = rb_check_embed_recipe(sc, bd, who))) return rc;
         CR_REQUIRE(sc->n_slabs == 0, "%s: small-table mode is not fused", who);
-        CR_REQUIRE(!bd->dx_accumulate, "%s: dx_accumulate is not supported (this kernel must be the only producer of dx)", who);
         CR_REQUIRE(sc->table_grad || sc->d_addend || sc->pos_grad, "%s: nothing to scatter into", who);
         CR_REQUIRE(sc->d_addend == nullptr || e->ld_add == d->D, "%s: d_addend must be dense [M, D]", who);
         a.sc = *sc;
@@ -521,11 +496,8 @@ static int stack_qkv_bwd_any(const cr_block_bwd_desc* bd, const cr_embed_bwd_des
     } else {
         CR_REQUIRE(bd->dx, "%s: dx is NULL", who);
     }
-    const bool split = precision == CR_PREC_BF16X3;
     hipStream_t s = cr_stream(stream);
-    if (d->D == 50) return split ? launch_qkv_bwd<true, 50>(a, s) : launch_qkv_bwd<false, 50>(a, s);
-    if (d->D == 64) return split ? launch_qkv_bwd<true, 64>(a, s) : launch_qkv_bwd<false, 64>(a, s);
-    return split ? launch_qkv_bwd<true, 0>(a, s) : launch_qkv_bwd<false, 0>(a, s);
+    return sb_dispatch(d->D, precision, [&](auto split, auto ds) { return launch_qkv_bwd<decltype(split)::value, decltype(ds)::value>(a, s); });
 }
 extern "C" int cr_stack_qkv_bwd(const cr_block_bwd_desc* bd, int B, int T, int precision, void* stream) {
     return stack_qkv_bwd_any(bd, nullptr, B, T, precision, stream, "cr_stack_qkv_bwd");

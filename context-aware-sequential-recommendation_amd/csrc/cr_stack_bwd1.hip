@@ -30,6 +30,10 @@
 // One gradient slab per SEQUENCE (slab n, the two sides write disjoint parameter ranges of it): B slabs instead of 2 B.
 // Fixed summation order, no atomics except the embedding scatter: bitwise reproducible like the kernels it replaces.
 // Shapes: one head, 8 <= D < 64 (bias gradients ride the ones column), T <= 224, bf16 arithmetic (split or plain).
+//
+// Shared with cr_stack_bwd.hip through cr_rbwd.hpp: r_tile_rows, r_zero, ffn_wgrad_accum (round loop), r_embed_bwd, embed_row_atomics and
+// the host's argument checks -- what could move without changing this kernel's instruction stream.  The row chain of b1_phase1 is a copy of
+// k_stack_ffn_bwd's and stays written out (any regrouping of it re-schedules the kernel: DESIGN.md section 4, "One row chain, two kernels").
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -241,11 +245,7 @@ __device__ __forceinline__ void b1_phase1(const B1Args& a, unsigned char* smem, 
     const int it = wave >> 1, jt0 = 2 * (wave & 1);
     RRaw rdy, rdy2, rhid, rfin, ro, rq, ry;               // rq: q_in (delta); rfin: f_in (Q side) / the tile's Q rows (K side)
     const size_t MD = (size_t)d.M * D;
-    auto tile_rows = [&](int rd, int& m, bool& rok) {
-        const int q = 16 * (rd * SB_TPR + wave) + (lane_now() & 15);
-        rok = q < T;
-        m = n * T + min(q, T - 1);
-    };
+    auto tile_rows = [&](int rd, int& m, bool& rok) { r_tile_rows(n, rd * SB_TPR + wave, T, m, rok); };
     // the rows of a tile in two halves: what the chain opens with (dy, dy2, y, hid), and what its end needs (f_in / Q, o, q_in)
     auto issue_a = [&](int rd) {
         if (rd * SB_TPR < B1_NKT(DS, a) && wave < min(SB_TPR, B1_NKT(DS, a) - rd * SB_TPR)) {
@@ -422,8 +422,7 @@ __device__ __forceinline__ void b1_phase1(const B1Args& a, unsigned char* smem, 
             if (QSIDE) {
                 __syncthreads();
                 B1_TS(25);
-                wgrad_accum<SPLIT, BIAS>(aw2, aw2b, Im, Im + SB_IMG, Im + IST, Im + IST + SB_IMG, ntr, it, jt0);                          // dW2 (+ db2) += hid^T g2
-                wgrad_accum<SPLIT, BIAS>(aw1, aw1b, Im + 2 * IST, Im + 2 * IST + SB_IMG, Im + 3 * IST, Im + 3 * IST + SB_IMG, ntr, it, jt0);  // dW1 (+ db1) += f_in^T g1
+                ffn_wgrad_accum<SPLIT, BIAS>(aw2, aw2b, aw1, aw1b, Im, ntr, it, jt0);
                 B1_TS(26);
                 __syncthreads();
                 B1_TS(27);
@@ -438,6 +437,7 @@ __device__ __forceinline__ void b1_phase1(const B1Args& a, unsigned char* smem, 
         const int ntr = min(SB_TPR, B1_NKT(DS, a) - (R - 1) * SB_TPR);
         __syncthreads();
         B1_TS(10);
+        // (ffn_wgrad_accum's two lines, written out: through the helper the headline instantiation's schedule moved here)
         wgrad_accum<SPLIT, BIAS>(aw2, aw2b, Im, Im + SB_IMG, Im + IST, Im + IST + SB_IMG, ntr, it, jt0);
         wgrad_accum<SPLIT, BIAS>(aw1, aw1b, Im + 2 * IST, Im + 2 * IST + SB_IMG, Im + 3 * IST, Im + 3 * IST + SB_IMG, ntr, it, jt0);
         __syncthreads();
@@ -451,24 +451,6 @@ __device__ __forceinline__ void b1_phase1(const B1Args& a, unsigned char* smem, 
     (void)MD; (void)part; (void)partF;
 }
 
-// ---- the embedding backward of a partial of dx, phase-2 half: g = partial * mask * keep / (1 - rate) in the registers ----
-// (cr_embed_bwd's recipe; the rows then wait in `buf` -- d_addend where the graph has one, else the dx buffer -- for phase 3)
-__device__ __forceinline__ void b1_scatter_prep(const B1Args& a, f32x4 (&dxl)[4], int m, bool rok, int D, uint32_t step_emb) {
-    const cr_embed_desc& e = a.sc.f;
-    const DropCtx dce = drop_ctx(e.drop, step_emb);
-    const int lg = lane_now() >> 4;
-    const int mk = e.mask_ids ? e.mask_ids[m] : 1;
-    const float kf = (rok && mk != 0) ? 1.0f : 0.0f;
-    const uint32_t eb = ((e.drop.row_offset + (uint32_t)m) * (uint32_t)D + (uint32_t)(4 * lg)) * CR_PHI + dce.key;
-#pragma unroll
-    for (int ct = 0; ct < 4; ++ct)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            float v = dxl[ct][r] * kf;
-            v *= drop_factor_x(dce, eb + (uint32_t)(16 * ct + r) * CR_PHI);
-            dxl[ct][r] = v;
-        }
-}
 // last thing a side does: the waiting rows of sequence n, lane = column: one contiguous float-atomic burst per table row.
 // A wave takes 16 rows at a time: their ids and gradient rows are requested together, then the atomics go out back to back
 // and the wave ends with them in flight (nothing in the kernel waits behind them: placed in front of phase 3 they held its
@@ -490,10 +472,7 @@ __device__ __forceinline__ void b1_scatter_rows(const B1Args& a, const float* bu
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int id = __shfl(my_id, r, 64);
-            if (r < nr && col < D) {
-                if (a.sc.table_grad && !(e.zero_pad && id == 0)) atomicAdd(a.sc.table_grad + (size_t)id * D + col, g[r] * e.scale);
-                if (a.sc.pos_grad) atomicAdd(a.sc.pos_grad + (size_t)((m0 + r) % e.T) * D + col, g[r]);
-            }
+            if (r < nr && col < D) embed_row_atomics(a.sc, id, m0 + r, col, D, g[r]);
         }
     }
 }
@@ -943,8 +922,7 @@ __device__ __forceinline__ void b1_q_side(const B1Args& a, unsigned char* smem, 
             for (int ct = 0; ct < 4; ++ct) dqin[ct] += dO[ct];
         }
         f32x4 x[4], dxl[4], ag[4], ab[4];
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) { ag[ct] = (f32x4){0.f, 0.f, 0.f, 0.f}; ab[ct] = ag[ct]; }
+        r_zero(ag, ab);
         r_finish(x, rx, dcx);
         // the NEXT tile's inputs, under the LayerNorm backward and the stores.  Behind the chain's own loads, and only where a next
         // tile exists: an unconditional request in front of them (static load counts, no full drain at the first use) made single
@@ -959,7 +937,7 @@ __device__ __forceinline__ void b1_q_side(const B1Args& a, unsigned char* smem, 
             for (int ct = 0; ct < 4; ++ct) dxl[ct] += old[ct];
         }
         if (ar.scatter) {
-            b1_scatter_prep(ar, dxl, m, rok, D, steps.emb);
+            r_embed_bwd(dxl, ar.sc.f, steps.emb, m, rok, D);      // (the rows then wait in sbuf -- d_addend where the graph has one, else dx -- for phase 3)
             r_store(ar.sbuf, mo, dxl, rok, dcx);
         } else {
             r_store(ar.bd.dx, mo, dxl, rok, dcx);
@@ -981,8 +959,7 @@ __device__ __forceinline__ void b1_q_side(const B1Args& a, unsigned char* smem, 
     if (tt1 < B1_NKT(DS, a)) r_issue(rg1, dQg, mo1, dcx, 16 * tt1 + li < T);
     // ---- phase 3: dWq dbq from images of q_in and dQ, dgamma1 dbeta1; then the scatter of this side's partial ----
     f32x4 awq[2], nob[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) { awq[j] = (f32x4){0.f, 0.f, 0.f, 0.f}; nob[j] = awq[j]; }
+    r_zero(awq, nob);
     const int it = wave >> 1, jt0 = 2 * (wave & 1);
     // ONE round: the images of q_in and dQ over all tiles (2 x 14 tiles x hi, lo) are exactly the image area
     __bf16* Gm = reinterpret_cast<__bf16*>(smem + L::MATB);
@@ -1315,7 +1292,7 @@ __device__ __forceinline__ void b1_k_side(const B1Args& a, unsigned char* smem, 
             r_gemm_t<SPLIT, true>(dxp, Wi + WST, Wi + WST + ST_WIMG, gh, gl);
         }
         if (ar.scatter) {
-            b1_scatter_prep(ar, dxp, m, rok, D, steps.emb);
+            r_embed_bwd(dxp, ar.sc.f, steps.emb, m, rok, D);
             r_store(ar.sbuf2, mo, dxp, rok, dcx);
         } else {
             r_store(ar.dx2, mo, dxp, rok, dcx);
@@ -1505,17 +1482,10 @@ extern "C" int cr_stack_block_bwd(const cr_block_bwd_desc* bd, const cr_attn_des
     a.bd = *bd; a.ad = *ad;
     a.B = B; a.T = T; a.nkt = (T + 15) / 16;
     const cr_block_desc* d = &bd->f;
-    CR_REQUIRE(bd->d_o && bd->dqkv && d->hid && d->f_in && d->o && d->q_in && d->x && d->mask_ids && d->w1 && d->w2 && d->wqkv && d->ln1_g && d->ln2_g,
-               "cr_stack_block_bwd: NULL pointer");
-    CR_REQUIRE(bd->g_w1 && bd->g_b1 && bd->g_w2 && bd->g_b2 && bd->g_ln2_g && bd->g_ln2_b && bd->g_wqkv && bd->g_bqkv && bd->g_ln1_g && bd->g_ln1_b,
-               "cr_stack_block_bwd: NULL gradient pointer");
-    CR_REQUIRE(bd->dq_part == nullptr, "cr_stack_block_bwd: dq_part is not taken");
+    if (int rc = rb_check_pointers(bd, true, true, "cr_stack_block_bwd")) return rc;
     a.dy2 = x->dy2; a.dx2 = x->dx2; a.ln_dy2 = x->lnf_dy2; a.d_addend2 = x->d_addend2;
     if (lnf) {
-        CR_REQUIRE(lnf->x == d->y && lnf->ldx == d->D && lnf->M == d->M && lnf->D == d->D, "cr_stack_block_bwd: the LayerNorm's input must be this block's y");
-        CR_REQUIRE(lnf->gamma && lnf->dy && lnf->dgamma && lnf->dbeta && lnf->accumulate == 0, "cr_stack_block_bwd: LayerNorm backward arguments");
-        CR_REQUIRE(lnf->slab_stride == bd->slab_stride && lnf->n_slabs == bd->n_slabs, "cr_stack_block_bwd: the LayerNorm's slabs must be the block's");
-        CR_REQUIRE((size_t)lnf->M * lnf->lddy * 4 < ((size_t)1 << 32), "cr_stack_block_bwd: dy of 4 GiB or more");
+        if (int rc = rb_check_final_ln(lnf, bd, "cr_stack_block_bwd")) return rc;
         a.ln = *lnf;
         a.has_ln = 1;
     } else {
@@ -1524,9 +1494,7 @@ extern "C" int cr_stack_block_bwd(const cr_block_bwd_desc* bd, const cr_attn_des
     }
     if (sc) {
         const cr_embed_desc* e = &sc->f;
-        CR_REQUIRE(e->ids && e->M == d->M && e->D == d->D && e->ld_out == d->D && e->col_off == 0 && e->T > 0 && e->V > 0,
-                   "cr_stack_block_bwd: the embedding recipe must describe the block's dense input x");
-        CR_REQUIRE(!bd->dx_accumulate, "cr_stack_block_bwd: dx_accumulate with a scatter (this kernel must be the only producer of dx)");
+        if (int rc = rb_check_embed_recipe(sc, bd, "cr_stack_block_bwd")) return rc;
         // (table_grad, pos_grad and d_addend all NULL is the occurrence-index form: the masked, dropped-out partial rows are LEFT in
         //  dx / dx2 -- d_addend / d_addend2 with an addend -- for cr_table_grad / cr_adam_desc.tg to gather; no atomics here)
         if (sc->n_slabs > 0) {
