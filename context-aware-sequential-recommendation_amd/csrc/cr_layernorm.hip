@@ -97,7 +97,9 @@ __global__ __launch_bounds__(1024) void k_ln_bwd(cr_ln_bwd_desc d) {
             dy[i] = (c < d.D && act) ? d.dy[(size_t)mm * d.lddy + c] : 0.0f;
             s += x[i];
         }
-        const float mean = row_sum<LPR>(s) * invD;
+        // divided like the forward, not multiplied by 1/D: `x - s * invD` contracts into one fma whose unrounded product leaves a constant
+        // row (mean exact, xhat = 0 in the forward) a residue of ~1e-8 that rstd = 1e4 turns into xhat ~ 1e-3 in dgamma
+        const float mean = row_sum<LPR>(s) / (float)d.D;
         float v = 0.0f;
 #pragma unroll
         for (int i = 0; i < MAXC; ++i) {

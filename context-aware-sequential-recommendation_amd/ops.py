@@ -54,10 +54,10 @@ def embed_fwd(ids, table, T, out, ld_out, col_off=0, zero_pad=True, scale=1.0, p
     return d
 
 
-def embed_bwd(fdesc, dout, table_grad=None, pos_grad=None, d_addend=None, slab_stride=0, n_slabs=0):
+def embed_bwd(fdesc, dout, table_grad=None, pos_grad=None, d_addend=None, slab_stride=0, n_slabs=0, out2=None):
     f = L.EmbedDesc.from_buffer_copy(fdesc)
     f.out = _p(dout)
-    d = L.EmbedBwdDesc(f, _p(table_grad), _p(pos_grad), _p(d_addend), slab_stride, n_slabs)
+    d = L.EmbedBwdDesc(f, _p(table_grad), _p(pos_grad), _p(d_addend), slab_stride, n_slabs, _p(_f32(out2, "out2")))
     L.call("cr_embed_bwd", C.byref(d), _stream())
 
 
