@@ -638,3 +638,254 @@ extern "C" int cr_score_topk(const cr_topk_desc* d, void* stream) {
     });
     return cr_check_launch("cr_score_topk");
 }
+
+// ---- top-K over per-query candidate lists (castrec.h cr_score_topk_lists) -------------------------------------------------------------
+// "The best K among THIS row's candidates."  Grid: (query b) x (segment of the row's list), 256 threads.  Every wave forms the query's
+// B fragments once the way k_topk_merge does for the excluded rows -- row b in every lane, so the query stands in every column -- and
+// takes 16 candidates per round: lane li reads cand[p + li], tk_src_row gives that row's A fragments (zeros for an id outside
+// 1 .. V-1, whose row is not read), one tk_tile gives the 16 scores, item 4 lg + r in c[r] of every lane of group lg.  The lane with
+// li == 4 lg + r owns that item: it holds the id it loaded and picks c[r].  Ids are requested two rounds ahead and rows one round
+// ahead, so a round's gather is in flight while the round before it is selected.  Selection is the sweep's on a TkLds of one query
+// (threshold, TK_CAP buffer, tk_fold by wave 0 whenever the buffer could not take another round of 64 and after the last round);
+// beside it every score is compared with the target's (integer counts, and a "target seen" flag).  No exclusions here: the host
+// subtracts them from the lists, so TkArgs.off stays NULL for the fold.  A score has the sweep's bits: one item row, one query, tk_tile.
+// One segment: the workgroup writes the final outputs.  More: its sorted list, count and flag go to the workspace, k_topk_merge (as it
+// is, without targets) runs the tournament and k_topk_lists_rank sums the counts.
+namespace {
+
+struct TlArgs {
+    TkArgs a;                               // q, ldq, src, B, K, tgt, part_*, top_*, rank; off = excl = NULL; n_chunks = segments
+    const int64_t* coff;                    // device copy of cand_off
+    const int32_t* cand;
+    int32_t* part_seen;                     // [n_seg, B]: the segment held the target
+    int seg_len;
+};
+
+template <int NK, bool SPLIT, bool IDX>
+__global__ __launch_bounds__(256) void k_topk_lists(TlArgs g) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const TkArgs& a = g.a;
+    const int K = a.K, V = a.src.V;
+    const TkLds l = tk_lds(smem, 1, NK, K);                // one query: no operand image (the fragments stay in registers)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, li = lane & 15, lg = lane >> 4;
+    const int b = blockIdx.x;
+    const int64_t p0 = g.coff[b] + (int64_t)blockIdx.y * g.seg_len;
+    const int64_t p1 = min(g.coff[b + 1], p0 + g.seg_len);
+    const int n_rounds = p1 > p0 ? (int)((p1 - p0 + 63) / 64) : 0;
+    int t = a.tgt ? a.tgt[b] : -1;
+    t = (t >= 1 && t < V) ? t : -1;
+
+    bf8 bh[NK], bl[NK];
+    {
+        float qv[NK][8];
+        tk_row_issue<NK>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.src.D);
+        tk_row_finish<NK, SPLIT>(qv, a.q, a.ldq, b, true, b == a.B - 1, a.src.D, bh, bl);
+    }
+    for (int i = threadIdx.x; i < K; i += 256) { l.top_s[i] = -INFINITY; l.top_id[i] = TK_PAD; }
+    if (threadIdx.x == 0) { l.cnt[0] = 0; l.thr[0] = -INFINITY; l.st[0] = 0.0f; l.tq[0] = 0; }      // tq: "target seen"
+    if (wave == 0 && t > 0) {                              // the target's score: its row in every lane, one tile
+        bf8 ah[NK], al[NK];
+        tk_src_row<NK, SPLIT, IDX>(a.src, t, true, ah, al);
+        const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+        if (lane == 0) l.st[0] = c[0];
+    }
+    __syncthreads();
+    const float s_t = l.st[0];
+
+    // candidate p0 + 64 round + 16 wave + li of the segment; 0 (not eligible) past its end
+    auto cand_at = [&](int round) {
+        const int64_t p = p0 + (int64_t)round * 64 + wave * 16 + li;
+        return p < p1 ? g.cand[p] : 0;
+    };
+    int id_c = cand_at(0), id_n = cand_at(1);
+    float v[NK][8];                                        // the round ahead: table rows in flight, or (IDX) the fragments themselves
+    bf8 nh[NK], nl[NK];
+    if (n_rounds > 0) {
+        const bool rok = id_c >= 1 && id_c < V;
+        if constexpr (IDX) tk_src_row<NK, SPLIT, true>(a.src, id_c, rok, nh, nl);
+        else tk_row_issue<NK>(v, a.src.table, a.src.D, id_c, rok, id_c == V - 1, a.src.D);
+    }
+    int rk = 0;
+    bool seen = false;
+    for (int round = 0; round < n_rounds; ++round) {
+        const int id = id_c;
+        const bool rok = id >= 1 && id < V;
+        bf8 ah[NK], al[NK];
+        if constexpr (IDX) {
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                ah[ks] = nh[ks];
+                if (SPLIT) al[ks] = nl[ks];
+            }
+        } else {
+            tk_row_finish<NK, SPLIT>(v, a.src.table, a.src.D, id, rok, id == V - 1, a.src.D, ah, al);
+        }
+        if (round + 1 < n_rounds) {
+            id_c = id_n;
+            const bool nok = id_c >= 1 && id_c < V;
+            if constexpr (IDX) tk_src_row<NK, SPLIT, true>(a.src, id_c, nok, nh, nl);
+            else tk_row_issue<NK>(v, a.src.table, a.src.D, id_c, nok, id_c == V - 1, a.src.D);
+            id_n = cand_at(round + 2);
+        }
+        const f32x4 c = tk_tile<NK, SPLIT>(ah, al, bh, bl);
+        const int r = li - 4 * lg;
+        if (r >= 0 && r < 4 && rok) {                      // the lane that owns item 4 lg + r = li of the tile
+            const float s = tk_pick(c, r);
+            if (s >= l.thr[0]) {
+                const int k = atomicAdd(&l.cnt[0], 1);
+                l.buf_s[k] = s;
+                l.buf_id[k] = id;
+            }
+            if (t > 0) {
+                if (id == t) seen = true;
+                else rk += (s > s_t || (s == s_t && id < t)) ? 1 : 0;
+            }
+        }
+        __syncthreads();
+        const int n = l.cnt[0];
+        if (wave == 0 && n > (round + 1 == n_rounds ? 0 : TK_CAP - 64)) tk_fold(l, 0, n, K, a, b, 0);
+        __syncthreads();
+    }
+
+    // every buffer is empty now (cnt = 0): the counts of the target's betters are summed there
+    if (a.tgt) {
+        if (rk) atomicAdd(&l.cnt[0], rk);                  // integer sums: the same total in any order
+        if (seen) l.tq[0] = 1;
+        __syncthreads();
+    }
+    if (a.n_chunks == 1) {
+        for (int k = threadIdx.x; k < K; k += 256) {
+            const int id = l.top_id[k];
+            a.top_ids[(size_t)b * K + k] = id == TK_PAD ? 0 : id;
+            a.top_scores[(size_t)b * K + k] = l.top_s[k];
+        }
+        if (a.tgt && threadIdx.x == 0) a.rank[b] = l.tq[0] ? l.cnt[0] : -1;
+    } else {
+        const size_t slot = (size_t)blockIdx.y * a.B + b;
+        for (int k = threadIdx.x; k < K; k += 256) {
+            a.part_s[slot * K + k] = l.top_s[k];
+            a.part_id[slot * K + k] = l.top_id[k];
+        }
+        if (a.tgt && threadIdx.x == 0) { a.part_cnt[slot] = l.cnt[0]; g.part_seen[slot] = l.tq[0]; }
+    }
+}
+
+// the rank of a segmented row: the segments' counts summed; -1 unless exactly one segment held the target
+__global__ __launch_bounds__(256) void k_topk_lists_rank(const int32_t* part_cnt, const int32_t* part_seen, int B, int n_seg, int32_t* rank) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    int cnt = 0, seen = 0;
+    for (int s = 0; s < n_seg; ++s) {
+        cnt += part_cnt[(size_t)s * B + b];
+        seen += part_seen[(size_t)s * B + b];
+    }
+    rank[b] = seen == 1 ? cnt : -1;
+}
+
+// the partition of lists whose longest has max_len candidates: segments of seg_len candidates, n_seg of them
+struct TlGeom {
+    int n_seg, seg_len;
+};
+bool tl_geometry(int B, int64_t max_len, TlGeom& g) {
+    if (B < 1 || max_len < 0 || max_len > 0x7fffffff) return false;
+    int64_t n = std::min<int64_t>(TK_MAX_CHUNKS, (max_len + 2047) / 2048);
+    n = std::max<int64_t>(1, std::min<int64_t>(n, std::max(1, (1024 + B - 1) / B)));
+    g.seg_len = (int)std::max<int64_t>(1, (max_len + n - 1) / n);
+    g.n_seg = (int)std::max<int64_t>(1, (max_len + g.seg_len - 1) / g.seg_len);
+    return true;
+}
+
+// workspace: [offsets (B + 1) int64 | with more than one segment: lists n_seg B K (float, int32), counts and flags n_seg B]
+size_t tl_workspace(int B, const TlGeom& g, int K) {
+    const size_t nb = g.n_seg > 1 ? (size_t)g.n_seg * B : 0;
+    return cr_align256(8 * ((size_t)B + 1)) + 2 * cr_align256(nb * K * 4) + 2 * cr_align256(nb * 4);
+}
+
+template <int NK, bool SPLIT, bool IDX>
+void tl_launch(const TlArgs& g, hipStream_t st) {
+    const TkArgs& a = g.a;
+    hipLaunchKernelGGL((k_topk_lists<NK, SPLIT, IDX>), dim3(a.B, a.n_chunks), dim3(256), tk_lds_bytes(1, NK, a.K), st, g);
+    if (a.n_chunks == 1) return;
+    TkArgs m = a;
+    m.tgt = nullptr;                                       // the tournament alone: the ranks need the segments' flags
+    hipLaunchKernelGGL((k_topk_merge<NK, SPLIT, IDX>), dim3((a.B + 3) / 4), dim3(256), 0, st, m);
+    if (a.tgt) hipLaunchKernelGGL(k_topk_lists_rank, dim3((a.B + 255) / 256), dim3(256), 0, st, a.part_cnt, g.part_seen, a.B, a.n_chunks, a.rank);
+}
+
+}  // namespace
+
+extern "C" int cr_topk_lists_segments(int B, int64_t max_len) {
+    TlGeom g;
+    return tl_geometry(B, max_len, g) ? g.n_seg : 0;
+}
+
+extern "C" size_t cr_score_topk_lists_workspace(int B, int64_t max_len, int D, int K) {
+    TlGeom g;
+    if (D < 8 || D > 256 || K < 1 || K > CR_TOPK_MAX || !tl_geometry(B, max_len, g)) return 0;
+    return tl_workspace(B, g, K);
+}
+
+extern "C" int cr_score_topk_lists(const cr_topk_lists_desc* d, void* stream) {
+    const char* who = "cr_score_topk_lists";
+    CR_REQUIRE(d, "cr_score_topk_lists: NULL descriptor");
+    CR_REQUIRE(d->K >= 1 && d->K <= CR_TOPK_MAX, "cr_score_topk_lists: K=%d outside 1 .. CR_TOPK_MAX (%d)", d->K, CR_TOPK_MAX);
+    CR_REQUIRE(d->B >= 1 && d->V >= 1, "cr_score_topk_lists: B=%d, V=%d must be >= 1", d->B, d->V);
+    if (const int rc = tk_check_shape(who, d->V, d->D, d->precision)) return rc;
+    CR_REQUIRE(d->ld >= d->D, "cr_score_topk_lists: ld=%d < D=%d", d->ld, d->D);
+    if (d->index) CR_REQUIRE(d->query, "cr_score_topk_lists: NULL query");
+    else CR_REQUIRE(d->query && d->table, "cr_score_topk_lists: NULL query or table");
+    CR_REQUIRE(d->top_ids && d->top_scores, "cr_score_topk_lists: NULL output (top_ids / top_scores)");
+    CR_REQUIRE(!d->targets || d->rank, "cr_score_topk_lists: targets given but rank is NULL");
+    CR_REQUIRE(d->cand_off, "cr_score_topk_lists: NULL cand_off");
+    CR_REQUIRE(d->cand_off[0] >= 0, "cr_score_topk_lists: cand_off[0]=%lld < 0", (long long)d->cand_off[0]);
+    int64_t max_len = 0;
+    for (int b = 0; b < d->B; ++b) {
+        const int64_t n = d->cand_off[b + 1] - d->cand_off[b];
+        CR_REQUIRE(n >= 0, "cr_score_topk_lists: cand_off decreases at row %d (%lld -> %lld)", b, (long long)d->cand_off[b],
+                   (long long)d->cand_off[b + 1]);
+        CR_REQUIRE(n <= 0x7fffffff, "cr_score_topk_lists: row %d names %lld candidates, 2^31 - 1 at most", b, (long long)n);
+        max_len = std::max(max_len, n);
+    }
+    CR_REQUIRE(d->cand_ids || max_len == 0, "cr_score_topk_lists: cand_off names ids but cand_ids is NULL");
+    if (d->index) {
+        const int planes = tk_index_planes(d->index_precision);
+        CR_REQUIRE(planes != 0, "cr_score_topk_lists: unknown index_precision %d", d->index_precision);
+        CR_REQUIRE(planes == 2 || d->precision == CR_PREC_BF16,
+                   "cr_score_topk_lists: a plain bf16 index serves precision CR_PREC_BF16 only, not %d", d->precision);
+        const size_t ib = cr_topk_index_bytes(d->V, d->D, d->index_precision);
+        CR_REQUIRE(d->index_bytes == ib, "cr_score_topk_lists: index_bytes=%zu, cr_topk_index_bytes(V=%d, D=%d) says %zu", d->index_bytes,
+                   d->V, d->D, ib);
+    }
+    TlGeom g;
+    CR_REQUIRE(tl_geometry(d->B, max_len, g), "cr_score_topk_lists: unsupported shape");
+    const size_t need = tl_workspace(d->B, g, d->K);
+    CR_REQUIRE(d->workspace && d->workspace_bytes >= need,
+               "cr_score_topk_lists: workspace of %zu bytes, cr_score_topk_lists_workspace says %zu", d->workspace ? d->workspace_bytes : (size_t)0,
+               need);
+
+    hipStream_t st = cr_stream(stream);
+    unsigned char* w = static_cast<unsigned char*>(d->workspace);
+    int64_t* off = reinterpret_cast<int64_t*>(w);
+    const hipError_t e = hipMemcpyAsync(off, d->cand_off, 8 * ((size_t)d->B + 1), hipMemcpyHostToDevice, st);
+    if (e != hipSuccess) return cr_set_error(CR_ERR_HIP, "cr_score_topk_lists: offsets copy: %s", hipGetErrorString(e));
+    w += cr_align256(8 * ((size_t)d->B + 1));
+    const size_t nb = g.n_seg > 1 ? (size_t)g.n_seg * d->B : 0;
+    TlArgs t;
+    TkArgs& a = t.a;
+    a.q = d->query; a.ldq = d->ld; a.src = tk_source(d->table, d->index, d->V, d->D);
+    a.B = d->B; a.K = d->K;
+    a.off = nullptr; a.excl = nullptr; a.tgt = d->targets; a.st_ws = nullptr;
+    a.part_s = reinterpret_cast<float*>(w); w += cr_align256(nb * d->K * 4);
+    a.part_id = reinterpret_cast<int32_t*>(w); w += cr_align256(nb * d->K * 4);
+    a.part_cnt = reinterpret_cast<int32_t*>(w); w += cr_align256(nb * 4);
+    t.part_seen = reinterpret_cast<int32_t*>(w);
+    a.top_ids = d->top_ids; a.top_scores = d->top_scores; a.rank = d->rank;
+    a.chunk = 0; a.n_chunks = g.n_seg;
+    t.coff = off; t.cand = d->cand_ids; t.seg_len = g.seg_len;
+    const bool split = d->precision != CR_PREC_BF16;       // CR_PREC_F32: the bf16x3 products (fp32-grade)
+    tk_dispatch(tk_nk(d->D), split, [&](auto nk, auto sp) {
+        if (d->index) tl_launch<nk, sp, true>(t, st);
+        else tl_launch<nk, sp, false>(t, st);
+    });
+    return cr_check_launch("cr_score_topk_lists");
+}

@@ -1664,7 +1664,7 @@ class Engine:
         O.test_logits(self.seq_emb, self.seq_emb.shape[1], self.p("item_emb"), cand, self.B, self.T, self.D, out)
         return out
 
-    def topk(self, k, excl_off=None, excl_ids=None, targets=None, index=None):
+    def topk(self, k, excl_off=None, excl_ids=None, targets=None, index=None, candidates=None):
         """Full-catalogue top-k of the last position of every sequence (after forward_eval): (ids [B, k] int32, scores [B, k] fp32,
         rank [B] int32 or None) as device tensors.  excl_off: host int64 [B + 1] CSR offsets into excl_ids (int32, host or device) --
         the items each row must not return nor count in its target's rank; targets: [B] ids whose rank among the eligible items is
@@ -1672,9 +1672,17 @@ class Engine:
         test_logits keeps its exact fp32 form.  index: an ItemIndex of this engine's item table (castrec_amd.index): the scores come
         from it instead of the table, with the same bits.  castrec.h cr_score_topk.  index may also be an ItemSubset of the table:
         the best k among its items only -- ids, exclusions and targets stay global ids, a target outside the subset has rank -1 and
-        ranks count the subset's eligible items."""
+        ranks count the subset's eligible items.  candidates: one iterable of item ids per row, or a prebuilt (off, ids) pair
+        (castrec_amd.index.candidates_for): the best k among each row's own candidates minus its exclusions (castrec.h
+        cr_score_topk_lists), from the table or from an ItemIndex -- not together with an ItemSubset."""
         from . import index as X
         V, D = self.itemnum + 1, self.D
+        cand = (None, None)
+        if candidates is not None:
+            if isinstance(index, X.ItemSubset):
+                raise ValueError("one filter per call: candidates= and an ItemSubset exclude each other")
+            cand = X.candidates_for(candidates, self.B, V, excl_off, excl_ids)
+            excl_off = excl_ids = None
         if isinstance(index, X.ItemSubset) and (index.parent_V, index.D) != (V, D):
             raise ValueError("subset of a [%d, %d] table, the engine's item table is [%d, %d]" % (index.parent_V, index.D, V, D))
         if isinstance(index, X.ItemIndex) and (index.V, index.D) != (V, D):
@@ -1682,7 +1690,8 @@ class Engine:
         ld = self.seq_emb.shape[1]
         query = self.seq_emb[self.T - 1:]                 # row b of the queries: seq_emb row b * T + T - 1
         return X.search(query, self.T * ld, self.B, k, self.p("item_emb") if index is None else index,
-                        L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3, self, excl_off, excl_ids, targets)
+                        L.PREC_BF16 if self.attn_precision == "bf16" else L.PREC_BF16X3, self, excl_off, excl_ids, targets,
+                        cand_off=cand[0], cand_ids=cand[1])
 
     # ---- parameter / gradient access (tests, checkpoints) ----------------------------------------
     def get_params(self):

@@ -10,6 +10,11 @@ ItemSubset: "the best k among these items" for a whole batch -- the allowed rows
 cr_topk_index_gather) that the same search runs over; global ids in and out, the score bits of the full search.
 
     ids, scores = ix.search(queries, k=10, allow=in_stock)      # or: sub = ix.subset(in_stock); sub.search(queries, k=10)
+
+Per-row candidate lists: "the best k among THIS row's candidates" (castrec.h cr_score_topk_lists) -- the rows a list names are gathered
+and scored, so the cost follows the lists; global ids, the score bits of the full search.
+
+    ids, scores = ix.search(queries, k=10, candidates=[row_0_ids, row_1_ids, ...])      # combines with exclude=
 """
 import numpy as np
 import torch
@@ -46,6 +51,53 @@ def excl_csr(rows, B):
     off[1:] = np.cumsum([len(r) for r in rows])
     ids = np.concatenate(rows).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
     return off, ids
+
+
+# ---- per-row candidate lists (castrec.h cr_score_topk_lists; pure numpy) -----------------------------------------------------------------
+def candidate_csr(rows, B, V, exclude=None):
+    """One iterable of item ids per row -> (host int64 offsets [B + 1], int32 ids) as cr_score_topk_lists takes them: each row unique
+    and ascending, minus the ids of the row's `exclude` (None, or one iterable per row; ids that are no candidates are ignored).
+    Empty rows are allowed.  ValueError for a wrong number of rows or a candidate outside 1 .. V-1."""
+    rows = [np.unique(np.asarray(r if isinstance(r, np.ndarray) else list(r), np.int64).ravel()) for r in rows]
+    if len(rows) != B:
+        raise ValueError("candidates has %d rows for a batch of %d" % (len(rows), B))
+    for b, r in enumerate(rows):
+        if r.size and (r[0] < 1 or r[-1] > V - 1):
+            raise ValueError("candidates must be item ids in 1 .. %d, row %d holds %d .. %d" % (V - 1, b, r[0], r[-1]))
+    if exclude is not None:
+        exclude = [np.asarray(e if isinstance(e, np.ndarray) else list(e), np.int64).ravel() for e in exclude]
+        if len(exclude) != B:
+            raise ValueError("exclude has %d rows for a batch of %d" % (len(exclude), B))
+        rows = [np.setdiff1d(r, e, assume_unique=False) for r, e in zip(rows, exclude)]
+    off = np.zeros(B + 1, np.int64)
+    off[1:] = np.cumsum([r.size for r in rows])
+    ids = np.concatenate(rows).astype(np.int32) if off[-1] else np.zeros(0, np.int32)
+    return off, ids
+
+
+def _is_prebuilt(candidates):
+    return isinstance(candidates, tuple) and len(candidates) == 2 and torch.is_tensor(candidates[1])
+
+
+def candidates_for(candidates, B, V, excl_off=None, excl_ids=None):
+    """The `candidates` argument of the public searches -> (cand_off, cand_ids) for search(): one iterable of ids per row, from which
+    the exclusion CSR (excl_csr) is subtracted row by row, or a prebuilt (off, ids) pair whose ids is an int32 CUDA tensor the caller
+    vouches for (distinct within a row; no exclusions can be subtracted from it: ValueError when some are given)."""
+    if _is_prebuilt(candidates):
+        off, ids = candidates
+        if excl_off is not None:
+            raise ValueError("a prebuilt (off, ids) candidates pair takes no exclude: subtract the exclusions when building it")
+        off = np.ascontiguousarray(_host(off), np.int64)
+        if off.shape != (B + 1,) or ids.dtype != torch.int32 or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous():
+            raise ValueError("prebuilt candidates: off int64 [B + 1 = %d] on the host, ids a contiguous int32 CUDA tensor" % (B + 1))
+        if off[0] < 0 or np.any(np.diff(off) < 0) or off[-1] > ids.numel():
+            raise ValueError("prebuilt candidates: off must not decrease and must stay inside ids (%d entries)" % ids.numel())
+        return off, ids
+    exclude = None
+    if excl_off is not None:
+        o, e = np.asarray(excl_off, np.int64), np.asarray(_host(excl_ids), np.int64)
+        exclude = [e[o[b]:o[b + 1]] for b in range(B)]
+    return candidate_csr(candidates, B, V, exclude)
 
 
 # ---- shared candidate subsets: global ids <-> the local ids of a gathered sub-index (pure numpy; ItemSubset and Engine.topk) --------
@@ -94,14 +146,18 @@ def _dev_i32(x, dev):
     return (x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x, np.int32))).to(dev, torch.int32).contiguous()
 
 
-def search(query, ld, B, k, source, precision, owner, excl_off=None, excl_ids=None, targets=None):
+def search(query, ld, B, k, source, precision, owner, excl_off=None, excl_ids=None, targets=None, cand_off=None, cand_ids=None):
     """cr_score_topk, marshalled once: the k best items for the B fp32 query rows query + b * ld (a CUDA tensor's storage) out of
     `source` -- the fp32 item table (a CUDA tensor [V, D]), an ItemIndex of it, or an ItemSubset (the best k among its items).
     precision: the search arithmetic (L.PREC_*).  excl_off / excl_ids: an exclusion CSR (excl_csr) and targets: [B] ids, host or
     device, all on global ids -- a subset's translation to its local ids and back happens here and nowhere else.  owner: the object
     that keeps the workspace between calls (its _topk_ws).  Returns device tensors (ids [B, k] int32, scores [B, k] fp32, rank [B]
-    int32 or None for no targets)."""
+    int32 or None for no targets).  cand_off / cand_ids: per-row candidate lists (candidate_csr; candidates_for has subtracted the
+    exclusions) -- the best k among row b's own candidates, castrec.h cr_score_topk_lists, from the table or an ItemIndex; without
+    them the call is the full search above."""
     dev, k = query.device, int(k)
+    if cand_off is not None:
+        return _search_lists(query, ld, B, k, source, precision, owner, excl_off, targets, cand_off, cand_ids)
     subset = source if isinstance(source, ItemSubset) else None
     if subset is not None:
         excl_off, excl_ids = excl_to_local(subset._map, excl_off, _host(excl_ids))
@@ -133,7 +189,37 @@ def search(query, ld, B, k, source, precision, owner, excl_off=None, excl_ids=No
     return ids, scores, rank
 
 
-def _search_numpy(source, queries, k, exclude, targets, precision):
+def _search_lists(query, ld, B, k, source, precision, owner, excl_off, targets, cand_off, cand_ids):
+    """search() with per-row candidate lists: cr_score_topk_lists, its workspace (sized for the longest row) kept on owner."""
+    dev = query.device
+    if isinstance(source, ItemSubset):
+        raise ValueError("one filter per call: candidates= and an ItemSubset (allow=) exclude each other")
+    if excl_off is not None:
+        raise ValueError("candidates= takes its exclusions on the host (candidates_for): none may reach the search")
+    cand_off = np.ascontiguousarray(cand_off, np.int64)
+    if cand_off.shape != (B + 1,):
+        raise ValueError("cand_off must have B + 1 = %d entries, got %s" % (B + 1, cand_off.shape))
+    cand_ids = _dev_i32(cand_ids, dev) if cand_off[-1] > cand_off[0] else None
+    if targets is not None:
+        targets = _dev_i32(targets, dev)
+    if torch.is_tensor(source):
+        (V, D), table, kw = source.shape, source, {}
+    else:
+        (V, D), kw = (source.V, source.D), dict(index=source.blob, index_precision=source.prec)
+        table = (V, D)
+    need = O.topk_lists_workspace_bytes(B, int(np.diff(cand_off).max()), D, k)
+    ws = getattr(owner, "_topk_lists_ws", None)
+    if ws is None or ws.numel() < need or ws.device != dev:
+        ws = owner._topk_lists_ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    ids = torch.empty(B, k, dtype=torch.int32, device=dev)
+    scores = torch.empty(B, k, dtype=torch.float32, device=dev)
+    rank = torch.empty(B, dtype=torch.int32, device=dev) if targets is not None else None
+    with torch.cuda.device(dev):
+        O.score_topk_lists(query, ld, table, B, k, precision, cand_off, cand_ids, targets, ws, ids, scores, rank, **kw)
+    return ids, scores, rank
+
+
+def _search_numpy(source, queries, k, exclude, targets, precision, candidates=None):
     """ItemIndex.search and ItemSubset.search: queries (numpy or CUDA) and per-row exclusion lists in, numpy out."""
     index = source.index if isinstance(source, ItemSubset) else source
     if not index.blob.is_cuda:
@@ -143,8 +229,11 @@ def _search_numpy(source, queries, k, exclude, targets, precision):
     if q.dim() != 2 or q.shape[1] != index.D:
         raise ValueError("queries must be [B, %d], got %s" % (index.D, tuple(q.shape)))
     B = q.shape[0]
-    top, sc, rk = search(q, index.D, B, k, source, index.prec if precision is None else _prec(precision), index, *excl_csr(exclude, B),
-                         targets=targets)
+    excl, cand = excl_csr(exclude, B), (None, None)
+    if candidates is not None:
+        cand, excl = candidates_for(candidates, B, index.V, *excl), (None, None)
+    top, sc, rk = search(q, index.D, B, k, source, index.prec if precision is None else _prec(precision), index, *excl,
+                         targets=targets, cand_off=cand[0], cand_ids=cand[1])
     out = (top.cpu().numpy(), sc.cpu().numpy())
     return out + (rk.cpu().numpy(),) if rk is not None else out
 
@@ -183,14 +272,19 @@ class ItemIndex(object):
             blob = O.topk_index_gather(m[1:], self.prec, index=self.blob, index_precision=self.prec, V=self.V, D=self.D)
         return ItemSubset(ItemIndex(m.numel(), self.D, self.prec, blob, self.version), m, self.V, self.version)
 
-    def search(self, queries, k, exclude=None, targets=None, precision=None, allow=None):
+    def search(self, queries, k, exclude=None, targets=None, precision=None, allow=None, candidates=None):
         """The k best items for each query row (dot product), as Model.recommend returns them: numpy (ids [B, k], scores [B, k]) and,
         with targets, each target's rank.  exclude: None or one iterable of ids per row.  precision: the search arithmetic, by
         default the index's own.  allow: an iterable of ids -- the best k among those items only, for every row: shorthand for
-        self.subset(allow).search(...) (keep the ItemSubset to search the same set again)."""
+        self.subset(allow).search(...) (keep the ItemSubset to search the same set again).  candidates: one iterable of ids per
+        row -- the best k among THAT row's candidates (minus the row's exclude; a target outside them has rank -1), or a prebuilt
+        (off, ids) pair (candidate_csr, ids an int32 CUDA tensor; exclude must then be None).  One filter per call: allow or
+        candidates."""
         if allow is not None:
+            if candidates is not None:
+                raise ValueError("one filter per call: allow= or candidates=")
             return self.subset(allow).search(queries, k, exclude=exclude, targets=targets, precision=precision)
-        return _search_numpy(self, queries, k, exclude, targets, precision)
+        return _search_numpy(self, queries, k, exclude, targets, precision, candidates)
 
     def save(self, path):
         """One uncompressed .npz: blob (uint8) and meta = [format, V, D, precision]."""
@@ -223,7 +317,8 @@ class ItemSubset(object):
     table, so a score has the bits of the full search); ids: int32 [n + 1] on the index's device, ascending, ids[0] == 0 -- local
     row -> global id; parent_V: the rows of the table the ids refer to; version: as ItemIndex.version.  Ascending ids make the local
     order the global order, so ties break as in the full search.  Everything public takes and returns global ids; ranks are ranks
-    among the eligible items of the subset.  One subset per call: per-query masks are not supported.
+    among the eligible items of the subset.  One subset per call, shared by all rows: a list per row goes through candidates=
+    (ItemIndex.search, Model.recommend), not through a subset.
 
         sub = ix.subset(ids)                           # out of an ItemIndex; or ItemSubset.build(table, ids) from the fp32 table
         top, scores = sub.search(queries, k=10)        # == ix.search(queries, 10, allow=ids)

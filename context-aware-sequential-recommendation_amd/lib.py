@@ -153,6 +153,13 @@ class TopkDesc(C.Structure):
                 ("index", c_p), ("index_bytes", C.c_size_t), ("index_precision", c_i)]
 
 
+class TopkListsDesc(C.Structure):
+    _fields_ = [("query", c_p), ("ld", c_i), ("table", c_p), ("V", c_i), ("D", c_i), ("B", c_i), ("K", c_i), ("precision", c_i),
+                ("cand_off", c_p), ("cand_ids", c_p), ("targets", c_p), ("top_ids", c_p), ("top_scores", c_p), ("rank", c_p),
+                ("workspace", c_p), ("workspace_bytes", C.c_size_t),
+                ("index", c_p), ("index_bytes", C.c_size_t), ("index_precision", c_i)]
+
+
 class SoftmaxCeDesc(C.Structure):
     _fields_ = [("seq_emb", c_p), ("ld", c_i), ("table", c_p), ("pos", c_p), ("neg", c_p), ("M", c_i), ("D", c_i), ("V", c_i),
                 ("precision", c_i), ("state", c_p), ("d_seq_emb", c_p), ("ldd", c_i), ("table_grad", c_p), ("lse_out", c_p),
@@ -247,6 +254,9 @@ _sig("cr_score_topk", c_i, [C.POINTER(TopkDesc), c_p])
 _sig("cr_topk_index_bytes", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_topk_index_build", c_i, [c_p, c_i, c_i, c_i, c_p, C.c_size_t, c_p])
 _sig("cr_topk_index_gather", c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, C.c_size_t, c_p])
+_sig("cr_score_topk_lists_workspace", C.c_size_t, [c_i, C.c_int64, c_i, c_i])
+_sig("cr_topk_lists_segments", c_i, [c_i, C.c_int64])
+_sig("cr_score_topk_lists", c_i, [C.POINTER(TopkListsDesc), c_p])
 _sig("cr_softmax_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_softmax_ce", c_i, [C.POINTER(SoftmaxCeDesc), c_p])
 _sig("cr_sampled_ce_workspace", C.c_size_t, [c_i, c_i, c_i])
@@ -261,7 +271,8 @@ EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "
            "cr_head_fwd_bwd", "cr_head_fwd_bwd_ln", "cr_stack_fwd_head_supported", "cr_stack_fwd_head", "cr_test_logits", "cr_adam_step", "cr_reduce_slabs", "cr_l2_penalty", "cr_graph_begin", "cr_graph_end", "cr_graph_launch",
            "cr_graph_destroy", "cr_sampler_create", "cr_sampler_next", "cr_sampler_destroy",
            "cr_tgrad_geometry", "cr_batch_index_layout", "cr_index_builder_create", "cr_index_build", "cr_index_builder_destroy", "cr_table_grad",
-           "cr_score_topk_workspace", "cr_score_topk", "cr_topk_index_bytes", "cr_topk_index_build", "cr_topk_index_gather", "cr_softmax_ce_workspace", "cr_softmax_ce",
+           "cr_score_topk_workspace", "cr_score_topk", "cr_topk_index_bytes", "cr_topk_index_build", "cr_topk_index_gather",
+           "cr_score_topk_lists_workspace", "cr_topk_lists_segments", "cr_score_topk_lists", "cr_softmax_ce_workspace", "cr_softmax_ce",
            "cr_sampled_ce_workspace", "cr_sampled_ce", "cr_gbce_workspace", "cr_gbce"]
 
 lib = _lib

@@ -266,34 +266,53 @@ class _Model(object):
         return ItemSubset.build(self._owner.p("item_emb"), allow, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3",
                                 version=self._param_version)
 
-    def similar_items(self, ids, k=10, index=None, allow=None):
+    def similar_items(self, ids, k=10, index=None, allow=None, candidates=None):
         """The k items whose table rows have the largest dot product with each given item's own row (the model's geometry: the scores
         of recommend with the item's vector as the query), the item itself left out.  Returns numpy (ids [n, k], scores [n, k]).
         index: an ItemIndex of the table to search instead of one built for this call.  allow: an iterable of item ids or an
-        ItemSubset -- the k most similar among those items only (one set for every row)."""
-        from .index import ItemIndex
+        ItemSubset -- the k most similar among those items only (one set for every row).  candidates: one iterable of item ids
+        per given item -- the k most similar among that item's own candidates (the table's rows are gathered unless index is
+        given); one filter per call, allow or candidates."""
+        from .index import ItemIndex, search
         ids = np.asarray(ids, np.int64).ravel()
         if ids.size == 0 or ids.min() < 1 or ids.max() > self.itemnum:
             raise ValueError("ids must be item ids in 1 .. %d" % self.itemnum)
+        if candidates is not None and allow is not None:
+            raise ValueError("one filter per call: allow= or candidates=")
         index = self._allowed(allow, index)
         table = self._owner.p("item_emb")
+        q = table[torch.from_numpy(ids).to(table.device)]
+        if candidates is not None:
+            from .index import PRECISIONS, _is_prebuilt, candidates_for, excl_csr
+            n = ids.size
+            cand = candidates_for(candidates, n, self.itemnum + 1, *((None, None) if _is_prebuilt(candidates) else excl_csr([[int(i)] for i in ids], n)))
+            prec = index.prec if index is not None else PRECISIONS["bf16" if self._owner.attn_precision == "bf16" else "bf16x3"]
+            top, sc, _ = search(q, q.shape[1], n, int(k), table if index is None else index, prec, self._owner,
+                                cand_off=cand[0], cand_ids=cand[1])
+            return top.cpu().numpy(), sc.cpu().numpy()
         if index is None:
             index = ItemIndex.build(table, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3")
-        q = table[torch.from_numpy(ids).to(table.device)]
         return index.search(q, int(k), exclude=[[int(i)] for i in ids])
 
     def recommend(self, u, seq, k=10, timeseq=None, hours_seq=None, days_seq=None, exclude="history", return_scores=True,
-                  targets=None, index=None, allow=None):
+                  targets=None, index=None, allow=None, candidates=None):
         """The k best items of the whole catalogue for each row of a batch (the last position's scores against every item row,
         sasrec.py:93-97 extended from a candidate list to the table; castrec.h cr_score_topk).  exclude: "history" (the nonzero ids
         of each row of seq), None, or one iterable of ids per row.  Returns numpy (ids [B, k], scores [B, k]) -- ids only when
         return_scores is False -- and, with targets ([B] ids), a third array: each target's 0-based rank among the eligible items
         (-1 for an excluded target).  Rows with fewer than k eligible items end in id 0, score -inf.  index: an ItemIndex of the item
         table (build_item_index): same results, the table's rows are not converted again.  allow: an iterable of item ids or an
-        ItemSubset (castrec_amd.index) -- the best k among those items only, one set shared by every row (per-row masks are not
-        supported); it combines with exclude, a target outside it has rank -1 and ranks count the set's eligible items.  With an
-        iterable the subset is gathered for this call (out of index when given): keep an ItemSubset to reuse it."""
-        from .index import excl_csr
+        ItemSubset (castrec_amd.index) -- the best k among those items only, one set shared by every row (a list per row goes
+        through candidates=); it combines with exclude, a target outside it has rank -1 and ranks count the set's eligible items.
+        With an iterable the subset is gathered for this call (out of index when given): keep an ItemSubset to reuse it.
+        candidates: one iterable of item ids per row -- the best k among THAT row's candidates (castrec.h cr_score_topk_lists: the
+        rows the lists name are gathered from the item table, or from index when given, so the cost follows the lists); it
+        combines with exclude ("history" included), a target that is no eligible candidate of its row has rank -1 and ranks count
+        the row's eligible candidates.  Or a prebuilt (off, ids) pair (castrec_amd.index.candidate_csr, ids an int32 CUDA tensor of
+        distinct ids per row) for large batches: exclude must then be None.  One filter per call: allow or candidates."""
+        from .index import ItemSubset, excl_csr
+        if candidates is not None and (allow is not None or isinstance(index, ItemSubset)):
+            raise ValueError("one filter per call: candidates= together with allow= or an ItemSubset")
         index = self._allowed(allow, index)
         seq = np.asarray(seq)
         if seq.ndim == 1:
@@ -307,7 +326,7 @@ class _Model(object):
             if exclude != "history":
                 raise ValueError("exclude must be 'history', None or a list of per-row id iterables")
             exclude = [r[r != 0] for r in seq.astype(np.int64)]
-        top, sc, rk = eng.topk(int(k), *excl_csr(exclude, B), targets, index=index)
+        top, sc, rk = eng.topk(int(k), *excl_csr(exclude, B), targets, index=index, candidates=candidates)
         out = (top.cpu().numpy(),) + ((sc.cpu().numpy(),) if return_scores else ())
         if targets is not None:
             out = out + (rk.cpu().numpy(),)

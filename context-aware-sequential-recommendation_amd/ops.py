@@ -169,6 +169,38 @@ def score_topk(query, ld, table, B, K, precision, excl_off, excl_ids, targets, w
     L.call("cr_score_topk", C.byref(d), _stream())
 
 
+def topk_lists_workspace_bytes(B, max_len, D, K):
+    n = L.lib.cr_score_topk_lists_workspace(B, max_len, D, K)
+    if n == 0:
+        raise ValueError("cr_score_topk_lists: unsupported shape B=%d max_len=%d D=%d K=%d (1 <= K <= %d, 8 <= D <= 256, rows shorter than 2^31)"
+                         % (B, max_len, D, K, L.CR_TOPK_MAX))
+    return n
+
+
+def score_topk_lists(query, ld, table, B, K, precision, cand_off, cand_ids, targets, workspace, top_ids, top_scores, rank=None,
+                     index=None, index_precision=None):
+    """cr_score_topk_lists: the K best of row b's candidates cand_ids[cand_off[b] : cand_off[b + 1]] (cand_off a host int64 numpy array
+    [B + 1], cand_ids an int32 CUDA tensor or None when every list is empty); everything else as score_topk, workspace of at least
+    topk_lists_workspace_bytes(B, the longest row, D, K) bytes."""
+    import numpy as np
+    off = np.ascontiguousarray(cand_off, np.int64)
+    if off.shape != (B + 1,):
+        raise ValueError("cand_off must have B + 1 = %d entries, got %s" % (B + 1, off.shape))
+    if index is not None and not torch.is_tensor(table):
+        (V, D), table = table, None
+    else:
+        V, D = table.shape
+    d = L.TopkListsDesc(_p(_f32(query, "query")), ld, _p(_f32(table, "table")), V, D, B, K, precision,
+                        off.ctypes.data, _p(_i32(cand_ids, "cand_ids")), _p(_i32(targets, "targets")),
+                        _p(_i32(top_ids, "top_ids")), _p(_f32(top_scores, "top_scores")), _p(_i32(rank, "rank")),
+                        _p(workspace), workspace.numel() * workspace.element_size())
+    if index is not None:
+        if index.dtype != torch.uint8 or not index.is_cuda or not index.is_contiguous():
+            raise TypeError("index must be a contiguous uint8 CUDA tensor")
+        d.index, d.index_bytes, d.index_precision = index.data_ptr(), index.numel(), int(precision if index_precision is None else index_precision)
+    L.call("cr_score_topk_lists", C.byref(d), _stream())
+
+
 def topk_index_bytes(V, D, precision=L.PREC_BF16X3):
     n = L.lib.cr_topk_index_bytes(V, D, precision)
     if n == 0:

@@ -502,6 +502,52 @@ int cr_topk_index_build(const float* table, int V, int D, int precision, void* i
 int cr_topk_index_gather(const float* table, const void* index, int index_precision, int V, int D,
                          const int32_t* ids, int n, int precision, void* out_index, size_t out_bytes, void* stream);
 
+/* ---- top-K over per-query candidate lists (csrc/cr_topk.hip) ---------------------------------------------------------
+ * "The best K among THIS row's candidates": row b's candidates are cand_ids[cand_off[b] .. cand_off[b + 1]), in any order.  The
+ * rows a list names are gathered -- from the fp32 table or from an item index of it -- and scored 16 at a time against the query;
+ * the cost follows the lists, not the catalogue.  There is no exclusion list: whoever makes a per-row list subtracts the row's
+ * exclusions from it.
+ *   - eligibility: an id outside 1 .. V-1 (0, negative, >= V) is not eligible and its row is never read.  The ids of one row must
+ *     be distinct; with duplicates the returned list is unspecified (nothing is read or written out of bounds, the call ends).
+ *   - outputs: the K best eligible candidates of the row, sorted by score descending, equal scores by smaller id first; fewer
+ *     than K eligible candidates: id 0, score -inf (cr_score_topk's filler); an empty row is all filler.
+ *   - targets (optional, device [B]): rank[b] = #{eligible c of row b, c != t : s_c > s_t or (s_c == s_t and c < t)}, s_t being the
+ *     score formed for t as a candidate; -1 when t is not among the row's eligible candidates.
+ *   - scores: the bits cr_score_topk returns for the same (query, item) at the same precision, from the table or from an index of
+ *     it (a score depends on one item row, one query and one product sequence).  A split index serves every precision, a plain
+ *     index CR_PREC_BF16 only; index_bytes must equal cr_topk_index_bytes(V, D, index_precision).
+ *   - determinism: no float atomics.  A list longer than 2 048 at a small B is cut into segments so that the device fills:
+ *     n = min(256, ceil(max_len / 2048), max(1, ceil(1024 / B))), segments of ceil(max_len / n) candidates (of every row),
+ *     n_seg = ceil(max_len / that length), at least 1 -- cr_topk_lists_segments, a function of (B, max_len) alone, max_len being
+ *     the longest row.  One launch for one segment; with more, a merge of the segments' lists and a sum of their counts follow.
+ *     Two calls return the same bits.
+ *   - cand_off: a HOST array [B + 1], cand_off[0] >= 0, non-decreasing, every row shorter than 2^31; read before the call
+ *     returns.  cand_ids: device; may be NULL when every list is empty.
+ *   - shapes: 1 <= K <= CR_TOPK_MAX, 8 <= D <= 256, V >= 1, B >= 1, ld >= D.
+ *   - workspace: at least cr_score_topk_lists_workspace(B, max_len, D, K) bytes of device memory.
+ * Every argument is checked before any device call. */
+typedef struct cr_topk_lists_desc cr_topk_lists_desc;
+struct cr_topk_lists_desc {
+    const float* query; int ld;       /* [B] rows of D floats, pitch ld >= D */
+    const float* table;               /* [V, D], or NULL with an index */
+    int V, D, B, K;
+    int precision;                    /* CR_PREC_*, as cr_score_topk */
+    const int64_t* cand_off;          /* host [B + 1] */
+    const int32_t* cand_ids;          /* device [cand_off[B]] */
+    const int32_t* targets;           /* device [B] or NULL */
+    int32_t* top_ids;                 /* device [B, K] */
+    float* top_scores;                /* device [B, K] */
+    int32_t* rank;                    /* device [B]; required with targets */
+    void* workspace;
+    size_t workspace_bytes;
+    const void* index;                /* optional: an item index of the table; NULL: the table is read */
+    size_t index_bytes;               /* == cr_topk_index_bytes(V, D, index_precision) */
+    int index_precision;              /* the precision the index was built with */
+};
+size_t cr_score_topk_lists_workspace(int B, int64_t max_len, int D, int K);   /* 0 outside the supported range */
+int cr_topk_lists_segments(int B, int64_t max_len);                           /* n_seg above; 0 for B < 1 or max_len outside 0 .. 2^31-1 */
+int cr_score_topk_lists(const cr_topk_lists_desc* d, void* stream);
+
 /* ---- full-catalogue softmax cross-entropy (csrc/cr_ce.hip) ----------------------------------------------------------
  * The training objective over the whole item table, an alternative to cr_head_fwd_bwd's one-negative BCE.  Rows m = 0 .. M-1,
  * h_m = seq_emb row m, E = table [V, D], istarget_m = (pos[m] != 0):
