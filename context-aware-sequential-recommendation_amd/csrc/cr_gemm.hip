@@ -218,6 +218,7 @@ extern "C" int cr_gemm_wgrad(const cr_wgrad_desc* d, int n, int slab_stride, int
         CR_REQUIRE(d[i].A && d[i].G && d[i].dW, "cr_gemm_wgrad[%d]: NULL pointer", i);
         CR_REQUIRE(d[i].M > 0 && d[i].N > 0 && d[i].K > 0, "cr_gemm_wgrad[%d]: bad shape", i);
         CR_REQUIRE(d[i].lda >= d[i].K && d[i].ldg >= d[i].N && d[i].ldw >= d[i].N, "cr_gemm_wgrad[%d]: leading dimension too small", i);
+        CR_REQUIRE(d[i].precision >= CR_PREC_F32 && d[i].precision <= CR_PREC_BF16, "cr_gemm_wgrad[%d]: unknown precision %d", i, d[i].precision);
         b.p[i] = d[i];
         tiles += cr_ceil_div(d[i].K, 64) * cr_ceil_div(d[i].N, 64);
     }

@@ -157,12 +157,16 @@ typedef struct {
     int M, N, K;
     int trans_b;
     int relu;
-    cr_rng drop;               /* element index = m*N + n */
+    cr_rng drop;               /* element index = (drop.row_offset + m)*N + n (N, not ldc) */
     const float* residual; int ldr;
     const int32_t* mask_ids;   /* [M] or NULL */
     int accumulate;            /* C += value */
-    int precision;             /* CR_PREC_*: fp32 MFMA (exact), or bf16 MFMA on split / plain operands (K, N >= 8) */
+    int precision;             /* CR_PREC_*: fp32 MFMA (exact), or bf16 MFMA on split / plain operands; see the dispatch rule below */
 } cr_gemm_desc;
+/* Dispatch (cr_gemm_rows and cr_gemm_wgrad alike): a launch runs on the bf16 matrix pipe if and only if every problem of the batch
+ * has the SAME precision, CR_PREC_BF16X3 or CR_PREC_BF16, and K >= 8 and N >= 8.  A batch of mixed precisions, or one with any K or
+ * N below 8, is computed whole by the exact fp32 kernels (never less accurate than asked for).  A precision outside CR_PREC_* is
+ * CR_ERR_INVALID. */
 int cr_gemm_rows(const cr_gemm_desc* d, int n_problems, void* stream);
 
 /* weight gradient: dW[K,N] = A[M,K]^T @ G[M,N], db[N] = colsum(G); reduction over M is split

@@ -1,7 +1,9 @@
-"""What the per-op GPU tests share (test_ops_gpu, test_attn_bf_gpu): device arrays, a fresh state block, the relative error and the
-fp64 attention core."""
+"""What the per-op GPU tests share (test_ops_gpu, test_attn_bf_gpu, test_row_ops_gpu, test_gemm_gpu): device arrays, a fresh state
+block, the relative error, sentinel-filled buffers and the fp64 attention core."""
 import numpy as np
 import torch
+
+SENTINEL = 0x7FC0BEEF          # a quiet NaN with a payload
 
 
 def dev(a, dtype=torch.float32):
@@ -12,6 +14,33 @@ def relerr(got, want):
     want = np.asarray(want, np.float64)
     got = got.detach().cpu().double().numpy() if isinstance(got, torch.Tensor) else np.asarray(got, np.float64)
     return float(np.abs(got - want).max() / (np.abs(want).max() + 1e-30))
+
+
+class Pad:
+    """[rows, ld] floats on the device plus a tail, all SENTINEL; regions = [(first column, columns)] are what a kernel may touch,
+    optionally filled with data (one array per region).  lead: SENTINEL words in front of the matrix (t is the matrix: with lead = 1
+    it starts one float past the allocation's boundary)."""
+
+    def __init__(self, rows, ld, regions, data=None, tail=9, lead=0):
+        self.rows, self.ld, self.regions = rows, ld, regions
+        host = np.full(lead + rows * ld + tail, SENTINEL, np.uint32).view(np.float32)
+        self.inside = np.zeros(rows * ld + tail, bool)
+        body, inside = host[lead:lead + rows * ld].reshape(rows, ld), self.inside[:rows * ld].reshape(rows, ld)
+        for k, (off, cols) in enumerate(regions):
+            assert off + cols <= ld
+            inside[:, off:off + cols] = True
+            if data is not None:
+                body[:, off:off + cols] = np.asarray(data if len(regions) == 1 else data[k], np.float32).reshape(rows, cols)
+        self.whole = torch.from_numpy(host.copy()).cuda()
+        self.t, self.lead = self.whole[lead:], lead
+
+    def read(self, k=0):
+        off, cols = self.regions[k]
+        return self.t[:self.rows * self.ld].reshape(self.rows, self.ld)[:, off:off + cols].contiguous().cpu().numpy()
+
+    def untouched(self):
+        bits = self.whole.cpu().numpy().view(np.uint32)
+        return bool((bits[:self.lead] == SENTINEL).all() and (bits[self.lead:][~self.inside] == SENTINEL).all())
 
 
 def new_state(step=0):

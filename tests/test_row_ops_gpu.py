@@ -31,12 +31,11 @@ import pytest
 import torch
 
 import row_ops_ref as R
-from ops_harness import dev, new_state, relerr
+from ops_harness import SENTINEL, Pad, dev, new_state, relerr  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 F64 = np.float64
-SENTINEL = 0x7FC0BEEF          # a quiet NaN with a payload
 
 
 @pytest.fixture(scope="module")
@@ -45,31 +44,6 @@ def ops():
     from castrec_amd import ops as O
     assert torch.cuda.is_available()
     return O
-
-
-class Pad:
-    """[rows, ld] floats on the device plus a tail, all SENTINEL; regions = [(first column, columns)] are what a kernel may touch,
-    optionally filled with data (one array per region)."""
-
-    def __init__(self, rows, ld, regions, data=None, tail=9):
-        self.rows, self.ld, self.regions = rows, ld, regions
-        host = np.full(rows * ld + tail, SENTINEL, np.uint32).view(np.float32)
-        self.inside = np.zeros(rows * ld + tail, bool)
-        body, inside = host[:rows * ld].reshape(rows, ld), self.inside[:rows * ld].reshape(rows, ld)
-        for k, (off, cols) in enumerate(regions):
-            assert off + cols <= ld
-            inside[:, off:off + cols] = True
-            if data is not None:
-                body[:, off:off + cols] = np.asarray(data if len(regions) == 1 else data[k], np.float32).reshape(rows, cols)
-        self.t = torch.from_numpy(host.copy()).cuda()
-
-    def read(self, k=0):
-        off, cols = self.regions[k]
-        return self.t[:self.rows * self.ld].reshape(self.rows, self.ld)[:, off:off + cols].contiguous().cpu().numpy()
-
-    def untouched(self):
-        bits = self.t.cpu().numpy().view(np.uint32)
-        return bool((bits[~self.inside] == SENTINEL).all())
 
 
 def within(got, ref, allow, what):
