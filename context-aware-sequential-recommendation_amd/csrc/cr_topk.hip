@@ -457,6 +457,52 @@ __global__ __launch_bounds__(256) void k_topk_index_write(TkSrc s, const int32_t
     tk_idx_store<NK, SPLIT>(idx, plane, tile, h, lo);
 }
 
+// Keeping an index in step with its table (castrec.h cr_topk_index_update, cr_topk_index_sync).  A row's groups are its own, so a row
+// is rewritten in place.  tk_idx_row_store is the store that mirrors the IDX branch of tk_src_row: lane (li, lg) puts the fragments
+// of ITS row r where that gather reads them, group (r >> 4) NK 64 + ks 64 + 16 lg + (r & 15), the lo plane `plane` groups further
+// on; every offset 64-bit; a lane without a row (!rok) stores nothing and forms no address from r.
+template <int NK, bool SPLIT>
+__device__ __forceinline__ void tk_idx_row_store(bf8* idx, int64_t plane, int r, bool rok, const bf8 (&hi)[NK], const bf8 (&lo)[NK]) {
+    if (!rok) return;
+    const int lg = (threadIdx.x & 63) >> 4;
+    bf8* p = idx + (int64_t)(r >> 4) * (NK * 64) + (lg * 16 + (r & 15));
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        p[ks * 64] = hi[ks];
+        if (SPLIT) p[plane + ks * 64] = lo[ks];
+    }
+}
+
+// The rows a list names: a wave takes 16 ids, lane li the id ids[16 w + li].  s is the fp32 source: the [V, D] table (source row =
+// the id) or, packed, the [n, D] rows in list order (source row = the position; s.V == n, so the re-read of the source's last row is
+// the build's).  An id outside 0 .. V-1, and a lane past the list, has no row: nothing of it is read or written.
+template <int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_topk_index_update(TkSrc s, int packed, int V, const int32_t* ids, int n, bf8* idx, int64_t plane) {
+    const int64_t j = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (threadIdx.x & 15);
+    const int id = j < n ? ids[j] : -1;
+    const bool rok = (unsigned)id < (unsigned)V;
+    const int row = !rok ? 0 : packed ? (int)j : id;
+    bf8 h[NK], lo[NK];
+    tk_src_row<NK, SPLIT, false>(s, row, rok, h, lo);
+    tk_idx_row_store<NK, SPLIT>(idx, plane, id, rok, h, lo);
+}
+
+// The tiles a flag array names: a wave per tile, rewritten whole -- the build's body, full 1 KB runs -- when any of its rows r < V has
+// (uint32_t)flags[r] >= since (cr_adam_desc.lazy_flags: the number of the last step that moved row r).  The test is wave-uniform; a
+// tile without such a row is left alone and its table rows are not read.
+template <int NK, bool SPLIT>
+__global__ __launch_bounds__(256) void k_topk_index_sync(TkSrc s, const int32_t* flags, uint32_t since, bf8* idx, int64_t plane) {
+    const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile >= s.n_tiles) return;                         // wave-uniform
+    const int r = tile * 16 + (threadIdx.x & 15);
+    const bool rok = r < s.V;
+    const bool hit = rok && (uint32_t)flags[rok ? r : 0] >= since;
+    if (__ballot(hit) == 0) return;                        // wave-uniform
+    bf8 h[NK], lo[NK];
+    tk_src_row<NK, SPLIT, false>(s, r, rok, h, lo);
+    tk_idx_store<NK, SPLIT>(idx, plane, tile, h, lo);
+}
+
 // planes of an index of `precision`: 2 (hi + lo; CR_PREC_F32 as CR_PREC_BF16X3), 1 (plain bf16), 0 for anything else
 int tk_index_planes(int precision) {
     return (precision == CR_PREC_BF16X3 || precision == CR_PREC_F32) ? 2 : precision == CR_PREC_BF16 ? 1 : 0;
@@ -570,6 +616,42 @@ extern "C" int cr_topk_index_gather(const float* table, const void* index, int i
                n + 1, need);
     tk_index_write(tk_source(table, index, V, D), ids, n, out_index, n + 1, planes, cr_stream(stream));
     return cr_check_launch("cr_topk_index_gather");
+}
+
+extern "C" int cr_topk_index_update(const float* src, int packed, int V, int D, int precision, void* index, size_t index_bytes,
+                                    const int32_t* ids, int n, void* stream) {
+    CR_REQUIRE(src && index && ids, "cr_topk_index_update: NULL src, index or ids");
+    if (const int rc = tk_check_shape("cr_topk_index_update", V, D, precision)) return rc;
+    CR_REQUIRE(n >= 1, "cr_topk_index_update: n=%d must be >= 1", n);
+    const size_t need = cr_topk_index_bytes(V, D, precision);
+    CR_REQUIRE(index_bytes == need, "cr_topk_index_update: index_bytes=%zu, cr_topk_index_bytes(V=%d, D=%d) says %zu", index_bytes, V, D,
+               need);
+    const TkIdxGeom g = tk_index_geom(V, D);
+    const TkSrc s = tk_source(src, nullptr, packed ? n : V, D);          // the source's own rows: its last row is re-read as the build's
+    const dim3 grid((unsigned)(((int64_t)n + 63) / 64));
+    bf8* idx = static_cast<bf8*>(index);
+    hipStream_t st = cr_stream(stream);
+    tk_dispatch(g.NK, tk_index_planes(precision) == 2, [&](auto nk, auto sp) {
+        hipLaunchKernelGGL((k_topk_index_update<nk, sp>), grid, dim3(256), 0, st, s, packed ? 1 : 0, V, ids, n, idx, g.plane);
+    });
+    return cr_check_launch("cr_topk_index_update");
+}
+
+extern "C" int cr_topk_index_sync(const float* table, int V, int D, int precision, void* index, size_t index_bytes, const int32_t* flags,
+                                  uint32_t since, void* stream) {
+    CR_REQUIRE(table && index && flags, "cr_topk_index_sync: NULL table, index or flags");
+    if (const int rc = tk_check_shape("cr_topk_index_sync", V, D, precision)) return rc;
+    const size_t need = cr_topk_index_bytes(V, D, precision);
+    CR_REQUIRE(index_bytes == need, "cr_topk_index_sync: index_bytes=%zu, cr_topk_index_bytes(V=%d, D=%d) says %zu", index_bytes, V, D,
+               need);
+    const TkSrc s = tk_source(table, nullptr, V, D);
+    const dim3 grid((s.n_tiles + 3) / 4);
+    bf8* idx = static_cast<bf8*>(index);
+    hipStream_t st = cr_stream(stream);
+    tk_dispatch(tk_nk(D), tk_index_planes(precision) == 2, [&](auto nk, auto sp) {
+        hipLaunchKernelGGL((k_topk_index_sync<nk, sp>), grid, dim3(256), 0, st, s, flags, since, idx, s.plane);
+    });
+    return cr_check_launch("cr_topk_index_sync");
 }
 
 extern "C" size_t cr_score_topk_workspace(int B, int V, int D, int K) {

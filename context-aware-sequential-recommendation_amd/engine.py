@@ -290,6 +290,7 @@ class Engine:
         self._resolve_options(attn_precision, lazy_adam, loss, ce_negatives, gbce_t, ce_proposal, row_sparse_adam, fused,
                               data_parallel=(batch_global is not None and batch_global != batch_size) or bool(row_offset))
         self.M = self.B * self.T
+        self.flags_epoch = 0                          # bumped wherever set_step zeroes lazy_flags: a flag then says nothing about earlier steps
         self._pending_embed = {}
         self._scatter_recipe, self._scatter_claimed = {}, set()      # out buffer of an embedding lookup -> ScatterRecipe
         self._ln_recipe, self._ln_claimed = {}, set()                # LayerNorm output pointer -> LnRecipe
@@ -1381,6 +1382,7 @@ class Engine:
             # row-sparse Adam claims a row with atomicExch(flag, step) != step: a flag left by an earlier run of the same
             # step number (counter moved back, checkpoint loaded) would read as "already claimed" and skip the row
             self.lazy_flags.zero_()
+            self.flags_epoch += 1                        # what the flags said about earlier steps is gone (models.IndexToken)
 
     def set_item_weights(self, w):
         """ce_proposal="popularity": the proposal of the coming steps from non-negative item weights w [itemnum + 1] (w[0] ignored;

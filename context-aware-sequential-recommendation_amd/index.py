@@ -15,6 +15,12 @@ Per-row candidate lists: "the best k among THIS row's candidates" (castrec.h cr_
 and scored, so the cost follows the lists; global ids, the score bits of the full search.
 
     ids, scores = ix.search(queries, k=10, candidates=[row_0_ids, row_1_ids, ...])      # combines with exclude=
+
+Keeping an index in step with training (castrec.h cr_topk_index_update / cr_topk_index_sync): rows are rewritten in place, the blob
+ends as a fresh build's.
+
+    model.refresh_item_index(ix)                   # "sync" (row-sparse Adam's flags name the moved rows) or "rebuild"
+    ids, rows, tok = model.item_delta(tok)         # ... and in a serving process that holds no table: ix.update(ids, rows=rows)
 """
 import numpy as np
 import torch
@@ -241,10 +247,12 @@ def _search_numpy(source, queries, k, exclude, targets, precision, candidates=No
 class ItemIndex(object):
     """V, D: the table's shape; precision: "bf16x3" (hi + lo planes: serves every search precision) or "bf16" (hi only, half the bytes:
     plain-bf16 searches only); blob: the uint8 tensor of castrec.h's layout; version: the parameter version of the model that built it
-    (Model.build_item_index), None for an index that was loaded or built from a bare table."""
+    (Model.build_item_index), None for an index that was loaded or built from a bare table; token: what the blob is in step with,
+    for Model.refresh_item_index / item_delta (models.IndexToken; None: unknown, a refresh rebuilds)."""
 
     def __init__(self, V, D, precision, blob, version=None):
         self.V, self.D, self.precision, self.blob, self.version = int(V), int(D), _NAMES[_prec(precision)], blob, version
+        self.token = None
         need = L.lib.cr_topk_index_bytes(self.V, self.D, self.prec)
         if need == 0 or blob.numel() != need or blob.dtype != torch.uint8:
             raise ValueError("index blob of %d bytes (%s) does not fit V=%d D=%d precision=%s (%d bytes)"
@@ -271,6 +279,74 @@ class ItemIndex(object):
         with torch.cuda.device(self.blob.device):
             blob = O.topk_index_gather(m[1:], self.prec, index=self.blob, index_precision=self.prec, V=self.V, D=self.D)
         return ItemSubset(ItemIndex(m.numel(), self.D, self.prec, blob, self.version), m, self.V, self.version)
+
+    # -- keeping the index in step with its table (castrec.h cr_topk_index_update / cr_topk_index_sync): a row's groups are its own, so
+    # the blob is rewritten in place, no allocation, and holds the bytes of a fresh build of the table.  An ItemSubset gathered
+    # earlier (subset(), search(allow=)) has its own blob: it stays the snapshot it was.  version: stored in self.version (None for
+    # an index that follows no model); Model.refresh_item_index drives sync / rebuild and sets it.
+    def _writable(self, what):
+        if not self.blob.is_cuda:
+            raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to %s it" % what)
+
+    def _table(self, table):
+        if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.float32 or tuple(table.shape) != (self.V, self.D):
+            raise ValueError("table must be a float32 CUDA tensor [%d, %d], got %s"
+                             % (self.V, self.D, tuple(table.shape) if torch.is_tensor(table) else type(table).__name__))
+        return table.contiguous()
+
+    def update(self, ids, rows=None, table=None, version=None):
+        """Rewrites the rows `ids` in place -- any iterable of item ids or an int32 CUDA tensor, each in 1 .. V-1 (ValueError
+        otherwise), duplicates allowed where they carry the same row.  Exactly one source: table, the float32 CUDA tensor [V, D] the
+        index follows (row ids[j] is read), or rows, float32 [n, D] (numpy or tensor) with rows[j] the new row of item ids[j] -- a
+        delta sent without the table (Model.item_delta), for an index that was load()-ed where no table exists.  An ItemSubset
+        gathered from this index earlier stays the snapshot it was."""
+        if (rows is None) == (table is None):
+            raise ValueError("ItemIndex.update takes exactly one source: rows or table (%s given)" % ("both" if rows is not None else "neither"))
+        if torch.is_tensor(ids):
+            if ids.dtype != torch.int32 or ids.dim() != 1:
+                raise ValueError("ids as a tensor must be int32 [n], got %s %s" % (ids.dtype, tuple(ids.shape)))
+            n = ids.numel()
+            lo, hi = (int(ids.min()), int(ids.max())) if n else (1, 1)
+        else:
+            ids = np.asarray(ids if isinstance(ids, np.ndarray) else list(ids), np.int64).ravel()
+            n = ids.size
+            lo, hi = (int(ids.min()), int(ids.max())) if n else (1, 1)
+        if n == 0:
+            raise ValueError("ItemIndex.update needs at least one id")
+        if lo < 1 or hi > self.V - 1:
+            raise ValueError("ids must be item ids in 1 .. %d, got %d .. %d" % (self.V - 1, lo, hi))
+        if rows is not None:
+            src = rows if torch.is_tensor(rows) else torch.from_numpy(np.ascontiguousarray(rows, np.float32))
+            if src.dtype != torch.float32 or tuple(src.shape) != (n, self.D):
+                raise ValueError("rows must be float32 [%d, %d] (one row per id), got %s %s" % (n, self.D, src.dtype, tuple(src.shape)))
+        self._writable("update")
+        dev = self.blob.device
+        ids = (ids if torch.is_tensor(ids) else torch.from_numpy(ids.astype(np.int32))).to(dev).contiguous()
+        src = src.to(dev).contiguous() if rows is not None else self._table(table)
+        with torch.cuda.device(dev):
+            O.topk_index_update(self.blob, self.V, self.D, self.prec, ids, src, packed=rows is not None)
+        self.version = version
+        return self
+
+    def sync(self, table, flags, since, version=None):
+        """Rewrites in place, from table (float32 CUDA [V, D]), every 16-row tile with a row whose flags[r] >= since: flags is the
+        int32 CUDA tensor [V] of row-sparse Adam (Engine.lazy_flags: the number of the last step that moved row r), so the rows moved
+        by steps since .. are refreshed; the other rows of such a tile are rewritten with the bytes they had.  Tiles without a flagged
+        row are neither read nor written.  An ItemSubset gathered earlier stays the snapshot it was."""
+        self._writable("sync")
+        with torch.cuda.device(self.blob.device):
+            O.topk_index_sync(self.blob, self._table(table), self.prec, flags, since)
+        self.version = version
+        return self
+
+    def rebuild(self, table, version=None):
+        """The whole blob again from table (float32 CUDA [V, D]), into the tensor it already has: ItemIndex.build without the
+        allocation.  An ItemSubset gathered earlier stays the snapshot it was."""
+        self._writable("rebuild")
+        with torch.cuda.device(self.blob.device):
+            O.topk_index_build(self._table(table), self.prec, out=self.blob)
+        self.version = version
+        return self
 
     def search(self, queries, k, exclude=None, targets=None, precision=None, allow=None, candidates=None):
         """The k best items for each query row (dot product), as Model.recommend returns them: numpy (ids [B, k], scores [B, k]) and,

@@ -254,6 +254,8 @@ _sig("cr_score_topk", c_i, [C.POINTER(TopkDesc), c_p])
 _sig("cr_topk_index_bytes", C.c_size_t, [c_i, c_i, c_i])
 _sig("cr_topk_index_build", c_i, [c_p, c_i, c_i, c_i, c_p, C.c_size_t, c_p])
 _sig("cr_topk_index_gather", c_i, [c_p, c_p, c_i, c_i, c_i, c_p, c_i, c_i, c_p, C.c_size_t, c_p])
+_sig("cr_topk_index_update", c_i, [c_p, c_i, c_i, c_i, c_i, c_p, C.c_size_t, c_p, c_i, c_p])
+_sig("cr_topk_index_sync", c_i, [c_p, c_i, c_i, c_i, c_p, C.c_size_t, c_p, c_u32, c_p])
 _sig("cr_score_topk_lists_workspace", C.c_size_t, [c_i, C.c_int64, c_i, c_i])
 _sig("cr_topk_lists_segments", c_i, [c_i, C.c_int64])
 _sig("cr_score_topk_lists", c_i, [C.POINTER(TopkListsDesc), c_p])
@@ -272,6 +274,7 @@ EXPORTS = ["cr_version", "cr_last_error", "cr_step_begin", "cr_ids_ring_next", "
            "cr_graph_destroy", "cr_sampler_create", "cr_sampler_next", "cr_sampler_destroy",
            "cr_tgrad_geometry", "cr_batch_index_layout", "cr_index_builder_create", "cr_index_build", "cr_index_builder_destroy", "cr_table_grad",
            "cr_score_topk_workspace", "cr_score_topk", "cr_topk_index_bytes", "cr_topk_index_build", "cr_topk_index_gather",
+           "cr_topk_index_update", "cr_topk_index_sync",
            "cr_score_topk_lists_workspace", "cr_topk_lists_segments", "cr_score_topk_lists", "cr_softmax_ce_workspace", "cr_softmax_ce",
            "cr_sampled_ce_workspace", "cr_sampled_ce", "cr_gbce_workspace", "cr_gbce"]
 

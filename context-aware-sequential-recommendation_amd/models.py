@@ -8,12 +8,21 @@ models/cast_N.py) on top of the native engine.
 ``sess`` is accepted and ignored (there is no TensorFlow session).  ``predict`` takes a whole batch of
 users; ``item_idx`` is either the reference's shared list of 101 candidates or a [B, n] array.
 """
+import collections
 import os
 
 import numpy as np
 import torch
 
 from .engine import MODELS, Engine, Hyper
+
+# What an ItemIndex is in step with (ItemIndex.token; Model.refresh_item_index, Model.item_delta).  table_epoch: Model._table_epoch,
+# bumped by everything that changes the item table other than a training step (load, load_tf_checkpoint, load_params).  flags_epoch:
+# how often the training engine has zeroed row-sparse Adam's flags since it was made (Engine.flags_epoch; 0 before it exists).  step:
+# the number of the next training step (Engine.step_number(); 1, a lower bound, before the engine exists), None where Adam is dense.
+# lazy_flags[r] is the number of the last step that moved row r, so within one pair of epochs the rows that differ from the index are
+# exactly those with a flag >= token.step.
+IndexToken = collections.namedtuple("IndexToken", "table_epoch flags_epoch step")
 
 
 class _Model(object):
@@ -34,6 +43,8 @@ class _Model(object):
         self._owner = Engine(self.name, usernum, itemnum, self.hp, 1, training=False)
         self.attention_weights = None
         self._param_version = 0               # bumped by whatever changes the parameters: an ItemIndex records the one it was built at
+        self._table_epoch = 0                 # ... and by whatever changes them other than a training step (IndexToken)
+        self._flags_epoch0 = 0                # the training engine's flags_epoch when it was made: no step had run yet
 
     # -- training ---------------------------------------------------------------------------------
     def data_parallel(self, rank, world, process_group=None, sparse=None):
@@ -81,6 +92,7 @@ class _Model(object):
                 if self._pending_opt is not None:
                     self._apply_opt(*self._pending_opt)
                     self._pending_opt = None
+                self._flags_epoch0 = self._train.flags_epoch
                 return self._train
             self._train = Engine(self.name, self.usernum, self.itemnum, self.hp, B, training=True, share=self._owner,
                                  n_slabs=self._n_slabs, batch_global=self._batch_global, row_offset=self._row_offset)
@@ -92,6 +104,7 @@ class _Model(object):
                 self._pending_opt = None
             if self._item_weights is not None:
                 self._train.set_item_weights(self._item_weights)
+            self._flags_epoch0 = self._train.flags_epoch
         if getattr(self, "_dp", None) is not None:
             if self._dp_rows[2] != B:
                 raise ValueError("global batch size changed from %d to %d (static graph)" % (self._dp_rows[2], B))
@@ -235,16 +248,79 @@ class _Model(object):
         from .index import ItemIndex
         if precision is None:
             precision = "bf16" if self._owner.attn_precision == "bf16" else "bf16x3"
-        return ItemIndex.build(self._owner.p("item_emb"), precision, version=self._param_version)
+        ix = ItemIndex.build(self._owner.p("item_emb"), precision, version=self._param_version)
+        ix.token = self._index_token()
+        return ix
+
+    def _row_sparse_engine(self):
+        """The training engine where it runs row-sparse Adam (its lazy_flags name the rows a step moved), else None."""
+        eng = self._train
+        return eng if eng is not None and eng.lazy_adam and getattr(eng, "lazy_flags", None) is not None else None
+
+    def _index_token(self):
+        """The IndexToken of the item table as it is now."""
+        if self._train is None:
+            return IndexToken(self._table_epoch, 0, 1)
+        eng = self._row_sparse_engine()
+        return IndexToken(self._table_epoch, self._train.flags_epoch - self._flags_epoch0, eng.step_number() if eng is not None else None)
+
+    def _sync_refusal(self, token, now):
+        """Why the rows moved since `token` cannot be read off row-sparse Adam's flags (a string), or None where they can."""
+        if self._row_sparse_engine() is None:
+            return "no training engine yet" if self._train is None else "dense Adam moves every row of the item table in every step"
+        if token is None or token.step is None or now.step is None:
+            return "the index carries no step to count from (it was loaded, built from a bare table, or built under dense Adam)"
+        if token.table_epoch != now.table_epoch:
+            return ("the item table was replaced since (table epoch %d, now %d: load / load_tf_checkpoint / load_params)"
+                    % (token.table_epoch, now.table_epoch))
+        if token.flags_epoch != now.flags_epoch:
+            return "row-sparse Adam's flags were cleared since (flags epoch %d, now %d: set_step)" % (token.flags_epoch, now.flags_epoch)
+        return None
+
+    def refresh_item_index(self, index):
+        """Brings an ItemIndex of the item table (build_item_index) in step with the parameters, in place, and returns how: "sync" --
+        under row-sparse Adam, when the index's token and the model agree on both epochs, only the 16-row tiles holding a row that a
+        step since the token moved are rewritten (ItemIndex.sync with the engine's lazy_flags, since=token.step) -- else "rebuild"
+        (ItemIndex.rebuild: the whole blob again, no allocation).  Either way the blob ends as the bytes of a fresh build_item_index(),
+        and index.version / index.token are the model's.  Nothing refreshes by itself: recommend(index=) keeps refusing a stale
+        index.  An ItemSubset gathered from the index earlier stays the snapshot it was."""
+        from .index import ItemIndex
+        if not isinstance(index, ItemIndex):
+            raise TypeError("refresh_item_index takes an ItemIndex (an ItemSubset is a snapshot: gather it again)")
+        self._check_index_shape(index)
+        table, now = self._owner.p("item_emb"), self._index_token()
+        if self._sync_refusal(index.token, now) is None:
+            index.sync(table, self._train.lazy_flags, since=index.token.step, version=self._param_version)
+            how = "sync"
+        else:
+            index.rebuild(table, version=self._param_version)
+            how = "rebuild"
+        index.token = now
+        return how
+
+    def item_delta(self, token):
+        """The item rows that training moved since `token` (an ItemIndex.token, or the token of the last call), for an index held where
+        no table is -- an ItemIndex.load-ed serving process runs ix.update(ids, rows=rows): returns (ids, rows, token_now), ids an int32
+        CUDA tensor [n] (possibly empty), rows float32 [n, D], token_now to pass next time.  RuntimeError, naming the reason, where
+        the flags cannot say which rows moved (dense Adam, a table load or cleared flags since the token): send the whole index."""
+        now = self._index_token()
+        why = self._sync_refusal(token, now)
+        if why is not None:
+            raise RuntimeError("item_delta: %s; rebuild and send the whole index" % why)
+        ids = torch.nonzero(self._train.lazy_flags >= int(token.step)).reshape(-1)
+        return ids.to(torch.int32), self._owner.p("item_emb")[ids], now
+
+    def _check_index_shape(self, index):
+        V = getattr(index, "parent_V", None) or index.V
+        if (V, index.D) != (self.itemnum + 1, self._owner.D):
+            raise ValueError("index of a [%d, %d] table, the model's item table is [%d, %d]"
+                             % (V, index.D, self.itemnum + 1, self._owner.D))
 
     def _check_index(self, index):
         """index: None, an ItemIndex or an ItemSubset (its parent_V is the table it refers to)."""
         if index is None:
             return
-        V = getattr(index, "parent_V", None) or index.V
-        if (V, index.D) != (self.itemnum + 1, self._owner.D):
-            raise ValueError("index of a [%d, %d] table, the model's item table is [%d, %d]"
-                             % (V, index.D, self.itemnum + 1, self._owner.D))
+        self._check_index_shape(index)
         if index.version is not None and index.version != self._param_version:
             raise RuntimeError("stale index: built at parameter version %d, the model is at %d (build_item_index() again)"
                                % (index.version, self._param_version))
@@ -363,6 +439,7 @@ class _Model(object):
             else:
                 self._pending_opt = (d["M"], d["V"], nxt)
         self._param_version += 1
+        self._table_epoch += 1
 
     def load_tf_checkpoint(self, prefix):
         """Loads a checkpoint written by the reference (tf.train.Saver bundle `<prefix>.index` +
@@ -393,6 +470,7 @@ class _Model(object):
             else:
                 self._pending_opt = (M, V, steps + 1)
         self._param_version += 1
+        self._table_epoch += 1
 
     def get_params(self):
         return self._owner.get_params()
@@ -400,6 +478,7 @@ class _Model(object):
     def load_params(self, d):
         self._owner.load_params(d)
         self._param_version += 1
+        self._table_epoch += 1
 
 
 class SASRec(_Model):

@@ -251,6 +251,60 @@ def topk_index_gather(ids, precision=L.PREC_BF16X3, table=None, index=None, inde
     return out
 
 
+def _index_blob(index, V, D, precision):
+    if not torch.is_tensor(index) or index.dtype != torch.uint8 or not index.is_cuda or not index.is_contiguous():
+        raise TypeError("index must be a contiguous uint8 CUDA tensor")
+    if index.numel() != topk_index_bytes(V, D, precision):
+        raise ValueError("index of %d bytes is not an index of V=%d D=%d precision=%d" % (index.numel(), V, D, precision))
+
+
+def topk_index_update(index, V, D, precision, ids, src, packed):
+    """cr_topk_index_update: rewrites rows ids (an int32 CUDA tensor [n], n >= 1; ids outside 0 .. V-1 are skipped) of `index`, the
+    uint8 CUDA blob of a [V, D] table built with `precision`, in place.  src: a contiguous float32 CUDA tensor -- the [V, D] table
+    (packed False: the source row of ids[j] is ids[j]) or [n, D] rows in list order (packed True: the source row of ids[j] is j)."""
+    V, D, precision = int(V), int(D), int(precision)
+    _index_blob(index, V, D, precision)
+    if not torch.is_tensor(ids) or not torch.is_tensor(src):
+        raise TypeError("ids must be an int32 CUDA tensor and src a float32 CUDA tensor")
+    _i32(ids, "ids")
+    if ids.dim() != 1 or not ids.is_contiguous() or ids.numel() < 1:
+        raise ValueError("ids must be a contiguous [n] tensor, n >= 1")
+    n = ids.numel()
+    _f32(src, "src")
+    want = (n, D) if packed else (V, D)
+    if tuple(src.shape) != want or not src.is_contiguous():
+        raise ValueError("src must be a contiguous [%d, %d] tensor (%s), got %s"
+                         % (want + ("packed rows" if packed else "the table", tuple(src.shape))))
+    if ids.device != index.device or src.device != index.device:
+        raise ValueError("index, ids and src must be on one device")
+    L.call("cr_topk_index_update", _p(src), 1 if packed else 0, V, D, precision, index.data_ptr(), index.numel(), ids.data_ptr(), n,
+           _stream())
+    return index
+
+
+def topk_index_sync(index, table, precision, flags, since):
+    """cr_topk_index_sync: rewrites in place every 16-row tile of `index` (the uint8 CUDA blob of table [V, D], built with `precision`)
+    that has a row with (uint32) flags[r] >= since.  table: a contiguous float32 CUDA tensor [V, D]; flags: an int32 CUDA tensor [V]
+    (Engine.lazy_flags)."""
+    if not torch.is_tensor(table) or not torch.is_tensor(flags):
+        raise TypeError("table must be a float32 CUDA tensor and flags an int32 CUDA tensor")
+    _f32(table, "table")
+    if table.dim() != 2 or not table.is_contiguous():
+        raise ValueError("table must be a contiguous [V, D] tensor")
+    V, D = table.shape
+    precision, since = int(precision), int(since)
+    _index_blob(index, V, D, precision)
+    _i32(flags, "flags")
+    if tuple(flags.shape) != (V,) or not flags.is_contiguous():
+        raise ValueError("flags must be a contiguous [V = %d] tensor, got %s" % (V, tuple(flags.shape)))
+    if not 0 <= since <= 0xffffffff:
+        raise ValueError("since=%d must fit an unsigned 32-bit step number" % since)
+    if flags.device != index.device or table.device != index.device:
+        raise ValueError("index, table and flags must be on one device")
+    L.call("cr_topk_index_sync", _p(table), V, D, precision, index.data_ptr(), index.numel(), flags.data_ptr(), since, _stream())
+    return index
+
+
 def softmax_ce_workspace_bytes(M, V, D):
     n = L.lib.cr_softmax_ce_workspace(M, V, D)
     if n == 0:

@@ -247,7 +247,8 @@ def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256, use_index=F
     """Full-ranking form of _evaluate: the same users (those its next call samples) and inputs, the target ranked against EVERY item outside the user's `rated`
     set (the set the sampled evaluator draws its 100 negatives outside of) instead of against 100 of them.  Draws nothing from
     np.random.  rank = #{eligible i : s_i > s_t} + #{eligible i != t : s_i == s_t, i < t} (castrec.h cr_score_topk).
-    use_index: one ItemIndex of the item table, built here, serves every batch (same ranks, bit for bit)."""
+    use_index: one ItemIndex of the item table serves every batch (same ranks, bit for bit) -- True: built here; an ItemIndex: the
+    caller's, brought in step first (model.refresh_item_index: under row-sparse Adam only the moved rows' tiles are rewritten)."""
     train, valid, test, usernum, itemnum = dataset[0], dataset[1], dataset[2], dataset[3], dataset[4]
     min_td, max_td = get_delta_range(train)
     rows = []
@@ -256,7 +257,11 @@ def _evaluate_full(model, dataset, args, mode, k=10, eval_batch=256, use_index=F
         if r is not None:
             rows.append((u,) + r)
     NDCG = HT = 0.0
-    kw = {"index": model.build_item_index()} if use_index else {}
+    if use_index is True or use_index is False or use_index is None:
+        kw = {"index": model.build_item_index()} if use_index else {}
+    else:
+        model.refresh_item_index(use_index)
+        kw = {"index": use_index}
     for i in range(0, len(rows), eval_batch):
         chunk = rows[i:i + eval_batch]
         us = [c[0] for c in chunk]

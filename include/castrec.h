@@ -506,6 +506,26 @@ int cr_topk_index_build(const float* table, int V, int D, int precision, void* i
 int cr_topk_index_gather(const float* table, const void* index, int index_precision, int V, int D,
                          const int32_t* ids, int n, int precision, void* out_index, size_t out_bytes, void* stream);
 
+/* ---- keeping an index in step with its table: row updates and flag sync (csrc/cr_topk.hip) ----------------------------
+ * Every row of an index has its own 16-byte groups (NK per plane), so a row is rewritten in place and the result is the rebuild's.
+ * index: an index of a [V, D] table built with `precision`; index_bytes must equal cr_topk_index_bytes(V, D, precision).  The
+ * written bytes are those cr_topk_index_build gives for that row (same code); everything else in the blob keeps its bytes.
+ *   - cr_topk_index_update: rewrites the rows ids[0 .. n-1] (device int32, n >= 1).  packed == 0: src is the [V, D] fp32 table
+ *     and the source row of ids[j] is ids[j]; packed != 0: src is [n, D] fp32 and the source row of ids[j] is j -- a delta sent
+ *     without the table.  An id outside 0 .. V-1 is skipped: its source row is not read and no address is formed from it.
+ *     Duplicates are allowed where they name the same source bytes; otherwise the winner is unspecified (nothing is written
+ *     outside those rows' groups).  Exactly the named rows' groups are written: both planes of a split index, column padding +0.
+ *     One asynchronous launch, a wave per 16 ids.
+ *   - cr_topk_index_sync: rewrites, whole, every tile of 16 rows that has a row r < V with (uint32_t)flags[r] >= since.  flags:
+ *     device int32 [V] in the form of cr_adam_desc.lazy_flags (the number of the last step that moved row r), never read at or
+ *     beyond V.  A tile without such a row is not written and its table rows are not read.  Under row-sparse Adam the other rows of
+ *     a rewritten tile are unchanged, so the result is the rebuild's.  One asynchronous launch, a wave per tile.
+ * Checked before any device call, as everything else. */
+int cr_topk_index_update(const float* src, int packed, int V, int D, int precision, void* index, size_t index_bytes,
+                         const int32_t* ids, int n, void* stream);
+int cr_topk_index_sync(const float* table, int V, int D, int precision, void* index, size_t index_bytes,
+                       const int32_t* flags, uint32_t since, void* stream);
+
 /* ---- top-K over per-query candidate lists (csrc/cr_topk.hip) ---------------------------------------------------------
  * "The best K among THIS row's candidates": row b's candidates are cand_ids[cand_off[b] .. cand_off[b + 1]), in any order.  The
  * rows a list names are gathered -- from the fp32 table or from an item index of it -- and scored 16 at a time against the query;

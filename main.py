@@ -56,7 +56,7 @@ def parse_args(argv=None):
     parser.add_argument('--eval_full_ranking', action='store_true',
                         help='also log NDCG@10 / HR@10 over the full catalogue (every item outside the user\'s rated set) at each evaluation')
     parser.add_argument('--eval_index', action='store_true',
-                        help='with --eval_full_ranking: build one item index per evaluation and rank every batch against it (same metrics)')
+                        help='with --eval_full_ranking: keep one item index for the run, refresh it in place before each evaluation and rank every batch against it (same metrics)')
     parser.add_argument('--loss', default='bce', choices=['bce', 'ce', 'sampled_ce', 'gbce'],
                         help='training objective: bce = the reference\'s pos / neg BCE with one sampled negative; ce = softmax '
                              'cross-entropy over the whole item catalogue; sampled_ce = softmax cross-entropy over the target and '
@@ -133,6 +133,16 @@ def main(argv=None):
                               '{}_{}'.format(args.train_dir, now.strftime("%m-%d-%Y-%H-%M-%S")))
     save_path = os.path.join(files_path, 'model.ckpt')
 
+    kept_index = []
+    def eval_index():
+        # --eval_index: one ItemIndex for the whole run, refreshed in place before each full-ranking evaluation (its bits are the
+        # table's, so the logged numbers are those of an index built per evaluation)
+        if not args.eval_index:
+            return False
+        if not kept_index:
+            kept_index.append(model.build_item_index())
+        return kept_index[0]
+
     if args.test_model:                                            # main.py:161-189
         ck = os.path.join(args.test_model, 'model.ckpt')
         if os.path.exists(ck) or os.path.exists(ck + '.index'):
@@ -144,7 +154,7 @@ def main(argv=None):
             u, seq, pos, neg, timeseq, ratings_seq, hours_seq, days_seq, _ = sampler.next_batch()
             auc, loss = model.train_step(u, seq, pos, neg, timeseq, hours_seq, days_seq)   # the reference's one-train-step quirk
             print(auc); print(loss)
-            f_test = evaluate_full(model, dataset, args, use_index=args.eval_index) if args.eval_full_ranking else None   # (same users: it restores `random`)
+            f_test = evaluate_full(model, dataset, args, use_index=eval_index()) if args.eval_full_ranking else None   # (same users: it restores `random`)
             t_test = evaluate(model, dataset, args)
             logger.info('test (NDCG@10: %.4f, HR@10: %.4f)' % (t_test[0], t_test[1]))
             if f_test is not None:
@@ -206,9 +216,9 @@ def main(argv=None):
                 logger.info('Model saved in path: %s' % model.save(save_path))
                 logger.info('Evaluating')
                 T += time.time() - t0
-                f_test = evaluate_full(model, dataset, args, use_index=args.eval_index) if args.eval_full_ranking else None
+                f_test = evaluate_full(model, dataset, args, use_index=eval_index()) if args.eval_full_ranking else None
                 t_test = evaluate(model, dataset, args)
-                f_valid = evaluate_valid_full(model, dataset, args, use_index=args.eval_index) if args.eval_full_ranking else None
+                f_valid = evaluate_valid_full(model, dataset, args, use_index=eval_index()) if args.eval_full_ranking else None
                 t_valid = evaluate_valid(model, dataset, args)
                 logger.info('epoch:%d, time: %f(s), valid (NDCG@10: %.4f, HR@10: %.4f), test (NDCG@10: %.4f, HR@10: %.4f)' % (
                     epoch, T, t_valid[0], t_valid[1], t_test[0], t_test[1]))
