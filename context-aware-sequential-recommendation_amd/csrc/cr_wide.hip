@@ -902,6 +902,14 @@ __global__ __launch_bounds__((WdCfg<NCT, 1>::NT)) void k_wide_ffn_bwd(cr_block_b
         bd.g_ln2_b[o] = tot[1];
         if (wgrad) { bd.g_b2[o] = tot[2]; bd.g_b1[o] = tot[3]; }
     }
+    if constexpr (WG) {
+        // a workgroup without a row block (n_slabs > nblk) never reached wg_product: its weight-gradient slab is zeros, written like
+        // every other slab (cr_adam_step / cr_reduce_slabs read all n_slabs)
+        if ((int)blockIdx.x >= nblk) {
+            const size_t so = (size_t)blockIdx.x * bd.slab_stride;
+            for (int i = threadIdx.x; i < D * D; i += WdCfg<NCT, 1>::NT) { bd.g_w1[so + i] = 0.0f; bd.g_w2[so + i] = 0.0f; }
+        }
+    }
 }
 
 // =====================================================================================================
@@ -1017,6 +1025,12 @@ __global__ __launch_bounds__((WdCfg<NCT, 1>::NT)) void k_wide_qkv_bwd(cr_block_b
         bd.g_ln1_g[o] = tot[0];
         bd.g_ln1_b[o] = tot[1];
         if (wgrad) { bd.g_bqkv[o] = tot[2]; bd.g_bqkv[o + D] = tot[3]; bd.g_bqkv[o + 2 * D] = tot[4]; }
+    }
+    if constexpr (WG) {
+        if ((int)blockIdx.x >= nblk) {                    // no row block: a zero slab, as in k_wide_ffn_bwd
+            const size_t so = (size_t)blockIdx.x * bd.slab_stride;
+            for (int i = threadIdx.x; i < 3 * D * D; i += WdCfg<NCT, 1>::NT) bd.g_wqkv[so + i] = 0.0f;
+        }
     }
 }
 

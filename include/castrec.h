@@ -321,6 +321,10 @@ typedef struct {
                                                   the softmax-backward row term the single-pass cr_attn_bwd needs */
     const float* dq_part;                      /* optional [M,D], read by qkv_bwd: second partial of dQ (added to dqkv's dQ rows) */
 } cr_block_bwd_desc;
+/* For every row-phase entry point of this header (cr_block_*, cr_stack_ffn_bwd* / cr_stack_qkv_bwd*, cr_wide_*): row buffers, weights
+ * and slabs need 4-byte alignment only; each backward call writes all n_slabs slabs of every gradient it forms, exact zeros where a
+ * workgroup owns no row (cr_adam_step / cr_reduce_slabs read them all); a call that returns an error has launched nothing and
+ * leaves every output as it was. */
 int cr_block_ln_ffn_bwd(const cr_block_bwd_desc* d, void* stream);
 int cr_block_ln_qkv_bwd(const cr_block_bwd_desc* d, void* stream);
 

@@ -1,4 +1,4 @@
-"""What the per-op GPU tests share (test_ops_gpu, test_attn_bf_gpu, test_row_ops_gpu, test_gemm_gpu): device arrays, a fresh state
+"""What the per-op GPU tests share (test_ops_gpu, test_attn_bf_gpu, test_row_ops_gpu, test_gemm_gpu, test_block_rows_gpu): device arrays, a fresh state
 block, the relative error, sentinel-filled buffers and the fp64 attention core."""
 import numpy as np
 import torch
