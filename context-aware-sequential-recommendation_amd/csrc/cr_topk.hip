@@ -87,9 +87,55 @@ __device__ __forceinline__ void tk_idx_store(bf8* idx, int64_t plane, int tile, 
     }
 }
 
-// The fragments of one row per lane (li): from the table as tk_row_issue / tk_row_finish give them, from the index by 16-byte gathers
-// of the same groups; a lane without a row (!rok) gets zeros.
-template <int NK, bool SPLIT, bool IDX>
+// The cosine form of tk_row_finish (castrec.h CR_INDEX_COSINE; the index writers alone): the masked row is scaled by the reciprocal of
+// its norm before the split, so the index holds the fragments of x / ||x||.  The arithmetic is fixed -- tests/topk_cosine_ref.py
+// restates it in numpy and the blob is compared byte for byte -- and nothing of it may be contracted into an fma (hipcc's default):
+//   lane (li, lg):  p = 0; for ks ascending, j = 0 .. 7 ascending: p = p + v * v     (a rounded product, then a rounded sum)
+//   the row's four lanes:  p += p of lane ^ 16, then p += p of lane ^ 32: ss = (p_lg + p_lg^1) + (p_lg^2 + p_lg^3), the same bits in all four
+//   inv = ss > 0 ? 1 / sqrt(ss) : 0   (correctly rounded square root, then correctly rounded division);  y = v * inv
+// A zero row -- row 0, a lane without a row, an ss that underflows to 0 -- stays zero.  The two exchanges need all 64 lanes of the wave
+// active: the callers' exits ahead of this are wave-uniform, and the one divergent branch here (the last row's refill) has ended.
+template <int NK>
+__device__ __forceinline__ float tk_inv_norm(const float (&v)[NK][8]) {
+#pragma clang fp contract(off)
+    float p = 0.0f;
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float sq = v[ks][j] * v[ks][j];
+            p = p + sq;
+        }
+    }
+    p = p + __shfl_xor(p, 16, 64);
+    p = p + __shfl_xor(p, 32, 64);
+    return p > 0.0f ? 1.0f / sqrtf(p) : 0.0f;
+}
+template <int NK, bool SPLIT>
+__device__ __forceinline__ void tk_row_finish_cos(float (&v)[NK][8], const float* src, int64_t ld, int row, bool rok, bool last, int D,
+                                                  bf8 (&hi)[NK], bf8 (&lo)[NK]) {
+#pragma clang fp contract(off)
+    const int lg = (threadIdx.x & 63) >> 4;
+    const float* p = src + (rok ? (int64_t)row * ld : 0);
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+        const int c = 32 * ks + 8 * lg;
+        const bool fix = item_fix(rok, last, c, D);
+        item_mask(v[ks], c, D, rok, fix);
+        if (fix) item_refill(v[ks], p, c, D);          // the partial chunk of the matrix's last row (one lane group of the grid)
+    }
+    const float inv = tk_inv_norm<NK>(v);
+#pragma unroll
+    for (int ks = 0; ks < NK; ++ks) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[ks][j] = v[ks][j] * inv;      // rounded here: split8's x - hi never sees an unrounded product
+        split8<SPLIT>(v[ks], hi[ks], lo[ks]);
+    }
+}
+
+// The fragments of one row per lane (li): from the table as tk_row_issue / tk_row_finish give them (COS: tk_row_finish_cos, the
+// writers of a cosine index), from the index by 16-byte gathers of the same groups; a lane without a row (!rok) gets zeros.
+template <int NK, bool SPLIT, bool IDX, bool COS = false>
 __device__ __forceinline__ void tk_src_row(const TkSrc& s, int row, bool rok, bf8 (&hi)[NK], bf8 (&lo)[NK]) {
     if constexpr (IDX) {
         const int lg = (threadIdx.x & 63) >> 4, r = rok ? row : 0;
@@ -107,7 +153,8 @@ __device__ __forceinline__ void tk_src_row(const TkSrc& s, int row, bool rok, bf
     } else {
         float v[NK][8];
         tk_row_issue<NK>(v, s.table, s.D, row, rok, row == s.V - 1, s.D);
-        tk_row_finish<NK, SPLIT>(v, s.table, s.D, row, rok, row == s.V - 1, s.D, hi, lo);
+        if constexpr (COS) tk_row_finish_cos<NK, SPLIT>(v, s.table, s.D, row, rok, row == s.V - 1, s.D, hi, lo);
+        else tk_row_finish<NK, SPLIT>(v, s.table, s.D, row, rok, row == s.V - 1, s.D, hi, lo);
     }
 }
 
@@ -445,7 +492,7 @@ __global__ __launch_bounds__(256) void k_topk_merge(TkArgs a) {
 // (the build: rows >= V and columns >= D are +0); with ids it is ids[r - 1], the index of the table {0; row ids[0]; ...; row
 // ids[n - 1]} -- no source row, so +0, for r = 0, r > n and an id outside 1 .. V-1.  A row's fragments depend on that row alone, so
 // the gathered bytes are the build's on the gathered table, whether they come from the table or (IDX) from an index of it.
-template <int NK, bool SPLIT, bool IDX>
+template <int NK, bool SPLIT, bool IDX, bool COS>
 __global__ __launch_bounds__(256) void k_topk_index_write(TkSrc s, const int32_t* ids, int n, bf8* idx, int64_t plane, int n_tiles) {
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= n_tiles) return;                           // wave-uniform
@@ -453,7 +500,7 @@ __global__ __launch_bounds__(256) void k_topk_index_write(TkSrc s, const int32_t
     const int row = !ids ? r : (r >= 1 && r <= n) ? ids[r - 1] : 0;
     const bool rok = row < s.V && (!ids || row >= 1);
     bf8 h[NK], lo[NK];
-    tk_src_row<NK, SPLIT, IDX>(s, row, rok, h, lo);        // (a lane without a row reads nothing at `row`)
+    tk_src_row<NK, SPLIT, IDX, COS>(s, row, rok, h, lo);   // (a lane without a row reads nothing at `row`)
     tk_idx_store<NK, SPLIT>(idx, plane, tile, h, lo);
 }
 
@@ -476,21 +523,21 @@ __device__ __forceinline__ void tk_idx_row_store(bf8* idx, int64_t plane, int r,
 // The rows a list names: a wave takes 16 ids, lane li the id ids[16 w + li].  s is the fp32 source: the [V, D] table (source row =
 // the id) or, packed, the [n, D] rows in list order (source row = the position; s.V == n, so the re-read of the source's last row is
 // the build's).  An id outside 0 .. V-1, and a lane past the list, has no row: nothing of it is read or written.
-template <int NK, bool SPLIT>
+template <int NK, bool SPLIT, bool COS>
 __global__ __launch_bounds__(256) void k_topk_index_update(TkSrc s, int packed, int V, const int32_t* ids, int n, bf8* idx, int64_t plane) {
     const int64_t j = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 16 + (threadIdx.x & 15);
     const int id = j < n ? ids[j] : -1;
     const bool rok = (unsigned)id < (unsigned)V;
     const int row = !rok ? 0 : packed ? (int)j : id;
     bf8 h[NK], lo[NK];
-    tk_src_row<NK, SPLIT, false>(s, row, rok, h, lo);
+    tk_src_row<NK, SPLIT, false, COS>(s, row, rok, h, lo);
     tk_idx_row_store<NK, SPLIT>(idx, plane, id, rok, h, lo);
 }
 
 // The tiles a flag array names: a wave per tile, rewritten whole -- the build's body, full 1 KB runs -- when any of its rows r < V has
 // (uint32_t)flags[r] >= since (cr_adam_desc.lazy_flags: the number of the last step that moved row r).  The test is wave-uniform; a
 // tile without such a row is left alone and its table rows are not read.
-template <int NK, bool SPLIT>
+template <int NK, bool SPLIT, bool COS>
 __global__ __launch_bounds__(256) void k_topk_index_sync(TkSrc s, const int32_t* flags, uint32_t since, bf8* idx, int64_t plane) {
     const int tile = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (tile >= s.n_tiles) return;                         // wave-uniform
@@ -499,7 +546,7 @@ __global__ __launch_bounds__(256) void k_topk_index_sync(TkSrc s, const int32_t*
     const bool hit = rok && (uint32_t)flags[rok ? r : 0] >= since;
     if (__ballot(hit) == 0) return;                        // wave-uniform
     bf8 h[NK], lo[NK];
-    tk_src_row<NK, SPLIT, false>(s, r, rok, h, lo);
+    tk_src_row<NK, SPLIT, false, COS>(s, r, rok, h, lo);
     tk_idx_store<NK, SPLIT>(idx, plane, tile, h, lo);
 }
 
@@ -531,6 +578,16 @@ int tk_check_shape(const char* who, int V, int D, int precision) {
     CR_REQUIRE(V >= 1, "%s: V=%d must be >= 1", who, V);
     CR_REQUIRE(tk_index_planes(precision) != 0, "%s: unknown precision %d", who, precision);
     return CR_OK;
+}
+
+// A writer's `precision` argument (castrec.h CR_INDEX_COSINE): the CR_PREC_* value alone, or the flag OR-ed onto CR_PREC_BF16X3 /
+// CR_PREC_BF16 for an index of normalised rows.  Strips the flag from exactly those two values; anything else -- the flag alone, another
+// bit, a negative number -- stays whole for tk_check_shape to refuse as the unknown precision it is.
+bool tk_writer_cosine(int& precision) {
+    const int base = precision ^ CR_INDEX_COSINE;
+    if (base != CR_PREC_BF16X3 && base != CR_PREC_BF16) return false;
+    precision = base;
+    return true;
 }
 
 struct TkGeom {
@@ -570,14 +627,16 @@ void tk_launch(const TkArgs& a, const TkGeom& g, hipStream_t st) {
     hipLaunchKernelGGL((k_topk_merge<NK, SPLIT, IDX>), dim3((a.B + 3) / 4), dim3(256), 0, st, a);
 }
 
-// the index of `rows` rows in `planes` planes, written from src: row for row (ids NULL) or from rows ids[0 .. n-1] behind a zero row
-void tk_index_write(const TkSrc& src, const int32_t* ids, int n, void* out, int rows, int planes, hipStream_t st) {
+// the index of `rows` rows in `planes` planes, written from src: row for row (ids NULL) or from rows ids[0 .. n-1] behind a zero row;
+// cosine: table rows are normalised (the rows of an index source are what they are)
+void tk_index_write(const TkSrc& src, const int32_t* ids, int n, void* out, int rows, int planes, bool cosine, hipStream_t st) {
     const TkIdxGeom g = tk_index_geom(rows, src.D);
     const dim3 grid((g.n_tiles + 3) / 4);
     bf8* idx = static_cast<bf8*>(out);
     tk_dispatch(g.NK, planes == 2, [&](auto nk, auto sp) {
-        if (src.idx) hipLaunchKernelGGL((k_topk_index_write<nk, sp, true>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
-        else hipLaunchKernelGGL((k_topk_index_write<nk, sp, false>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
+        if (src.idx) hipLaunchKernelGGL((k_topk_index_write<nk, sp, true, false>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
+        else if (cosine) hipLaunchKernelGGL((k_topk_index_write<nk, sp, false, true>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
+        else hipLaunchKernelGGL((k_topk_index_write<nk, sp, false, false>), grid, dim3(256), 0, st, src, ids, n, idx, g.plane, g.n_tiles);
     });
 }
 
@@ -591,10 +650,11 @@ extern "C" size_t cr_topk_index_bytes(int V, int D, int precision) {
 
 extern "C" int cr_topk_index_build(const float* table, int V, int D, int precision, void* index, size_t index_bytes, void* stream) {
     CR_REQUIRE(table && index, "cr_topk_index_build: NULL table or index");
+    const bool cosine = tk_writer_cosine(precision);
     if (const int rc = tk_check_shape("cr_topk_index_build", V, D, precision)) return rc;
     const size_t need = cr_topk_index_bytes(V, D, precision);
     CR_REQUIRE(index_bytes >= need, "cr_topk_index_build: index of %zu bytes, cr_topk_index_bytes says %zu", index_bytes, need);
-    tk_index_write(tk_source(table, nullptr, V, D), nullptr, 0, index, V, tk_index_planes(precision), cr_stream(stream));
+    tk_index_write(tk_source(table, nullptr, V, D), nullptr, 0, index, V, tk_index_planes(precision), cosine, cr_stream(stream));
     return cr_check_launch("cr_topk_index_build");
 }
 
@@ -603,6 +663,7 @@ extern "C" int cr_topk_index_gather(const float* table, const void* index, int i
     CR_REQUIRE((table != nullptr) != (index != nullptr), "cr_topk_index_gather: exactly one source, table or index, must be non-NULL (%s)",
                table ? "both given" : "both NULL");
     CR_REQUIRE(ids && out_index, "cr_topk_index_gather: NULL ids or out_index");
+    const bool cosine = tk_writer_cosine(precision);      // (an index source is copied: its rows carry their metric already)
     if (const int rc = tk_check_shape("cr_topk_index_gather", V, D, precision)) return rc;
     CR_REQUIRE(n >= 1 && n < 0x7fffffff, "cr_topk_index_gather: n=%d must be >= 1 (and n + 1 an int)", n);
     const int planes = tk_index_planes(precision);
@@ -614,13 +675,14 @@ extern "C" int cr_topk_index_gather(const float* table, const void* index, int i
     const size_t need = cr_topk_index_bytes(n + 1, D, precision);
     CR_REQUIRE(out_bytes >= need, "cr_topk_index_gather: out_index of %zu bytes, cr_topk_index_bytes(n + 1 = %d) says %zu", out_bytes,
                n + 1, need);
-    tk_index_write(tk_source(table, index, V, D), ids, n, out_index, n + 1, planes, cr_stream(stream));
+    tk_index_write(tk_source(table, index, V, D), ids, n, out_index, n + 1, planes, cosine, cr_stream(stream));
     return cr_check_launch("cr_topk_index_gather");
 }
 
 extern "C" int cr_topk_index_update(const float* src, int packed, int V, int D, int precision, void* index, size_t index_bytes,
                                     const int32_t* ids, int n, void* stream) {
     CR_REQUIRE(src && index && ids, "cr_topk_index_update: NULL src, index or ids");
+    const bool cosine = tk_writer_cosine(precision);
     if (const int rc = tk_check_shape("cr_topk_index_update", V, D, precision)) return rc;
     CR_REQUIRE(n >= 1, "cr_topk_index_update: n=%d must be >= 1", n);
     const size_t need = cr_topk_index_bytes(V, D, precision);
@@ -632,7 +694,8 @@ extern "C" int cr_topk_index_update(const float* src, int packed, int V, int D, 
     bf8* idx = static_cast<bf8*>(index);
     hipStream_t st = cr_stream(stream);
     tk_dispatch(g.NK, tk_index_planes(precision) == 2, [&](auto nk, auto sp) {
-        hipLaunchKernelGGL((k_topk_index_update<nk, sp>), grid, dim3(256), 0, st, s, packed ? 1 : 0, V, ids, n, idx, g.plane);
+        if (cosine) hipLaunchKernelGGL((k_topk_index_update<nk, sp, true>), grid, dim3(256), 0, st, s, packed ? 1 : 0, V, ids, n, idx, g.plane);
+        else hipLaunchKernelGGL((k_topk_index_update<nk, sp, false>), grid, dim3(256), 0, st, s, packed ? 1 : 0, V, ids, n, idx, g.plane);
     });
     return cr_check_launch("cr_topk_index_update");
 }
@@ -640,6 +703,7 @@ extern "C" int cr_topk_index_update(const float* src, int packed, int V, int D, 
 extern "C" int cr_topk_index_sync(const float* table, int V, int D, int precision, void* index, size_t index_bytes, const int32_t* flags,
                                   uint32_t since, void* stream) {
     CR_REQUIRE(table && index && flags, "cr_topk_index_sync: NULL table, index or flags");
+    const bool cosine = tk_writer_cosine(precision);
     if (const int rc = tk_check_shape("cr_topk_index_sync", V, D, precision)) return rc;
     const size_t need = cr_topk_index_bytes(V, D, precision);
     CR_REQUIRE(index_bytes == need, "cr_topk_index_sync: index_bytes=%zu, cr_topk_index_bytes(V=%d, D=%d) says %zu", index_bytes, V, D,
@@ -649,7 +713,8 @@ extern "C" int cr_topk_index_sync(const float* table, int V, int D, int precisio
     bf8* idx = static_cast<bf8*>(index);
     hipStream_t st = cr_stream(stream);
     tk_dispatch(tk_nk(D), tk_index_planes(precision) == 2, [&](auto nk, auto sp) {
-        hipLaunchKernelGGL((k_topk_index_sync<nk, sp>), grid, dim3(256), 0, st, s, flags, since, idx, s.plane);
+        if (cosine) hipLaunchKernelGGL((k_topk_index_sync<nk, sp, true>), grid, dim3(256), 0, st, s, flags, since, idx, s.plane);
+        else hipLaunchKernelGGL((k_topk_index_sync<nk, sp, false>), grid, dim3(256), 0, st, s, flags, since, idx, s.plane);
     });
     return cr_check_launch("cr_topk_index_sync");
 }

@@ -28,9 +28,24 @@ import torch
 from . import lib as L
 from . import ops as O
 
-FORMAT = 1
+FORMAT = 1                       # a dot-product index: meta = [1, V, D, precision], the file this module has always written
+FORMAT_METRIC = 2                # any other metric: one more meta entry, the metric's code
 PRECISIONS = {"bf16x3": L.PREC_BF16X3, "bf16": L.PREC_BF16, "f32": L.PREC_BF16X3}
 _NAMES = {L.PREC_BF16X3: "bf16x3", L.PREC_BF16: "bf16"}
+METRIC_CODES = {"dot": 0, "cosine": 1}
+_METRIC_NAMES = {c: m for m, c in METRIC_CODES.items()}
+
+
+def _metric(m):
+    if m not in METRIC_CODES:
+        raise ValueError("metric must be one of %s, got %r" % (sorted(METRIC_CODES), m))
+    return m
+
+
+def _file_metric(path, code):
+    if code not in _METRIC_NAMES:
+        raise ValueError("%s: unknown metric code %d (this build knows %s)" % (path, code, _METRIC_NAMES))
+    return _METRIC_NAMES[code]
 
 
 def _prec(p):
@@ -248,10 +263,13 @@ class ItemIndex(object):
     """V, D: the table's shape; precision: "bf16x3" (hi + lo planes: serves every search precision) or "bf16" (hi only, half the bytes:
     plain-bf16 searches only); blob: the uint8 tensor of castrec.h's layout; version: the parameter version of the model that built it
     (Model.build_item_index), None for an index that was loaded or built from a bare table; token: what the blob is in step with,
-    for Model.refresh_item_index / item_delta (models.IndexToken; None: unknown, a refresh rebuilds)."""
+    for Model.refresh_item_index / item_delta (models.IndexToken; None: unknown, a refresh rebuilds).  metric: "dot" -- the blob
+    holds the table's rows x -- or "cosine" -- it holds x / ||x||, normalised on the device as the blob is written (castrec.h
+    CR_INDEX_COSINE: same size, same layout, same search kernels).  update / sync / rebuild and subset carry the index's own metric."""
 
-    def __init__(self, V, D, precision, blob, version=None):
+    def __init__(self, V, D, precision, blob, version=None, metric="dot"):
         self.V, self.D, self.precision, self.blob, self.version = int(V), int(D), _NAMES[_prec(precision)], blob, version
+        self.metric = _metric(metric)
         self.token = None
         need = L.lib.cr_topk_index_bytes(self.V, self.D, self.prec)
         if need == 0 or blob.numel() != need or blob.dtype != torch.uint8:
@@ -263,27 +281,31 @@ class ItemIndex(object):
         return PRECISIONS[self.precision]
 
     @classmethod
-    def build(cls, table, precision="bf16x3", version=None):
+    def build(cls, table, precision="bf16x3", version=None, metric="dot"):
+        """The index of table (a float32 CUDA tensor [V, D]).  metric="cosine": of its rows normalised, x / ||x|| (a zero row stays
+        zero), without a normalised copy of the table: one pass, the same bytes of index."""
+        _metric(metric)
         if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2:
             raise TypeError("ItemIndex.build takes a float32 CUDA tensor [V, D]")
         table = table.contiguous()
         p = _prec(precision)
-        return cls(table.shape[0], table.shape[1], p, O.topk_index_build(table, p), version)
+        return cls(table.shape[0], table.shape[1], p, O.topk_index_build(table, p, metric=metric), version, metric)
 
     def subset(self, ids):
         """An ItemSubset of the items `ids` (any iterable of ids in 1 .. V-1), gathered out of this index: no table needed.  The
-        subset inherits precision and version."""
+        subset inherits precision, version and metric (the rows of a cosine index are normalised already: they are copied)."""
         if not self.blob.is_cuda:
             raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to gather a subset")
         m = torch.from_numpy(subset_ids(ids, self.V)).to(self.blob.device)
         with torch.cuda.device(self.blob.device):
             blob = O.topk_index_gather(m[1:], self.prec, index=self.blob, index_precision=self.prec, V=self.V, D=self.D)
-        return ItemSubset(ItemIndex(m.numel(), self.D, self.prec, blob, self.version), m, self.V, self.version)
+        return ItemSubset(ItemIndex(m.numel(), self.D, self.prec, blob, self.version, self.metric), m, self.V, self.version)
 
     # -- keeping the index in step with its table (castrec.h cr_topk_index_update / cr_topk_index_sync): a row's groups are its own, so
     # the blob is rewritten in place, no allocation, and holds the bytes of a fresh build of the table.  An ItemSubset gathered
     # earlier (subset(), search(allow=)) has its own blob: it stays the snapshot it was.  version: stored in self.version (None for
-    # an index that follows no model); Model.refresh_item_index drives sync / rebuild and sets it.
+    # an index that follows no model); Model.refresh_item_index drives sync / rebuild and sets it.  All three write with the index's own
+    # metric and take RAW rows: a cosine index normalises them as its build did, so one delta (Model.item_delta) serves either kind.
     def _writable(self, what):
         if not self.blob.is_cuda:
             raise RuntimeError("this ItemIndex was loaded on the CPU (inspection only): load it with device='cuda' to %s it" % what)
@@ -324,7 +346,7 @@ class ItemIndex(object):
         ids = (ids if torch.is_tensor(ids) else torch.from_numpy(ids.astype(np.int32))).to(dev).contiguous()
         src = src.to(dev).contiguous() if rows is not None else self._table(table)
         with torch.cuda.device(dev):
-            O.topk_index_update(self.blob, self.V, self.D, self.prec, ids, src, packed=rows is not None)
+            O.topk_index_update(self.blob, self.V, self.D, self.prec, ids, src, packed=rows is not None, metric=self.metric)
         self.version = version
         return self
 
@@ -335,7 +357,7 @@ class ItemIndex(object):
         row are neither read nor written.  An ItemSubset gathered earlier stays the snapshot it was."""
         self._writable("sync")
         with torch.cuda.device(self.blob.device):
-            O.topk_index_sync(self.blob, self._table(table), self.prec, flags, since)
+            O.topk_index_sync(self.blob, self._table(table), self.prec, flags, since, metric=self.metric)
         self.version = version
         return self
 
@@ -344,13 +366,15 @@ class ItemIndex(object):
         allocation.  An ItemSubset gathered earlier stays the snapshot it was."""
         self._writable("rebuild")
         with torch.cuda.device(self.blob.device):
-            O.topk_index_build(self._table(table), self.prec, out=self.blob)
+            O.topk_index_build(self._table(table), self.prec, out=self.blob, metric=self.metric)
         self.version = version
         return self
 
     def search(self, queries, k, exclude=None, targets=None, precision=None, allow=None, candidates=None):
         """The k best items for each query row (dot product), as Model.recommend returns them: numpy (ids [B, k], scores [B, k]) and,
-        with targets, each target's rank.  exclude: None or one iterable of ids per row.  precision: the search arithmetic, by
+        with targets, each target's rank.  On a cosine index the dot product is with the normalised rows: a score is q . x / ||x||
+        = cos(q, x) ||q||, so the order within a row is the cosine order; the queries are not normalised here (divide a row's scores
+        by ||q|| for cosines; Model.similar_items(metric="cosine") does).  exclude: None or one iterable of ids per row.  precision: the search arithmetic, by
         default the index's own.  allow: an iterable of ids -- the best k among those items only, for every row: shorthand for
         self.subset(allow).search(...) (keep the ItemSubset to search the same set again).  candidates: one iterable of ids per
         row -- the best k among THAT row's candidates (minus the row's exclude; a target outside them has rank -1), or a prebuilt
@@ -363,28 +387,34 @@ class ItemIndex(object):
         return _search_numpy(self, queries, k, exclude, targets, precision, candidates)
 
     def save(self, path):
-        """One uncompressed .npz: blob (uint8) and meta = [format, V, D, precision]."""
+        """One uncompressed .npz: blob (uint8) and meta = [1, V, D, precision] for a dot-product index (format 1, unchanged), meta =
+        [2, V, D, precision, metric code] (format 2; cosine: 1) otherwise."""
+        meta = [FORMAT, self.V, self.D, self.prec] if self.metric == "dot" else \
+            [FORMAT_METRIC, self.V, self.D, self.prec, METRIC_CODES[self.metric]]
         with open(path, "wb") as f:
-            np.savez(f, blob=self.blob.cpu().numpy(), meta=np.array([FORMAT, self.V, self.D, self.prec], np.int64))
+            np.savez(f, blob=self.blob.cpu().numpy(), meta=np.array(meta, np.int64))
         return path
 
     @classmethod
     def load(cls, path, device="cuda"):
-        """device="cpu" only inspects the file (V, D, precision, blob); such an index does not search.  version is None."""
+        """device="cpu" only inspects the file (V, D, precision, metric, blob); such an index does not search.  version is None."""
         with np.load(path) as z:
             meta = [int(x) for x in z["meta"]]
-            if len(meta) != 4 or meta[0] != FORMAT:
-                raise ValueError("%s: item index format %s, this build reads format %d" % (path, meta[:1], FORMAT))
-            _, V, D, p = meta
+            if not ((len(meta) == 4 and meta[0] == FORMAT) or (len(meta) == 5 and meta[0] == FORMAT_METRIC and "ids" not in z.files)):
+                raise ValueError("%s: item index format %s with %d meta entries, this build reads format %d (4 entries) and %d (5; "
+                                 "an ItemSubset file loads with ItemSubset.load)" % (path, meta[:1], len(meta), FORMAT, FORMAT_METRIC))
+            V, D, p = meta[1:4]
+            metric = _file_metric(path, meta[4]) if len(meta) == 5 else "dot"
             need = L.lib.cr_topk_index_bytes(V, D, p) if p in _NAMES else 0
             blob = z["blob"]
             if need == 0 or blob.dtype != np.uint8 or blob.size != need:
                 raise ValueError("%s: blob of %d bytes does not fit its meta V=%d D=%d precision=%d (%d bytes)"
                                  % (path, blob.size, V, D, p, need))
-        return cls(V, D, p, torch.from_numpy(np.ascontiguousarray(blob)).to(device), None)
+        return cls(V, D, p, torch.from_numpy(np.ascontiguousarray(blob)).to(device), None, metric)
 
 
-SUBSET_FORMAT = 1
+SUBSET_FORMAT = 1                # a subset of dot-product rows: meta = [1, n + 1, D, precision, parent_V]
+SUBSET_FORMAT_METRIC = 2         # any other metric: a sixth meta entry, the metric's code
 
 
 class ItemSubset(object):
@@ -412,10 +442,13 @@ class ItemSubset(object):
     D = property(lambda self: self.index.D)
     precision = property(lambda self: self.index.precision)
     prec = property(lambda self: self.index.prec)
+    metric = property(lambda self: self.index.metric)
 
     @classmethod
-    def build(cls, table, ids, precision="bf16x3", version=None):
-        """From the fp32 table itself (a float32 CUDA tensor [V, D]): only the subset's rows are read, no full index is needed."""
+    def build(cls, table, ids, precision="bf16x3", version=None, metric="dot"):
+        """From the fp32 table itself (a float32 CUDA tensor [V, D]): only the subset's rows are read, no full index is needed.
+        metric="cosine": the gathered rows are normalised as ItemIndex.build(metric="cosine") normalises them."""
+        _metric(metric)
         if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.float32 or table.dim() != 2:
             raise TypeError("ItemSubset.build takes a float32 CUDA tensor [V, D]")
         table = table.contiguous()
@@ -423,8 +456,8 @@ class ItemSubset(object):
         V, D = table.shape
         m = torch.from_numpy(subset_ids(ids, V)).to(table.device)
         with torch.cuda.device(table.device):
-            blob = O.topk_index_gather(m[1:], p, table=table)
-        return cls(ItemIndex(m.numel(), D, p, blob, version), m, V, version)
+            blob = O.topk_index_gather(m[1:], p, table=table, metric=metric)
+        return cls(ItemIndex(m.numel(), D, p, blob, version, metric), m, V, version)
 
     def search(self, queries, k, exclude=None, targets=None, precision=None):
         """ItemIndex.search among the subset's items: global ids in, global ids out.  An excluded id outside the subset is ignored; a
@@ -432,10 +465,13 @@ class ItemSubset(object):
         return _search_numpy(self, queries, k, exclude, targets, precision)
 
     def save(self, path):
-        """One uncompressed .npz: blob (uint8), ids (int32 [n + 1]) and meta = [format, n + 1, D, precision, parent_V]."""
+        """One uncompressed .npz: blob (uint8), ids (int32 [n + 1]) and meta = [1, n + 1, D, precision, parent_V] for dot-product rows
+        (format 1, unchanged), meta = [2, n + 1, D, precision, parent_V, metric code] (format 2; cosine: 1) otherwise."""
+        meta = [SUBSET_FORMAT, self.index.V, self.D, self.prec, self.parent_V]
+        if self.metric != "dot":
+            meta = [SUBSET_FORMAT_METRIC] + meta[1:] + [METRIC_CODES[self.metric]]
         with open(path, "wb") as f:
-            np.savez(f, blob=self.index.blob.cpu().numpy(), ids=self._map,
-                     meta=np.array([SUBSET_FORMAT, self.index.V, self.D, self.prec, self.parent_V], np.int64))
+            np.savez(f, blob=self.index.blob.cpu().numpy(), ids=self._map, meta=np.array(meta, np.int64))
         return path
 
     @classmethod
@@ -443,10 +479,12 @@ class ItemSubset(object):
         """device="cpu" only inspects the file; such a subset does not search.  version is None."""
         with np.load(path) as z:
             meta = [int(x) for x in z["meta"]]
-            if len(meta) != 5 or meta[0] != SUBSET_FORMAT or "ids" not in z.files:
-                raise ValueError("%s: not an item subset file of format %d (meta %s; an ItemIndex file loads with ItemIndex.load)"
-                                 % (path, SUBSET_FORMAT, meta))
-            _, V, D, p, parent_V = meta
+            if "ids" not in z.files or not ((len(meta) == 5 and meta[0] == SUBSET_FORMAT) or
+                                            (len(meta) == 6 and meta[0] == SUBSET_FORMAT_METRIC)):
+                raise ValueError("%s: not an item subset file of format %d or %d (meta %s; an ItemIndex file loads with ItemIndex.load)"
+                                 % (path, SUBSET_FORMAT, SUBSET_FORMAT_METRIC, meta))
+            V, D, p, parent_V = meta[1:5]
+            metric = _file_metric(path, meta[5]) if len(meta) == 6 else "dot"
             need = L.lib.cr_topk_index_bytes(V, D, p) if p in _NAMES else 0
             blob, ids = z["blob"], z["ids"]
             if need == 0 or blob.dtype != np.uint8 or blob.size != need:
@@ -454,5 +492,5 @@ class ItemSubset(object):
                                  % (path, blob.size, V, D, p, need))
             if ids.dtype != np.int32:
                 raise ValueError("%s: ids of type %s, int32 expected" % (path, ids.dtype))
-        index = ItemIndex(V, D, p, torch.from_numpy(np.ascontiguousarray(blob)).to(device), None)
+        index = ItemIndex(V, D, p, torch.from_numpy(np.ascontiguousarray(blob)).to(device), None, metric)
         return cls(index, torch.from_numpy(np.ascontiguousarray(ids)).to(device), parent_V, None)

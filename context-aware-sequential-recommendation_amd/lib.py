@@ -32,6 +32,7 @@ CR_SCE_MAX_SAMPLES = 16384       # castrec.h: sample ids per cr_sampled_ce call 
 CR_SCE_SITE = 0x5CE00000         # castrec.h: the cr_site_key site of cr_sampled_ce's device draw
 CR_GBCE_SITE = 0x6BCE0000        # castrec.h: the cr_site_key site of cr_gbce's device draw
 PREC_F32, PREC_BF16X3, PREC_BF16 = 0, 1, 2
+INDEX_COSINE = 0x100             # castrec.h CR_INDEX_COSINE: OR-ed into the precision of the four item-index writers
 ELT_COPY, ELT_ADD, ELT_DROPOUT, ELT_RELU_BWD, ELT_ROWMASK, ELT_GRADPREP = 0, 1, 2, 3, 4, 5
 
 

@@ -240,17 +240,23 @@ class _Model(object):
                                      want_attn=want_attention)
         return self._eval[key]
 
-    def build_item_index(self, precision=None):
+    def build_item_index(self, precision=None, metric="dot"):
         """An ItemIndex (castrec_amd.index) of the current item table for recommend(index=), similar_items(index=) and
         ItemIndex.search / save.  precision: "bf16x3" or "bf16"; by default what the engine's top-K computes in ("bf16" at
-        attn_precision "bf16").  The index is a snapshot: it records the parameter version, and recommend refuses it once a
-        training step or a load has changed the parameters."""
+        attn_precision "bf16").  metric: "dot", the table's rows as the model scores them, or "cosine", the rows normalised as the
+        index is written (item-to-item similarity: similar_items; no normalised copy of the table is made).  The index is a
+        snapshot: it records the parameter version, and recommend refuses it once a training step or a load has changed the
+        parameters; refresh_item_index brings either kind back in step."""
         from .index import ItemIndex
         if precision is None:
-            precision = "bf16" if self._owner.attn_precision == "bf16" else "bf16x3"
-        ix = ItemIndex.build(self._owner.p("item_emb"), precision, version=self._param_version)
+            precision = self._index_precision()
+        ix = ItemIndex.build(self._owner.p("item_emb"), precision, version=self._param_version, metric=metric)
         ix.token = self._index_token()
         return ix
+
+    def _index_precision(self):
+        """The precision of an index or subset made for one call: what the engine's top-K computes in."""
+        return "bf16" if self._owner.attn_precision == "bf16" else "bf16x3"
 
     def _row_sparse_engine(self):
         """The training engine where it runs row-sparse Adam (its lazy_flags name the rows a step moved), else None."""
@@ -281,8 +287,9 @@ class _Model(object):
         """Brings an ItemIndex of the item table (build_item_index) in step with the parameters, in place, and returns how: "sync" --
         under row-sparse Adam, when the index's token and the model agree on both epochs, only the 16-row tiles holding a row that a
         step since the token moved are rewritten (ItemIndex.sync with the engine's lazy_flags, since=token.step) -- else "rebuild"
-        (ItemIndex.rebuild: the whole blob again, no allocation).  Either way the blob ends as the bytes of a fresh build_item_index(),
-        and index.version / index.token are the model's.  Nothing refreshes by itself: recommend(index=) keeps refusing a stale
+        (ItemIndex.rebuild: the whole blob again, no allocation).  Either way the blob ends as the bytes of a fresh build_item_index()
+        of the index's precision and metric (a cosine index is written from the raw table rows, normalised as its build normalised
+        them), and index.version / index.token are the model's.  Nothing refreshes by itself: recommend(index=) keeps refusing a stale
         index.  An ItemSubset gathered from the index earlier stays the snapshot it was."""
         from .index import ItemIndex
         if not isinstance(index, ItemIndex):
@@ -300,7 +307,8 @@ class _Model(object):
 
     def item_delta(self, token):
         """The item rows that training moved since `token` (an ItemIndex.token, or the token of the last call), for an index held where
-        no table is -- an ItemIndex.load-ed serving process runs ix.update(ids, rows=rows): returns (ids, rows, token_now), ids an int32
+        no table is -- an ItemIndex.load-ed serving process runs ix.update(ids, rows=rows), whatever the index's metric (the rows are
+        raw table rows; a cosine index normalises them as it writes): returns (ids, rows, token_now), ids an int32
         CUDA tensor [n] (possibly empty), rows float32 [n, D], token_now to pass next time.  RuntimeError, naming the reason, where
         the flags cannot say which rows moved (dense Adam, a table load or cleared flags since the token): send the whole index."""
         now = self._index_token()
@@ -325,9 +333,10 @@ class _Model(object):
             raise RuntimeError("stale index: built at parameter version %d, the model is at %d (build_item_index() again)"
                                % (index.version, self._param_version))
 
-    def _allowed(self, allow, index):
+    def _allowed(self, allow, index, metric="dot"):
         """What recommend / similar_items search: `index` itself without allow; with allow (an ItemSubset, or an iterable of item ids)
-        the ItemSubset -- gathered out of `index` when there is one, else from the item table's rows."""
+        the ItemSubset -- gathered out of `index` when there is one (it inherits the index's metric), else from the item table's rows
+        with `metric`."""
         from .index import ItemSubset
         self._check_index(index)
         if allow is None:
@@ -339,36 +348,59 @@ class _Model(object):
             if isinstance(index, ItemSubset):
                 raise ValueError("allow= with index= an ItemSubset: pass one subset")
             return index.subset(allow)
-        return ItemSubset.build(self._owner.p("item_emb"), allow, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3",
-                                version=self._param_version)
+        return ItemSubset.build(self._owner.p("item_emb"), allow, self._index_precision(), version=self._param_version, metric=metric)
 
-    def similar_items(self, ids, k=10, index=None, allow=None, candidates=None):
-        """The k items whose table rows have the largest dot product with each given item's own row (the model's geometry: the scores
-        of recommend with the item's vector as the query), the item itself left out.  Returns numpy (ids [n, k], scores [n, k]).
-        index: an ItemIndex of the table to search instead of one built for this call.  allow: an iterable of item ids or an
-        ItemSubset -- the k most similar among those items only (one set for every row).  candidates: one iterable of item ids
-        per given item -- the k most similar among that item's own candidates (the table's rows are gathered unless index is
-        given); one filter per call, allow or candidates."""
-        from .index import ItemIndex, search
+    def similar_items(self, ids, k=10, index=None, allow=None, candidates=None, metric=None):
+        """The k items most similar to each given item, the item itself left out.  Returns numpy (ids [n, k], scores [n, k]).
+        metric: "dot" -- the largest dot product of the table rows (the model's geometry: the scores of recommend with the item's
+        vector as the query; large-norm items come out similar to everything) -- or "cosine" -- the largest cosine, and the scores
+        are cosines: the search runs on an index of normalised rows and its scores q . x / ||x|| are divided by the query rows' fp32
+        norms (a query row of norm 0 gets scores 0).  None: the metric of the index or ItemSubset that is given, "dot" without one.
+        index: an ItemIndex of the table (build_item_index, of either metric) to search instead of one built for this call.  allow:
+        an iterable of item ids or an ItemSubset -- the k most similar among those items only (one set for every row).  candidates:
+        one iterable of item ids per given item -- the k most similar among that item's own candidates (under "dot" the table's
+        rows are gathered unless index is given; under "cosine" an index is built for the call unless one is given); one filter
+        per call, allow or candidates.  ValueError when an explicit metric differs from that of a given index or ItemSubset."""
+        from .index import ItemIndex, ItemSubset, _metric, search
         ids = np.asarray(ids, np.int64).ravel()
         if ids.size == 0 or ids.min() < 1 or ids.max() > self.itemnum:
             raise ValueError("ids must be item ids in 1 .. %d" % self.itemnum)
         if candidates is not None and allow is not None:
             raise ValueError("one filter per call: allow= or candidates=")
-        index = self._allowed(allow, index)
+        if metric is not None:
+            _metric(metric)
+        for what, given in (("index=", index), ("allow=", allow if isinstance(allow, ItemSubset) else None)):
+            if given is None:
+                continue
+            if metric is not None and given.metric != metric:
+                raise ValueError("similar_items(metric=%r) with %s of metric %r: search an index of the metric that is asked for, "
+                                 "or leave metric=None" % (metric, what + " " + type(given).__name__, given.metric))
+            metric = given.metric
+        metric = metric or "dot"
+        index = self._allowed(allow, index, metric)
         table = self._owner.p("item_emb")
         q = table[torch.from_numpy(ids).to(table.device)]
+        if metric == "cosine" and index is None:
+            index = ItemIndex.build(table, self._index_precision(), metric="cosine")
+
+        def scores(sc):                                   # q . x / ||x|| -> cosines
+            if metric != "cosine":
+                return sc
+            sc = sc if torch.is_tensor(sc) else torch.from_numpy(sc).to(q.device)
+            qn = torch.linalg.vector_norm(q, dim=1, keepdim=True)
+            return torch.where(qn > 0, sc / torch.where(qn > 0, qn, torch.ones_like(qn)), torch.zeros_like(sc)).cpu().numpy()
         if candidates is not None:
             from .index import PRECISIONS, _is_prebuilt, candidates_for, excl_csr
             n = ids.size
             cand = candidates_for(candidates, n, self.itemnum + 1, *((None, None) if _is_prebuilt(candidates) else excl_csr([[int(i)] for i in ids], n)))
-            prec = index.prec if index is not None else PRECISIONS["bf16" if self._owner.attn_precision == "bf16" else "bf16x3"]
+            prec = index.prec if index is not None else PRECISIONS[self._index_precision()]
             top, sc, _ = search(q, q.shape[1], n, int(k), table if index is None else index, prec, self._owner,
                                 cand_off=cand[0], cand_ids=cand[1])
-            return top.cpu().numpy(), sc.cpu().numpy()
+            return top.cpu().numpy(), scores(sc) if metric == "cosine" else sc.cpu().numpy()
         if index is None:
-            index = ItemIndex.build(table, "bf16" if self._owner.attn_precision == "bf16" else "bf16x3")
-        return index.search(q, int(k), exclude=[[int(i)] for i in ids])
+            index = ItemIndex.build(table, self._index_precision())
+        top, sc = index.search(q, int(k), exclude=[[int(i)] for i in ids])
+        return top, scores(sc)
 
     def recommend(self, u, seq, k=10, timeseq=None, hours_seq=None, days_seq=None, exclude="history", return_scores=True,
                   targets=None, index=None, allow=None, candidates=None):
@@ -377,7 +409,8 @@ class _Model(object):
         of each row of seq), None, or one iterable of ids per row.  Returns numpy (ids [B, k], scores [B, k]) -- ids only when
         return_scores is False -- and, with targets ([B] ids), a third array: each target's 0-based rank among the eligible items
         (-1 for an excluded target).  Rows with fewer than k eligible items end in id 0, score -inf.  index: an ItemIndex of the item
-        table (build_item_index): same results, the table's rows are not converted again.  allow: an iterable of item ids or an
+        table (build_item_index): same results, the table's rows are not converted again.  An index of metric "cosine" is taken as
+        well, for models trained on normalised item scores: the scores are then seq_emb . x / ||x||.  allow: an iterable of item ids or an
         ItemSubset (castrec_amd.index) -- the best k among those items only, one set shared by every row (a list per row goes
         through candidates=); it combines with exclude, a target outside it has rank -1 and ranks count the set's eligible items.
         With an iterable the subset is gathered for this call (out of index when given): keep an ItemSubset to reuse it.

@@ -208,8 +208,19 @@ def topk_index_bytes(V, D, precision=L.PREC_BF16X3):
     return n
 
 
-def topk_index_build(table, precision=L.PREC_BF16X3, out=None):
-    """cr_topk_index_build: the item index of table [V, D] (a contiguous float32 CUDA tensor) as a uint8 CUDA tensor."""
+METRICS = {"dot": 0, "cosine": L.INDEX_COSINE}     # what an index's rows hold: x, or x / ||x|| (castrec.h CR_INDEX_COSINE)
+
+
+def _writer_precision(precision, metric):
+    """The `precision` argument of the four index writers: the CR_PREC_* value with the metric's flag OR-ed in."""
+    if metric not in METRICS:
+        raise ValueError("metric must be one of %s, got %r" % (sorted(METRICS), metric))
+    return int(precision) | METRICS[metric]
+
+
+def topk_index_build(table, precision=L.PREC_BF16X3, out=None, metric="dot"):
+    """cr_topk_index_build: the item index of table [V, D] (a contiguous float32 CUDA tensor) as a uint8 CUDA tensor.  metric
+    "cosine": the index of the rows x / ||x|| (castrec.h CR_INDEX_COSINE); the same size, searched by the same calls."""
     _f32(table, "table")
     if table.dim() != 2 or not table.is_contiguous():
         raise ValueError("table must be a contiguous [V, D] tensor")
@@ -217,15 +228,18 @@ def topk_index_build(table, precision=L.PREC_BF16X3, out=None):
     n = topk_index_bytes(V, D, precision)
     if out is None:
         out = torch.empty(n, dtype=torch.uint8, device=table.device)
-    L.call("cr_topk_index_build", _p(table), V, D, precision, out.data_ptr(), out.numel(), _stream())
+    L.call("cr_topk_index_build", _p(table), V, D, _writer_precision(precision, metric), out.data_ptr(), out.numel(), _stream())
     return out
 
 
-def topk_index_gather(ids, precision=L.PREC_BF16X3, table=None, index=None, index_precision=None, V=None, D=None, out=None):
+def topk_index_gather(ids, precision=L.PREC_BF16X3, table=None, index=None, index_precision=None, V=None, D=None, out=None,
+                      metric="dot"):
     """cr_topk_index_gather: the index of {0; source row ids[0]; ...} as a uint8 CUDA tensor.  ids: an int32 CUDA tensor [n] of ids in
     1 .. V-1.  The source is `table` (a contiguous float32 CUDA tensor [V, D]) or `index` (a uint8 CUDA tensor from topk_index_build
-    of a [V, D] table, built with index_precision) -- exactly one."""
+    of a [V, D] table, built with index_precision) -- exactly one.  metric "cosine": rows read from a table are normalised; the rows
+    of an index source are copied as they are (a sub-index of a cosine index is a cosine index whatever is said here)."""
     _i32(ids, "ids")
+    wprec = _writer_precision(precision, metric)
     if (table is None) == (index is None):
         raise ValueError("topk_index_gather takes exactly one source: table or index")
     if table is not None:
@@ -246,7 +260,7 @@ def topk_index_gather(ids, precision=L.PREC_BF16X3, table=None, index=None, inde
     nb = topk_index_bytes(n + 1, D, precision)
     if out is None:
         out = torch.empty(nb, dtype=torch.uint8, device=ids.device)
-    L.call("cr_topk_index_gather", _p(table), _p(index), index_precision, V, D, ids.data_ptr(), n, precision, out.data_ptr(), out.numel(),
+    L.call("cr_topk_index_gather", _p(table), _p(index), index_precision, V, D, ids.data_ptr(), n, wprec, out.data_ptr(), out.numel(),
            _stream())
     return out
 
@@ -258,11 +272,13 @@ def _index_blob(index, V, D, precision):
         raise ValueError("index of %d bytes is not an index of V=%d D=%d precision=%d" % (index.numel(), V, D, precision))
 
 
-def topk_index_update(index, V, D, precision, ids, src, packed):
+def topk_index_update(index, V, D, precision, ids, src, packed, metric="dot"):
     """cr_topk_index_update: rewrites rows ids (an int32 CUDA tensor [n], n >= 1; ids outside 0 .. V-1 are skipped) of `index`, the
     uint8 CUDA blob of a [V, D] table built with `precision`, in place.  src: a contiguous float32 CUDA tensor -- the [V, D] table
-    (packed False: the source row of ids[j] is ids[j]) or [n, D] rows in list order (packed True: the source row of ids[j] is j)."""
+    (packed False: the source row of ids[j] is ids[j]) or [n, D] rows in list order (packed True: the source row of ids[j] is j).
+    metric: the metric `index` was built with -- "cosine" normalises the raw rows of src as the build did."""
     V, D, precision = int(V), int(D), int(precision)
+    wprec = _writer_precision(precision, metric)
     _index_blob(index, V, D, precision)
     if not torch.is_tensor(ids) or not torch.is_tensor(src):
         raise TypeError("ids must be an int32 CUDA tensor and src a float32 CUDA tensor")
@@ -277,15 +293,16 @@ def topk_index_update(index, V, D, precision, ids, src, packed):
                          % (want + ("packed rows" if packed else "the table", tuple(src.shape))))
     if ids.device != index.device or src.device != index.device:
         raise ValueError("index, ids and src must be on one device")
-    L.call("cr_topk_index_update", _p(src), 1 if packed else 0, V, D, precision, index.data_ptr(), index.numel(), ids.data_ptr(), n,
+    L.call("cr_topk_index_update", _p(src), 1 if packed else 0, V, D, wprec, index.data_ptr(), index.numel(), ids.data_ptr(), n,
            _stream())
     return index
 
 
-def topk_index_sync(index, table, precision, flags, since):
+def topk_index_sync(index, table, precision, flags, since, metric="dot"):
     """cr_topk_index_sync: rewrites in place every 16-row tile of `index` (the uint8 CUDA blob of table [V, D], built with `precision`)
     that has a row with (uint32) flags[r] >= since.  table: a contiguous float32 CUDA tensor [V, D]; flags: an int32 CUDA tensor [V]
-    (Engine.lazy_flags)."""
+    (Engine.lazy_flags).  metric: the metric `index` was built with, as in topk_index_update."""
+    wprec = _writer_precision(precision, metric)
     if not torch.is_tensor(table) or not torch.is_tensor(flags):
         raise TypeError("table must be a float32 CUDA tensor and flags an int32 CUDA tensor")
     _f32(table, "table")
@@ -301,7 +318,7 @@ def topk_index_sync(index, table, precision, flags, since):
         raise ValueError("since=%d must fit an unsigned 32-bit step number" % since)
     if flags.device != index.device or table.device != index.device:
         raise ValueError("index, table and flags must be on one device")
-    L.call("cr_topk_index_sync", _p(table), V, D, precision, index.data_ptr(), index.numel(), flags.data_ptr(), since, _stream())
+    L.call("cr_topk_index_sync", _p(table), V, D, wprec, index.data_ptr(), index.numel(), flags.data_ptr(), since, _stream())
     return index
 
 

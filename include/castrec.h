@@ -530,6 +530,28 @@ int cr_topk_index_update(const float* src, int packed, int V, int D, int precisi
 int cr_topk_index_sync(const float* table, int V, int D, int precision, void* index, size_t index_bytes,
                        const int32_t* flags, uint32_t since, void* stream);
 
+/* ---- cosine index: rows normalised as the index is written (csrc/cr_topk.hip) -----------------------------------------
+ * CR_INDEX_COSINE is OR-ed into the `precision` argument of the four writers -- cr_topk_index_build, cr_topk_index_gather,
+ * cr_topk_index_update, cr_topk_index_sync -- beside CR_PREC_BF16X3 or CR_PREC_BF16 (the flag alone, 0x100, is refused: name the
+ * base precision; any other bit is an unknown precision, as before).  The blob then holds, in the layout above, hi = bf16(y) and
+ * lo = bf16(y - hi) of y = x / ||x|| instead of x.  Nothing else changes: the size is cr_topk_index_bytes of the base precision, and
+ * cr_score_topk / cr_score_topk_lists search such a blob as any other (they take no flag, the same kernels run): a score is
+ * q . y = cos(q, x) ||q||, so the order within a query is the cosine order; divide by ||q|| for the cosine itself.  A writer must be
+ * given the flag the index was built with: update and sync take RAW rows and normalise them the same way, so the blob ends as the
+ * bytes of a fresh cosine build.  cr_topk_index_gather normalises rows it reads from a table; from an index source the flag is
+ * accepted and ignored (the fragments are copied: a sub-index of a cosine index is a cosine index).
+ * The arithmetic, all fp32, round to nearest even, no fused multiply-add, subnormals kept -- a caller can reproduce the bytes:
+ *   - the row is first masked as for any index (+0 at columns >= D); a lane l of the row's tile holds columns 32 ks + 8 (l >> 4) + j;
+ *   - per lane group lg = 0 .. 3: p_lg = 0, then for ks = 0 .. NK-1 ascending and j = 0 .. 7 ascending  p_lg = p_lg + (v * v),
+ *     v the element at column 32 ks + 8 lg + j, the product rounded before the sum;
+ *   - ss = (p_0 + p_1) + (p_2 + p_3)   (two exchanges between lanes: distance 16, then 32; every lane of the row ends with these bits);
+ *   - inv = ss > 0 ? 1 / sqrt(ss) : 0, the square root correctly rounded, then the division correctly rounded;
+ *   - y = v * inv, rounded; then hi / lo as above.
+ * A row of zeros stays zeros (row 0 of an embedding table; also a row whose ss underflows to 0).  Multiplying a row by a power of
+ * two leaves its bytes unchanged as long as nothing overflows or goes subnormal.  Error of the stored row against x / ||x|| in exact
+ * arithmetic: at most 2^-16.6 |y_c| (split) or 2^-8 |y_c| (plain, bf16's own rounding) per element. */
+#define CR_INDEX_COSINE 0x100
+
 /* ---- top-K over per-query candidate lists (csrc/cr_topk.hip) ---------------------------------------------------------
  * "The best K among THIS row's candidates": row b's candidates are cand_ids[cand_off[b] .. cand_off[b + 1]), in any order.  The
  * rows a list names are gathered -- from the fp32 table or from an item index of it -- and scored 16 at a time against the query;
